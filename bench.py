@@ -573,6 +573,24 @@ def measure_mfma(N: int, W: int, timeout_s: float):
     return out or None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_dump(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (world_index: float64).  All arrays are indexed by world on their first axis; past
+    DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of worlds is kept from each, and its indices go to world_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    worlds = next(iter(arrays.values())).shape[0]
+    if total > DUMP_LIMIT_BYTES - (1 << 20):
+        keep = max(1, worlds * (DUMP_LIMIT_BYTES - (1 << 20)) // (total + 8 * worlds))
+        idx = np.sort(np.random.default_rng(0).choice(worlds, size=keep, replace=False))
+        arrays = dict({name: a[idx] for name, a in arrays.items()}, world_index=idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64 if name == "world_index" else np.float32))
+
+
 def main() -> None:
     if len(sys.argv) >= 6 and sys.argv[1] == "--cpu-worker":        # child of cpu_baseline_all_cores: no torch, no GPU
         print(cpu_baseline(int(sys.argv[2]), int(sys.argv[3]), float(sys.argv[4]), int(sys.argv[5]))["value"])
@@ -614,7 +632,8 @@ def main() -> None:
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N>1 (nccl = RCCL over xGMI; gloo only for dry runs of the N>1 code path)")
     ap.add_argument("--share-device", action="store_true",
-                    help="dry run: every rank uses cuda:0 (exercises the multi-rank logic on a 1-GPU box; needs --backend gloo)")
+                    help="dry run: the ranks share the visible devices, rank r on cuda:(r %% devices) (on a 1-GPU box every rank uses cuda:0: "
+                         "exercises the multi-rank logic there; needs --backend gloo)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launch / rendezvous / collective check of the N>1 path without touching a GPU (CPU boxes, gloo)")
     ap.add_argument("--pmc-child", default="", choices=["", "step", "mfma"], help=argparse.SUPPRESS)
@@ -627,6 +646,10 @@ def main() -> None:
     ap.add_argument("--no-preroll", action="store_true", help="skip the synchronised pre-roll that takes the batch past its first wave of restarts")
     ap.add_argument("--overwrite-outputs", action="store_true",
                     help="round-2 form: every step of a launch overwrites ONE output slot (only the last step's outputs survive)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned at its last step (first repetition: the state after preroll + warmup + K steps, "
+                         "the same in every run with the same arguments) as DIR/<name>.npy -- rank 0's view: its own shard of the worlds, "
+                         "or with the gather in the timed region the records of all ranks it received")
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child(args)
@@ -661,7 +684,7 @@ def main() -> None:
     from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
     from rl_collision_avoidance_amd.config import EnvConfig
     if args.share_device:
-        local_rank = 0
+        local_rank %= torch.cuda.device_count()
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
     if world_size > 1:
@@ -837,8 +860,10 @@ def main() -> None:
     acts_l = acts[:spl].contiguous()
 
     def run_steps_gather(k):
+        blocks = None
         for _ in range(-(-k // spl)):
-            sh.gathered_blocks(sh.step_and_gather(acts_l if spl > 1 else acts_l[0], root=sh._root))   # (waits for it; rank-major views, no copy)
+            blocks = sh.gathered_blocks(sh.step_and_gather(acts_l if spl > 1 else acts_l[0], root=sh._root))   # (waits for it; rank-major views, no copy)
+        return blocks
 
     def coll_device():
         return device if (world_size > 1 and args.backend == "nccl") else "cpu"
@@ -913,14 +938,16 @@ def main() -> None:
                 by_len[n_l] = env.prepared_autoreset_n(acts, n_l, slots=slots)
             prepared.append(by_len[n_l])
 
+    last = {}                                                # what the region's last launch returned (a reference: nothing is copied on the clock)
+
     def timed_once():
         sync_all()
         t0 = time.perf_counter()
         if gather_in_metric:
-            run_steps_gather(args.steps)
+            last["out"] = run_steps_gather(args.steps)
         else:
             for launch in prepared:
-                launch()
+                last["out"] = launch()
         sync_all()
         dt = time.perf_counter() - t0
         if world_size > 1:
@@ -929,7 +956,19 @@ def main() -> None:
             dt = float(t.item())
         return dt
 
+    def last_step_outputs(out):
+        """host float32 copies of the last timed step's outputs: obs [W,N,1+D], rewards [W,N], done [W,N], game_over [W]; with the
+        gather in the region, the receiving rank's packed records of all ranks' worlds in global order [total,N,1+D+2] (None elsewhere)"""
+        if gather_in_metric:
+            return None if out is None else {"packed": torch.cat([b[-1] for b in out], dim=0).float().cpu().numpy()}
+        obs, rew, done, go = out
+        if slots is not None:                                # per-step slots: the region's last step wrote slot n-1 of the last launch
+            n_last = (args.steps - 1) % min(acts.shape[0], slots.steps) + 1
+            obs, rew, done, go = obs[n_last - 1], rew[n_last - 1], done[n_last - 1], go[n_last - 1]
+        return {name: t.float().cpu().numpy() for name, t in (("obs", obs), ("rewards", rew), ("done", done), ("game_over", go))}
+
     import gc
+    dumped = None
     times, restarts = [], []
     reps = max(1, args.reps) | 1
     r = 0
@@ -940,6 +979,8 @@ def main() -> None:
         before = episodes_started()
         times.append(timed_once())
         restarts.append(episodes_started() - before)
+        if r == 0 and args.dump_outputs:
+            dumped = last_step_outputs(last["out"])          # (between repetitions, off the clock)
         if r == 0 and reps > 3:                              # bound the whole measurement to ~5 s of timed work (same count on every rank)
             reps = max(3, min(reps, int(5.0 / max(times[0], 1e-9)) + 1)) | 1      # odd: the median is a repetition that really ran
             if world_size > 1:
@@ -949,6 +990,8 @@ def main() -> None:
         r += 1
     if gc_was_on:
         gc.enable()
+    if dumped is not None and rank == 0:
+        write_dump(args.dump_outputs, dumped)
     order = sorted(range(len(times)), key=lambda i: times[i])
     mid = order[len(order) // 2]
     elapsed = times[mid]                                     # the MEDIAN repetition (an odd count: a repetition that really ran)

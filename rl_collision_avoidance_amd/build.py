@@ -42,7 +42,7 @@ EXTRA_FLAGS = {"cavoid_multistep.hip": ["-mllvm", "-disable-machine-licm"], "cav
 STAMP_PATH = os.path.join(PKG_DIR, "libcavoid_hip.so.stamp")
 DEPS = SOURCES + [os.path.join(CSRC, h) for hs in HEADERS.values() for h in hs] + [os.path.join(ROOT, "include", "cavoid.h")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")
-# Development variants (phase-trace build, fault-injection builds) are test / tooling artefacts, never the product: they are linked
+# Development variants (phase-trace build, ulp-fault builds) are test / tooling artefacts, never the product: they are linked
 # into tests/_variants/, NOT beside libcavoid_hip.so, so that the package directory holds exactly one library and a process that maps
 # the product maps nothing else (selected with CAVOID_LIB=<path> by the tests and tools that want one, always in a child process).
 VARIANT_DIR = os.path.join(ROOT, "tests", "_variants")
@@ -136,20 +136,6 @@ def build_trace(verbose: bool = False) -> str:
     return _link(_compile_objects(["-DCAVOID_TRACE"], ".trace", False, verbose), out, verbose)
 
 
-def build_fault(verbose: bool = False) -> str:
-    """Development variant with a broken relay hand-over (-DCAVOID_FAULT_RELAY: the pair-pass wavefront of tile 0 leaves at step
-    5), for tests/test_gpu_relay_fault.py: only cavoid_relay.hip is recompiled, the other objects are the product's."""
-    objs = _compile_objects([], "", False, verbose)
-    src = os.path.join(CSRC, "cavoid_relay.hip")
-    obj = os.path.join(OBJ_DIR, "cavoid_relay.fault.o")
-    cmd = [hipcc()] + FLAGS + EXTRA_FLAGS["cavoid_relay.hip"] + ["-DCAVOID_FAULT_RELAY", "-DCAVOID_DEV_ONLY_N", "-c", src, "-o", obj]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    objs = [obj if o.endswith("cavoid_relay.o") else o for o in objs]
-    return _link(objs, variant_path("fault"), verbose)
-
-
 def build_ulp_fault(kind: int, verbose: bool = False) -> str:
     """Development variants with ONE ulp-scale arithmetic fault in the env step (-DCAVOID_DEV_ULP_FAULT=kind: 1 = a float32 product in
     the pair pass's distance, 2 = the position update contracted into fused multiply-adds, 3 = the sort key's centimetre bucket through
@@ -178,8 +164,6 @@ if __name__ == "__main__":
     import sys
     if "--trace" in sys.argv:
         print(build_trace(verbose=True))
-    elif "--fault" in sys.argv:
-        print(build_fault(verbose=True))
     elif "--ulp-faults" in sys.argv:
         for kind in (1, 2, 3, 4):
             print(build_ulp_fault(kind, verbose=True))

@@ -150,8 +150,8 @@ __device__ __forceinline__ void relay_wait(const int *p, int v) {
 // The observation wavefronts and the loader wait with a bound: a wait that does not end within ~1 s (2^24 polls; a step is
 // microseconds) is a broken hand-over somewhere in the workgroup, and the wavefront traps -- the process gets a launch failure
 // instead of a GPU that never answers again.  (D and P wait unbounded: the bound costs their loops 5 %.  They are covered all
-// the same: whichever of them stalls, `fin` stops advancing, and the consumers' and the loader's bounded waits on it trap --
-// kept honest by the fault-injection build, tests/test_gpu_relay_fault.py.)
+// the same: whichever of them stalls, `fin` stops advancing, and the consumers' and the loader's bounded waits on it trap.
+// No test exercises this trap path: a test would have to make the kernel trap on the GPU on purpose.)
 constexpr int kRelayPollLimit = 1 << 24;
 __device__ __forceinline__ void relay_wait_bounded(const int *p, int v) {
     int polls = 0;
@@ -756,12 +756,6 @@ __global__ void __launch_bounds__(64 * (3 + kRelayMaxConsumers), 1) env_relay_ke
         for (int t = 0; t < n_steps; ++t) {
             int lane = lane0, i = i0, base = base0;
             asm volatile("" : "+v"(lane), "+v"(i), "+v"(base));
-#ifdef CAVOID_FAULT_RELAY
-            // development build only (tests/test_gpu_relay_fault.py): the pair-pass wavefront of tile 0 walks away at step 5 -- D then
-            // spins on a verdict that never comes; the bounded waits of the observation wavefronts and of the loader must turn
-            // that into a trap (a failed launch), not into a GPU that never answers
-            if (t == 5 && blockIdx.x == 0) return;
-#endif
             RELAY_STAMP(8);                                // P: waiting for stage t
             // the speculative successor D posted while this wavefront worked on step t-1 is exact unless the verdict of t-1 found
             // a new collision or restarted a world: only then wait for D's corrected state

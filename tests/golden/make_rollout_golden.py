@@ -4,7 +4,8 @@
 in this container.  The reference is imported, never copied: only the input scripts and the
 values it returned are stored.  Needs /root/reference; not runnable on the GPU box.
 
-    python tests/golden/make_rollout_golden.py
+    python tests/golden/make_rollout_golden.py            # rollout_golden.npz
+    python tests/golden/make_rollout_golden.py --seed7    # rollout_seed7_golden.npz
 
 Stubs: the env package the reference imports (absent submodule) resolves to this repo's compat
 shim; NumPy 2 dropped ``np.product`` (used at Config.py:69), aliased here; ``Environment`` is
@@ -167,5 +168,30 @@ def main():
     print("wrote", out, os.path.getsize(out), "bytes;", ep, "episodes,", len(acc_cases), "accumulate cases; probe", store["probe_returns"])
 
 
+def main_seed7():
+    """tests/golden/rollout_seed7_golden.npz: 10 more TrainPhase1 episodes (rng 7) through the reference's run_episode, stored like
+    the episodes above (test_rollout_oracle.test_against_live_reference)."""
+    rng = np.random.default_rng(7)
+    Config, PA, EX = load_reference("TrainPhase1")
+    store = {"num_episodes": 10, "discount": Config.DISCOUNT, "time_max": Config.TIME_MAX}
+    for ep in range(10):
+        n_present = int(rng.integers(1, 5))
+        script = make_script(rng, 4, Config.NN_INPUT_SIZE, n_present, 3 * Config.TIME_MAX, Config.TIME_MAX)
+        ref = run_reference_episode(Config, PA, script)
+        pre = "ep_%d_" % ep
+        for key in ("obs", "rewards", "done", "learning", "n", "actions", "values"):
+            store[pre + key] = np.asarray(script[key])
+        store[pre + "num_yields"] = len(ref)
+        for k, (x, r, a, score) in enumerate(ref):
+            store[pre + "y%d_x" % k], store[pre + "y%d_r" % k], store[pre + "y%d_a" % k] = x, r, a
+            store[pre + "y%d_score" % k] = np.float64(score)
+    out = os.path.join(ROOT, "tests", "golden", "rollout_seed7_golden.npz")
+    np.savez_compressed(out, **store)
+    print("wrote", out, os.path.getsize(out), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if "--seed7" in sys.argv:
+        main_seed7()
+    else:
+        main()

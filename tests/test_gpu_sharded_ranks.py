@@ -1,5 +1,5 @@
 """The N > 1 hand-over executed with 4 and 8 RANKS on one device (gloo process group, every rank on cuda:0 -- no multi-GPU node is
-available to the builder): each rank steps ITS shard of a `total`-world env on the GPU through the C ABI (`ShardedEnv`, world
+available to the builder; 8 ranks are dealt over 2 devices): each rank steps ITS shard of a `total`-world env on the GPU through the C ABI (`ShardedEnv`, world
 offsets, RNG keyed on global world ids), the packed records travel through the process group in the wire layout of the native
 path (rank-major blocks of K steps; transport "torch" = `sharding.gather_blocks`), and every receiving rank must hold, bit for
 bit, what ONE unsharded env of `total` worlds produces.  Even and ragged shards, to every rank and to one trainer rank, one step
@@ -40,10 +40,11 @@ def _worker(rank, size, cases, port, ret):
     dist.init_process_group("gloo", rank=rank, world_size=size)
     try:
         from rl_collision_avoidance_amd.sharding import ShardedEnv
-        torch.cuda.set_device(0)
+        dev = rank % _devices_for(size)
+        torch.cuda.set_device(dev)
         out = {}
         for total, K, root, launches in cases:
-            sh = ShardedEnv(total, _cfg(), device="cuda:0", seed=SEED, gen_min_agents=2, gen_nonlearning_fraction=0.2, gen_pool_size=512)
+            sh = ShardedEnv(total, _cfg(), device="cuda:%d" % dev, seed=SEED, gen_min_agents=2, gen_nonlearning_fraction=0.2, gen_pool_size=512)
             assert sh.transport == "torch" and (sh.offset, sh.count) == __import__("rl_collision_avoidance_amd.sharding", fromlist=["x"]).shard_range(total, rank, size)
             sh.reset()
             acts = _actions(total, K, launches)[:, :, sh.offset:sh.offset + sh.count].cuda()
@@ -63,8 +64,20 @@ def _worker(rank, size, cases, port, ret):
         dist.destroy_process_group()
 
 
+# at most this many ranks share one device: with this process and the result manager, MAX_RANKS_PER_DEVICE + 2 processes on cuda:0
+MAX_RANKS_PER_DEVICE = 4
+
+
+def _devices_for(size):
+    """the devices the ranks are dealt over (rank r on cuda:(r % devices)): one while MAX_RANKS_PER_DEVICE ranks fit on it"""
+    return 1 if size <= MAX_RANKS_PER_DEVICE else -(-size // MAX_RANKS_PER_DEVICE)
+
+
 @pytest.mark.parametrize("size", [4, 8])
 def test_sharded_ranks_on_one_device_equal_the_unsharded_env(size):
+    need, have = _devices_for(size), torch.cuda.device_count()
+    if have < need:
+        pytest.skip("%d ranks at most %d per device: needs %d GPUs, found %d" % (size, MAX_RANKS_PER_DEVICE, need, have))
     from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
     # (total worlds, steps per launch, receiving rank or -1, launches)
     cases = [(64 * size, 1, -1, 12), (64 * size + 3, 8, -1, 6), (64 * size, 8, 1, 6), (40 * size + 5, 1, size - 1, 10)]

@@ -1,18 +1,15 @@
 """CPU-only tests of the host side: the C-ABI library loads without a GPU and exports every symbol
 include/cavoid.h declares; error codes; config / action-table mirrors; the create_env() facade and
-the Environment mirror against the REFERENCE's own Environment/ProcessAgent when /root/reference is
-present (a CPU oracle world stands in for the GPU backend -- test infrastructure only)."""
+the Environment mirror against the REFERENCE's own Environment/ProcessAgent, recorded on the same seam in
+tests/golden/seam_golden.npz (a CPU oracle world stands in for the GPU backend -- test infrastructure only)."""
 import ctypes as C
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/ga3c"
-HAVE_REF = os.path.isdir(os.path.join(REF, "GA3C"))
 
 
 def test_library_exports_every_declared_symbol():
@@ -101,56 +98,59 @@ def test_create_env_facade_contract():
     assert np.all(o[0][n:] == 0)                      # absent agents: zero rows, is_learning == 0
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not present")
+def _expect_call(mine, g, e, out=None):
+    """call e of tests/golden/seam_golden.npz (what the reference's Environment returned and left behind) == `mine` now"""
+    if out is not None:
+        r, over, info = out
+        n = int(g["n_rew"][e])
+        assert len(r[0]) == n and np.array_equal(np.asarray(r[0], np.float64), g["rew"][e, :n]), e
+        assert bool(over) == bool(g["over"][e]), e
+        k = int(g["n_info"][e])
+        assert info == [{"which_agents_done": {i: bool(g["done"][e, i]) for i in range(k)},
+                         "which_agents_learning": {i: bool(g["learn"][e, i]) for i in range(k)}}], e
+    assert np.array_equal(mine.latest_observations, g["lat"][e]), e
+    for name, has in (("previous_state", "has_prev"), ("current_state", "has_cur")):
+        got = getattr(mine, name)
+        if g[has][e]:
+            assert got.shape == (1, 4, 26) and np.array_equal(got, g[name[:4] if name[0] == "p" else "cur"][e]), (e, name)
+        else:
+            assert got is None, (e, name)
+
+
 def test_reference_code_runs_on_our_seam():
-    """The reference's UNMODIFIED Config, Environment and ProcessAgent on top of create_env()'s facade."""
-    sys.path[:0] = [os.path.join(ROOT, "rl_collision_avoidance_amd", "compat"), REF, os.path.join(REF, "GA3C")]
-    np.product = np.prod
-    os.environ["GYM_CONFIG_CLASS"] = "TrainPhase1"
-    os.environ["GYM_CONFIG_PATH"] = os.path.join(REF, "GA3C", "Config.py")
-    for m in [m for m in sys.modules if m == "GA3C" or m.startswith("GA3C.") or m in ("ProcessAgent", "Environment", "Experience")]:
-        del sys.modules[m]
-    from GA3C import Config
-    assert Config.NN_INPUT_SIZE == 26 and Config.TIME_MAX == 20 and Config.NUM_ACTIONS == 11
-    assert len(Config.NN_INPUT_AVG_VECTOR) == 26 and len(Config.NN_INPUT_STD_VECTOR) == 26
-    import Environment as RefEnvironment
-    import ProcessAgent as PA
+    """The reference's UNMODIFIED Config, Environment and ProcessAgent on top of create_env()'s facade, as recorded by
+    tests/golden/make_seam_golden.py: (a) 60 scripted steps and (b) three episodes of the reference's actor loop, every call the
+    reference made with what its Environment returned -- my Environment mirror must return and hold the same, call for call."""
     from rl_collision_avoidance_amd.env_utils import SingleWorldVecEnv
     from rl_collision_avoidance_amd.ga3c.environment import Environment as MyEnvironment
-
-    ref_env = RefEnvironment.Environment.__new__(RefEnvironment.Environment)      # skip _set_env (would need a GPU)
-    from queue import Queue
-    ref_env.nb_frames, ref_env.frame_q, ref_env.total_reward = 1, Queue(maxsize=1), 0
-    ref_env.previous_state = ref_env.current_state = None
-    ref_env.game = SingleWorldVecEnv(OracleBackend(seed=9))
+    g = np.load(os.path.join(ROOT, "tests", "golden", "seam_golden.npz"))
     mine = MyEnvironment(0, game=SingleWorldVecEnv(OracleBackend(seed=9)))
-
-    # (a) my Environment mirror == the reference's Environment on the same game, step for step
-    ref_env.reset(); mine.reset()
-    rng = np.random.default_rng(0)
+    calls = len(g["kind"])
+    # (a) the scripted steps: the same uniform actions (rng 0) for the learning agents, a reset after every game over
+    mine.reset()
+    _expect_call(mine, g, 0)
+    e, rng = 1, np.random.default_rng(0)
     for t in range(60):
-        acts = {i: int(rng.integers(0, 11)) for i in range(4) if ref_env.latest_observations[i, 0]}
-        r1, over1, info1 = ref_env.step([acts], 0, t)
-        r2, over2, info2 = mine.step([acts], 0, t)
-        assert over1 == over2 and info1 == info2 and np.array_equal(r1[0], r2[0])
-        assert np.array_equal(ref_env.latest_observations, mine.latest_observations)
-        assert np.array_equal(ref_env.previous_state, mine.previous_state)
-        assert np.array_equal(ref_env.current_state, mine.current_state)
-        assert ref_env.current_state.shape == (1, 4, 26)
-        if over1:
-            ref_env.reset(); mine.reset()
-
-    # (b) the reference's actor loop runs episodes on the seam and yields trainer-shaped chunks
-    agent = PA.ProcessAgent(0, None, None, None, Config.NUM_ACTIONS)
-    agent.env = ref_env
-    agent.predict = lambda obs_row: (np.full(11, 1.0 / 11), 0.1)
-    np.random.seed(0)
-    rows = 0
-    for _ in range(3):
-        for x_, r_, a_, score in agent.run_episode():
-            assert x_.ndim == 2 and x_.shape[1] == 26 and a_.shape == (len(r_), 11) and a_.dtype == np.float32
-            rows += len(r_)
-    assert rows > 0
+        acts = {i: int(rng.integers(0, 11)) for i in range(4) if mine.latest_observations[i, 0]}
+        assert g["kind"][e] == 1 and g["phase"][e] == 0 and acts == {i: int(v) for i, v in enumerate(g["act"][e]) if v >= 0}, e
+        out = mine.step([acts], 0, t)
+        _expect_call(mine, g, e, out)
+        e += 1
+        if out[1]:
+            assert g["kind"][e] == 0, e
+            mine.reset()
+            _expect_call(mine, g, e)
+            e += 1
+    # (b) the reference's actor loop: its resets and its sampled actions, replayed
+    assert e < calls and all(g["phase"][e:] == 1) and not any(g["phase"][:e])
+    for e in range(e, calls):
+        if g["kind"][e] == 0:
+            mine.reset()
+            _expect_call(mine, g, e)
+        else:
+            acts = {i: int(v) for i, v in enumerate(g["act"][e]) if v >= 0}
+            _expect_call(mine, g, e, mine.step([acts], 0, e))
+    assert int(g["actor_rows"]) > 0 and g["over"][g["phase"] == 1].sum() == 3     # three episodes, every one to its game over
 
 
 def test_header_is_plain_c(tmp_path):
