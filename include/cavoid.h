@@ -208,6 +208,27 @@ int cavoid_step_autoreset(cavoid_env *env, const int32_t *actions, float *obs, f
  * cavoid_actor_run). */
 int cavoid_step_autoreset_n(cavoid_env *env, const int32_t *actions, int64_t action_stride, int32_t n_steps, int64_t out_step_stride,
                             float *obs, float *rewards, uint8_t *done, uint8_t *game_over, void *stream);
+/* Table actions outside [0, num_actions) are CLAMPED to that range by every stepping form (a negative index acts as 0, one at or
+ * past num_actions as num_actions - 1); the action of a done or scripted agent is ignored.  This header is the definition: the
+ * C oracle indexes the table without a clamp. */
+
+/* which kernel form the last stepping launch of this handle ran (cavoid_step, _packed, _continuous and every
+ * cavoid_step*_autoreset* entry point; reset and observe leave it alone, cavoid_step_push and the actor do not report here).
+ * Several forms carry the same call and a form that does not carry a configuration hands it to the next one; all of them are
+ * bit-identical to CAVOID_FORM_STEP.  relay_consumers (may be NULL) receives the
+ * observation wavefronts per tile the relay launch really used (the launcher lowers CAVOID_RELAY_CONSUMERS until the LDS fits),
+ * 0 for the other forms.  Returns CAVOID_FORM_NONE before the first stepping launch, when the last one failed, and for a NULL env. */
+enum {
+    CAVOID_FORM_NONE = 0,
+    CAVOID_FORM_STEP = 1,      /* env_kernel, one step per launch, one wavefront per tile */
+    CAVOID_FORM_QUAD = 2,      /* env_quad_kernel: one auto-reset step, four wavefronts per tile */
+    CAVOID_FORM_RVO = 3,       /* the ORCA-carrying instantiations of cavoid_rvo.hip (any step mode) */
+    CAVOID_FORM_LOOP_PF = 4,   /* env_kernel's in-launch step loop, next pool record in registers (MODE_STEP_AUTORESET_PF) */
+    CAVOID_FORM_LOOP = 5,      /* env_kernel's in-launch step loop, restarts gathered on demand (MODE_STEP_AUTORESET_N) */
+    CAVOID_FORM_PIPE = 6,      /* env_pipe_kernel: the step loop on two wavefronts per tile */
+    CAVOID_FORM_RELAY = 7      /* env_relay_kernel: the step loop cut into roles on 3 + relay_consumers wavefronts per tile */
+};
+int32_t cavoid_last_step_form(const cavoid_env *env, int32_t *relay_consumers);
 
 /* The env-level CONTINUOUS action space (run-ws/config.yaml:3-5, ACTION_SPACE_TYPE = 0: "continuous" at the gym level; SURVEY App. A:
  * the discretisation lives in the policy) in the auto-reset and K-step launch forms: float actions [n_steps][W,N,2] -- (speed,

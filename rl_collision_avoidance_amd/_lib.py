@@ -23,6 +23,8 @@ F_POLICY_MASK = 7
 POLICY_EXTERNAL, POLICY_STATIC, POLICY_NONCOOP, POLICY_RVO, POLICY_FROZEN_NET = 0, 1, 2, 3, 4
 F_DONE_MASK = 7
 COMM_FORCE_RCCL = 1
+# CAVOID_FORM_* (cavoid_last_step_form): the kernel form a stepping launch ran, by enum value
+STEP_FORMS = ("NONE", "STEP", "QUAD", "RVO", "LOOP_PF", "LOOP", "PIPE", "RELAY")
 
 
 class CavoidCfg(C.Structure):
@@ -94,6 +96,7 @@ SYMBOLS = [
     ("cavoid_destroy", None, [_P]),
     ("cavoid_num_worlds", C.c_int64, [_P]),
     ("cavoid_obs_width", C.c_int32, [_P]),
+    ("cavoid_last_step_form", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("cavoid_seed", C.c_int, [_P, C.c_uint64, _P, _P]),
     ("cavoid_get_episode", C.c_int, [_P, _P, _P]),
     ("cavoid_pool_refresh", C.c_int, [_P, C.c_uint32, _P]),

@@ -250,6 +250,16 @@ class BatchedCollisionAvoidanceEnv(object):
         _lib.check(self._lib.cavoid_get_episode(self._h, self._ptr(out), self._stream()), "cavoid_get_episode")
         return out
 
+    @property
+    def last_step_form(self) -> Tuple[str, int]:
+        """(form, relay consumers) of the last stepping launch: which kernel ran it ("STEP", "QUAD", "RVO", "LOOP_PF", "LOOP",
+        "PIPE", "RELAY"; "NONE" before the first one) and, for "RELAY", the observation wavefronts per tile it used (else 0).
+        The forms are bit-identical; a launcher that does not carry a configuration hands it to the next form silently, so a
+        test that means one form asserts it here.  Host bookkeeping only: no synchronisation."""
+        nc = C.c_int32(0)
+        form = self._lib.cavoid_last_step_form(self._h, C.byref(nc))
+        return _lib.STEP_FORMS[form], int(nc.value)
+
     # -- state -------------------------------------------------------------------------------------
     def set_state(self, state_f64: torch.Tensor, state_f32: torch.Tensor, flags: torch.Tensor) -> None:
         """Inject explicit world states (SoA): f64 [4,W*N] px,py,heading,t_remaining; f32 [5,W*N]

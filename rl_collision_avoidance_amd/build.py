@@ -43,14 +43,20 @@ STAMP_PATH = os.path.join(PKG_DIR, "libcavoid_hip.so.stamp")
 DEPS = SOURCES + [os.path.join(CSRC, h) for hs in HEADERS.values() for h in hs] + [os.path.join(ROOT, "include", "cavoid.h")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")
 # Development variants (phase-trace build, ulp-fault builds) are test / tooling artefacts, never the product: they are linked
-# into tests/_variants/, NOT beside libcavoid_hip.so, so that the package directory holds exactly one library and a process that maps
-# the product maps nothing else (selected with CAVOID_LIB=<path> by the tests and tools that want one, always in a child process).
+# NOT beside libcavoid_hip.so, so that the package directory holds exactly one library and a process that maps the product maps
+# nothing else (selected with CAVOID_LIB=<path> by the tests and tools that want one, always in a child process).
+# The phase-trace build goes to tests/_variants/ (the tracing tools load it from there).
 VARIANT_DIR = os.path.join(ROOT, "tests", "_variants")
+# The ulp-fault builds go beside the objects they are linked from, under a name that carries the digest of the sources: the library a
+# test finds at variant_path() was built from THESE sources, whatever the file times say and whatever was built in the tree before
+# (a variant of older sources lacks entry points the binding now requires, and an mtime can be newer than the sources it predates).
+FAULT_DIR = os.path.join(OBJ_DIR, "variants")
 
 
 def variant_path(name: str) -> str:
-    os.makedirs(VARIANT_DIR, exist_ok=True)
-    return os.path.join(VARIANT_DIR, "libcavoid_hip_%s.so" % name)
+    """The ulp-fault variant `name` (e.g. "ulp2") of the current sources."""
+    os.makedirs(FAULT_DIR, exist_ok=True)
+    return os.path.join(FAULT_DIR, "libcavoid_hip_%s-%s.so" % (name, source_digest()[:16]))
 
 
 # -ffp-contract=off: the reference env is unfused NumPy float64; keep mul/add separate so that the
@@ -132,7 +138,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
 def build_trace(verbose: bool = False) -> str:
     """Development variant with in-kernel phase time stamps (tools/trace_step.py); never loaded by
     the product (select it with CAVOID_LIB=<path>)."""
-    out = variant_path("trace")
+    os.makedirs(VARIANT_DIR, exist_ok=True)
+    out = os.path.join(VARIANT_DIR, "libcavoid_hip_trace.so")
     return _link(_compile_objects(["-DCAVOID_TRACE"], ".trace", False, verbose), out, verbose)
 
 
@@ -141,15 +148,19 @@ def build_ulp_fault(kind: int, verbose: bool = False) -> str:
     the pair pass's distance, 2 = the position update contracted into fused multiply-adds, 3 = the sort key's centimetre bucket through
     float32, 4 = a float32 product in the ORCA policy's squared distance), for tests/test_gpu_tie_classifier.py: what the parity harness and its tie classifier say about faults of the size the
     classifier excuses.  Only the env kernels' translation units are recompiled (dev-only N = 4, 10); never loaded by the product."""
+    import glob
     from concurrent.futures import ThreadPoolExecutor
+    out = variant_path("ulp%d" % kind)
+    if os.path.exists(out):                    # (its name carries the digest of the sources it was built from: these)
+        return out
+    build()                                    # the product's objects, current by content
     objs = _compile_objects([], "", False, verbose)
     jobs, swap = [], {}
     for name in ("cavoid_capi.hip", "cavoid_multistep.hip", "cavoid_rvo.hip", "cavoid_relay.hip"):
         src = os.path.join(CSRC, name)
         obj = os.path.join(OBJ_DIR, name.replace(".hip", ".ulp%d.o" % kind))
-        deps = [src, os.path.join(ROOT, "include", "cavoid.h")] + [os.path.join(CSRC, h) for h in HEADERS[name]]
-        if not os.path.exists(obj) or any(os.path.getmtime(d) > os.path.getmtime(obj) for d in deps):
-            jobs.append([hipcc()] + FLAGS + EXTRA_FLAGS.get(name, []) + ["-DCAVOID_DEV_ULP_FAULT=%d" % kind, "-DCAVOID_DEV_ONLY_N", "-c", src, "-o", obj])
+        # always recompiled: no variant of these sources exists, so an object of this name is of other sources, whatever its time
+        jobs.append([hipcc()] + FLAGS + EXTRA_FLAGS.get(name, []) + ["-DCAVOID_DEV_ULP_FAULT=%d" % kind, "-DCAVOID_DEV_ONLY_N", "-c", src, "-o", obj])
         swap[os.path.join(OBJ_DIR, name.replace(".hip", ".o"))] = obj
     if jobs:
         if verbose:
@@ -157,7 +168,12 @@ def build_ulp_fault(kind: int, verbose: bool = False) -> str:
                 print(" ".join(j), flush=True)
         with ThreadPoolExecutor(max_workers=len(jobs)) as pool:
             list(pool.map(subprocess.check_call, jobs))
-    return _link([swap.get(o, o) for o in objs], variant_path("ulp%d" % kind), verbose)
+    for old in glob.glob(os.path.join(FAULT_DIR, "libcavoid_hip_ulp%d-*.so" % kind)):    # variants of earlier sources
+        os.remove(old)
+    tmp = out + ".tmp"
+    _link([swap.get(o, o) for o in objs], tmp, verbose)
+    os.replace(tmp, out)                       # (the digest-named file appears only once it is complete)
+    return out
 
 
 if __name__ == "__main__":

@@ -336,15 +336,23 @@ extern "C" int32_t cavoid_obs_width(const cavoid_env *e) { return e ? e->k.width
 
 template <int MODE>
 static int launch(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
+    constexpr bool stepping = MODE == MODE_STEP || MODE == MODE_STEP_AUTORESET;     // (reset / observe leave cavoid_last_step_form alone)
+    if (stepping) e->last_form = CAVOID_FORM_NONE;
     // the 'everything' instantiations (cavoid_rvo.hip): ORCA agents; box scenarios generated inside the auto-reset step
-    if (((MODE == MODE_STEP || MODE == MODE_STEP_AUTORESET) && e->k.rvo_enabled) ||
-        (MODE == MODE_STEP_AUTORESET && e->k.gen_mode == 1 && e->k.pool_size <= 0))
+    if ((stepping && e->k.rvo_enabled) || (MODE == MODE_STEP_AUTORESET && e->k.gen_mode == 1 && e->k.pool_size <= 0))
         return cavoid_launch_rvo(e, MODE, io, s, ev_start, ev_stop);
     if (MODE == MODE_STEP_AUTORESET) {                     // small batches: the step spread over four wavefronts per tile, where that form carries it
         const int rc = cavoid_launch_quad(e, io, s, ev_start, ev_stop);
         if (rc != CAVOID_EUNSUPPORTED) return rc;
     }
-    return launch_on<MODE>(e, e->k, e->st, e->grid, io, s, ev_start, ev_stop);
+    const int rc = launch_on<MODE>(e, e->k, e->st, e->grid, io, s, ev_start, ev_stop);
+    return stepping ? note_form(e, rc, CAVOID_FORM_STEP) : rc;
+}
+
+extern "C" int32_t cavoid_last_step_form(const cavoid_env *e, int32_t *relay_consumers) {
+    const int32_t form = e ? e->last_form : CAVOID_FORM_NONE;
+    if (relay_consumers) *relay_consumers = form == CAVOID_FORM_RELAY ? e->last_relay_consumers : 0;
+    return form;
 }
 
 // scenario look-ahead (cavoid.h, gen_lookahead): every world's ring must hold the scenarios of the episodes the next n_steps steps can start
@@ -555,6 +563,7 @@ static int launch_autoreset(cavoid_env *e, KIO io, const int32_t *actions, int64
     io.cont = cont;
     io.action_stride = action_stride;
     io.n_steps = n_steps;
+    e->last_form = CAVOID_FORM_NONE;                   // (the dispatcher that launches records its form)
     if (int rc = cavoid_ahead_prepare(e, n_steps, s, &ev_start)) return rc;      // (a timed launch includes its look-ahead refill, when it needs one)
     const int rc = (n_steps > 1 || e->prefetch_single)           // the in-launch step loop lives in cavoid_multistep.hip
                        ? cavoid_launch_multistep(e, io, e->latency_mode != 0, s, ev_start, ev_stop)

@@ -37,11 +37,22 @@ struct cavoid_env {
     int quad = -1;               // one-step auto-reset launches with four cooperating wavefronts per tile (env_quad_kernel): -1 = where it pays
                                  // (<= 512 tiles), 0 / 1 = never / wherever it can run (CAVOID_QUAD)
     int prefetch_single = 0;     // ... and single-step launches too (CAVOID_PREFETCH_POOL=1; costs 64 B of reads per agent-step)
+    int last_form = CAVOID_FORM_NONE;   // what the last successful stepping call launched (cavoid_last_step_form): set by the dispatcher that launched
+    int last_relay_consumers = 0;       // ... and, for CAVOID_FORM_RELAY, the consumer count it used
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
 
 namespace cavoid {
+
+// the dispatchers' bookkeeping for cavoid_last_step_form: a launch that succeeded records its form
+static inline int note_form(cavoid_env *e, int rc, int form, int relay_consumers = 0) {
+    if (rc == CAVOID_OK) {
+        e->last_form = form;
+        e->last_relay_consumers = relay_consumers;
+    }
+    return rc;
+}
 
 template <int MODE, bool RVO = false>
 static inline int launch_on(cavoid_env *e, const KCfg &k, const KState &st, int grid_x, const KIO &io, hipStream_t s,

@@ -12,15 +12,15 @@ int cavoid_launch_multistep(cavoid_env *e, const KIO &io, bool prefetch, hipStre
         return cavoid_launch_rvo(e, prefetch ? MODE_STEP_AUTORESET_PF : MODE_STEP_AUTORESET_N, io, s, ev_start, ev_stop);
     // (continuous actions: the role-split and pipelined forms decode table actions only -- the single-wavefront loops carry them)
     if (prefetch && e->pipeline >= 2 && !io.cont) {                     // small batch: the step cut into roles on several wavefronts (env_relay_kernel)
-        const int rc = cavoid_launch_relay(e, io, s, ev_start, ev_stop);
+        const int rc = cavoid_launch_relay(e, io, s, ev_start, ev_stop);   // (records its own form: it knows the consumer count)
         if (rc != CAVOID_EUNSUPPORTED) return rc;
     }
     if (prefetch && e->pipeline && !io.cont) {                          // two wavefronts per tile, pipelined (env_pipe_kernel)
         const int rc = launch_pipe<false>(e, io, s, ev_start, ev_stop);
-        if (rc != CAVOID_EUNSUPPORTED) return rc;
+        if (rc != CAVOID_EUNSUPPORTED) return note_form(e, rc, CAVOID_FORM_PIPE);
     }
-    if (prefetch) return launch_on<MODE_STEP_AUTORESET_PF>(e, e->k, e->st, e->grid, io, s, ev_start, ev_stop);
-    return launch_on<MODE_STEP_AUTORESET_N>(e, e->k, e->st, e->grid, io, s, ev_start, ev_stop);
+    if (prefetch) return note_form(e, launch_on<MODE_STEP_AUTORESET_PF>(e, e->k, e->st, e->grid, io, s, ev_start, ev_stop), CAVOID_FORM_LOOP_PF);
+    return note_form(e, launch_on<MODE_STEP_AUTORESET_N>(e, e->k, e->st, e->grid, io, s, ev_start, ev_stop), CAVOID_FORM_LOOP);
 }
 
 #ifdef CAVOID_TRACE

@@ -40,7 +40,7 @@ int cavoid_launch_quad(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t e
     }
 #undef CAVOID_QUAD_CASE
     HIP_TRY(hipGetLastError());
-    return CAVOID_OK;
+    return note_form(e, CAVOID_OK, CAVOID_FORM_QUAD);
 }
 
 #ifdef CAVOID_TRACE

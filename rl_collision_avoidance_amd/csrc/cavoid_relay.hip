@@ -21,6 +21,7 @@ int cavoid_launch_relay(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t 
     const int tile_floats = (k.tile_rows * row + 3) & ~3;
     if (k.tile_rows < k.wpw * e->cfg.max_agents) return CAVOID_EUNSUPPORTED;   // one pass per step only
     const dim3 grid((unsigned)tiles);
+    int used_nc = 0;                                   // the consumer count the launch really uses (cavoid_last_step_form)
 #define CAVOID_RELAY_CASE(NN) \
     case NN: {                                                                                                          \
         int nc = e->relay_consumers;                                                                                    \
@@ -37,6 +38,7 @@ int cavoid_launch_relay(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t 
             }                                                                                                           \
         }                                                                                                               \
         const dim3 block(64 * (3 + nc));                                                                                \
+        used_nc = nc;                                                                                                   \
         if (ev_start || ev_stop)                                                                                        \
             hipExtLaunchKernelGGL((env_relay_kernel<NN>), grid, block, lds, s, ev_start, ev_stop, 0, k, e->st, e->pool, io);  \
         else                                                                                                            \
@@ -53,7 +55,7 @@ int cavoid_launch_relay(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t 
     }
 #undef CAVOID_RELAY_CASE
     HIP_TRY(hipGetLastError());
-    return CAVOID_OK;
+    return note_form(e, CAVOID_OK, CAVOID_FORM_RELAY, used_nc);
 }
 
 #ifdef CAVOID_TRACE

@@ -6,7 +6,7 @@
 
 using namespace cavoid;
 
-int cavoid_launch_rvo(cavoid_env *e, int mode, const KIO &io, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+static int launch_rvo(cavoid_env *e, int mode, const KIO &io, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     if (mode == MODE_STEP_AUTORESET_PF && e->pipeline && !io.cont) {       // (the pipelined form decodes table actions only)
         const int rc = launch_pipe<true>(e, io, s, ev_start, ev_stop);
         if (rc != CAVOID_EUNSUPPORTED) return rc;
@@ -18,6 +18,10 @@ int cavoid_launch_rvo(cavoid_env *e, int mode, const KIO &io, hipStream_t s, hip
         case MODE_STEP_AUTORESET_N: return launch_on<MODE_STEP_AUTORESET_N, true>(e, e->k, e->st, e->grid, io, s, ev_start, ev_stop);
         default: return CAVOID_EINVAL;
     }
+}
+
+int cavoid_launch_rvo(cavoid_env *e, int mode, const KIO &io, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    return note_form(e, launch_rvo(e, mode, io, s, ev_start, ev_stop), CAVOID_FORM_RVO);
 }
 
 #ifdef CAVOID_TRACE

@@ -15,7 +15,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 
-def _make(W, N, seed, reflush, greedy=False, skip_finished=None, **over):
+def _make(W, N, seed, reflush, greedy=False, skip_finished=None, M=None, **over):
     from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
     from rl_collision_avoidance_amd.config import EnvConfig
     from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
@@ -25,6 +25,8 @@ def _make(W, N, seed, reflush, greedy=False, skip_finished=None, **over):
     class Cfg(EnvConfig):
         def __init__(self):
             self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
+            if M is not None:
+                self.MAX_NUM_OTHER_AGENTS_OBSERVED = M
             EnvConfig.__init__(self)
     cfg = Cfg()
     env = BatchedCollisionAvoidanceEnv(W, cfg, device="cuda:0", seed=seed, **over)
@@ -72,12 +74,22 @@ def _same(a, b, what):
     (4, 8192, False, False, dict(rvo_enabled=1, gen_rvo_fraction=1.0, gen_nonlearning_fraction=0.7, gen_pool_size=20000)),
     (4, 8192, False, False, dict()),
     (10, 4096, False, False, dict(gen_min_agents=2)),
+    # the env step's configuration space inside the fused kernel: the clip to M < N - 1 neighbours, the other sort orders, the
+    # U7 / U2 switches, the max-turn-rate dynamics
+    (4, 600, False, False, dict(M=2, gen_min_agents=4)),
+    (6, 300, False, False, dict(M=3, gen_min_agents=5, gen_nonlearning_fraction=0.2)),
+    (4, 500, False, False, dict(sort_method=1, gen_min_agents=3)),                  # closest_first
+    (5, 400, False, False, dict(sort_method=2, gen_min_agents=2)),                  # time_to_impact
+    (4, 500, False, False, dict(sort_round_gap=0, sort_tie_lateral=0, wrap_closed_end=1)),
+    # unicycle_max_turn_rate, with turns the clamp cuts (the default table's widest, pi/6, is below max_turn_rate * dt)
+    (4, 500, False, False, dict(dynamics=1, gen_min_agents=2, actions=[[1.0, 0.3], [1.0, -0.3], [1.0, 0.0], [1.0, 0.9], [1.0, -0.9], [0.5, 1.2],
+                                                                      [0.5, -1.2], [0.0, 0.7], [0.0, -0.7], [1.0, 1.5], [1.0, -1.5]])),
 ])
 def test_fused_actor_equals_step_by_step(N, W, reflush, greedy, over):
     seed = 21
     env_a, net_a, pol_a, a = _make(W, N, seed, reflush, greedy, **over)
     env_b, net_b, pol_b, b = _make(W, N, seed, reflush, greedy, **over)
-    assert a.fused_available
+    assert a.fused_available and a.actor_path.startswith("fused actor kernel"), a.actor_path
     for p, q in zip(net_a.parameters(), net_b.parameters()):
         assert torch.equal(p, q)
     _same(a.obs, b.obs, "first observation")

@@ -16,6 +16,8 @@ pytestmark = pytest.mark.gpu
 
 OBS_TOL, STATE_TOL = 1e-5, 1e-9
 FIELDS = dict(sensing_horizon=3.0, reward_time_step=-0.01)
+# an action table with turns beyond max_turn_rate * dt (0.6 rad), straight ahead at index 2: the max-turn clamp really acts
+WIDE = [[1.0, 0.3], [1.0, -0.3], [1.0, 0.0], [1.0, 0.9], [1.0, -0.9], [0.5, 1.2], [0.5, -1.2], [0.0, 0.7], [0.0, -0.7], [1.0, 1.5], [1.0, -1.5]]
 
 
 def _env(W, N, M=None, seed=0, **over):
@@ -49,6 +51,15 @@ def _check_step(tag, out, ora, env, st, ep):
     assert np.array_equal(env.episode.cpu().numpy().view(np.uint32), ep), tag
 
 
+# the forms each case runs (last_step_form): (N, M, W, sort, pipe) -> (one step per launch, the K-step launch)
+HORIZON_FORMS = {
+    (4, None, 512, 0, None): ("QUAD", ("RELAY", 3)), (4, None, 512, 1, "1"): ("QUAD", ("PIPE", 0)),
+    (4, None, 512, 0, "0"): ("QUAD", ("LOOP_PF", 0)), (4, None, 40000, 0, None): ("STEP", ("LOOP", 0)),
+    (10, None, 300, 0, None): ("QUAD", ("PIPE", 0)), (10, 4, 300, 1, None): ("QUAD", ("PIPE", 0)),
+    (6, None, 200, 2, None): ("QUAD", ("RELAY", 3)), (5, None, 256, 0, None): ("QUAD", ("LOOP", 0)),
+}
+
+
 @pytest.mark.parametrize("N,M,W,sort,pipe,over", [
     (4, None, 512, 0, None, dict()),                                              # relay kernel (BASELINE configs[1] shape)
     (4, None, 512, 1, "1", dict(gen_min_agents=2, gen_nonlearning_fraction=0.3)),  # two-wavefront pipeline, closest_first, scripted agents
@@ -80,6 +91,7 @@ def test_finite_sensing_horizon_and_time_step_reward(N, M, W, sort, pipe, over, 
     for t in range(single):
         a = _acts(rng, W, N)
         out = env.step_autoreset(torch.from_numpy(a).cuda())
+        assert env.last_step_form == (HORIZON_FORMS[(N, M, W, sort, pipe)][0], 0)
         ora = co.step_autoreset(ocfg, ogen, seed, st, ep, a)
         _check_step(("single", N, t), out, ora, env, st, ep)
         twin.step_autoreset(torch.from_numpy(a).cuda())
@@ -92,8 +104,10 @@ def test_finite_sensing_horizon_and_time_step_reward(N, M, W, sort, pipe, over, 
     acts = np.stack([_acts(rng, W, N) for _ in range(K)])
     slots = env.new_step_slots(K)
     obs, rew, done, go = env.step_autoreset_n(torch.from_numpy(acts).cuda(), slots=slots)
+    assert env.last_step_form == HORIZON_FORMS[(N, M, W, sort, pipe)][1]
     pslots = twin.new_step_slots(K, packed=True)
     twin.step_autoreset_packed(torch.from_numpy(acts).cuda(), pslots)
+    assert twin.last_step_form == HORIZON_FORMS[(N, M, W, sort, pipe)][1]
     restarts = 0
     for t in range(K):
         oobs, orew, odone, ogo = co.step_autoreset(ocfg, ogen, seed, st, ep, acts[t])
@@ -109,6 +123,50 @@ def test_finite_sensing_horizon_and_time_step_reward(N, M, W, sort, pipe, over, 
     assert torch.equal(pslots.packed[..., :width], obs) and torch.equal(pslots.packed[..., width], rew)
     assert torch.equal(pslots.packed[..., width + 1], done.float()) and torch.equal(pslots.game_over, go)
     env.close(); twin.close()
+
+
+@pytest.mark.parametrize("N,M,W,over,steps", [
+    (6, 2, 200, dict(FIELDS, gen_min_agents=4), (40, 40)),                          # M < N - 1 with a horizon (relay_coop_last's clip)
+    (4, None, 300, dict(sort_method=1, gen_min_agents=3), (40, 40)),                # closest_first
+    (5, None, 200, dict(dynamics=1, actions=WIDE, gen_min_agents=2), (40, 40)),     # unicycle_max_turn_rate: the relay's own clamp
+    (4, None, 300, dict(evaluate_mode=1, gen_min_agents=2, gen_nonlearning_fraction=0.3), (40, 40)),
+    (4, None, 256, dict(gen_min_agents=2), (129,)),                                 # one launch of 129 steps: the action ring wraps twice
+])
+def test_relay_kernel_configurations_against_the_oracle(N, M, W, over, steps):
+    """env_relay_kernel (the default K-step form of these batches, asserted) straight against the float64 oracle in configurations
+    the relay is not otherwise held to the oracle in; every step of every launch in its slot."""
+    seed = 37
+    env = _env(W, N, M, seed=seed, **over)
+    ocfg, ogen = rp.oracle_for(N, M, **over)
+    st = co.State.empty(W, N)
+    ep = np.zeros(W, np.uint32)
+    co.generate(ocfg, ogen, seed, st, ep)
+    env.reset()
+    rng = np.random.default_rng(seed)
+    Mv = N - 1 if M is None else M
+    clipped = hidden = False
+    for K in steps:
+        acts = np.stack([_acts(rng, W, N) for _ in range(K)])
+        slots = env.new_step_slots(K)
+        obs, rew, done, go = env.step_autoreset_n(torch.from_numpy(acts).cuda(), slots=slots)
+        assert env.last_step_form == ("RELAY", 3)
+        for t in range(K):
+            oobs, orew, odone, ogo = co.step_autoreset(ocfg, ogen, seed, st, ep, acts[t])
+            assert np.array_equal(done[t].cpu().numpy(), odone) and np.array_equal(go[t].cpu().numpy(), ogo), (K, t)
+            assert rp.obs_diff(obs[t].cpu().numpy(), oobs).max() <= OBS_TOL, (K, t)
+            assert np.array_equal(obs[t][..., 1].cpu().numpy(), oobs[..., 1].astype(np.float32)), (K, t)
+            assert np.abs(rew[t].cpu().numpy() - orew).max() <= OBS_TOL, (K, t)
+            n_world = ((st.flags.reshape(W, N) & 0x20) != 0).sum(axis=1)
+            clipped |= bool((n_world - 1 > Mv).any())
+            hidden |= bool((oobs[..., 1] < np.minimum(n_world - 1, Mv)[:, None]).any())
+        f64, f32, fl = [v.cpu().numpy() for v in env.get_state()]
+        assert np.array_equal(fl.view(np.uint32), st.flags) and np.array_equal(f32, st.f32), K
+        np.testing.assert_allclose(f64, st.f64, rtol=0, atol=STATE_TOL)
+        assert np.array_equal(env.episode.cpu().numpy().view(np.uint32), ep), K
+    assert ep.max() >= 1                                    # worlds restarted inside the launches
+    if M is not None:
+        assert clipped and hidden                           # the clip and the horizon really hid neighbours
+    env.close()
 
 
 def test_time_step_reward_known_answer():

@@ -73,6 +73,20 @@ def test_packed_outputs_equal_plain_outputs(N, M, W, nonl, gen_min):
     a.close(); b.close()
 
 
+# the form each case's K-step launches must run (BatchedCollisionAvoidanceEnv.last_step_form): (N, W, pool, wpw, pipe) -> (form, consumers)
+MULTI_STEP_FORMS = {
+    (4, 300, 65536, None, None): ("RELAY", 3), (4, 300, 65536, None, "1"): ("PIPE", 0), (4, 300, 65536, None, "0"): ("LOOP_PF", 0),
+    (4, 300, 0, None, None): ("LOOP", 0),                   # no pool: out of latency mode
+    (4, 5000, 500, 16, None): ("RELAY", 3), (4, 5000, 500, 16, "1"): ("PIPE", 0),
+    (4, 5000, 500, 1, None): ("LOOP_PF", 0),                # 5000 tiles: too many for the relay (512) and the pipeline (1024)
+    (10, 257, 300, None, None): ("PIPE", 0),                # N > 6: the relay hands it to the pipeline
+    (10, 257, 0, 3, None): ("LOOP", 0),
+    (3, 1000, 7, 5, None): ("RELAY", 3), (3, 1000, 7, 5, "1"): ("PIPE", 0),
+    (2, 777, 64, None, None): ("RELAY", 3), (5, 333, 100, None, None): ("RELAY", 3),
+    (16, 130, 64, None, None): ("PIPE", 0),
+}
+
+
 @pytest.mark.parametrize("N,W,pool,wpw,pipe", [
     (4, 300, 65536, None, None),   # latency mode, default form: env_relay_kernel (roles on wavefronts of one workgroup per tile)
     (4, 300, 65536, None, "1"),    # ... env_pipe_kernel (two wavefronts per tile)
@@ -104,6 +118,8 @@ def test_multi_step_launch_equals_single_steps(N, W, pool, wpw, pipe, monkeypatc
     a.reset(); b.reset()
     for lo, n in ((0, 1), (1, 7), (8, 24), (32, 16)):       # chunks of different lengths, incl. n = 1
         a.step_autoreset_n(acts[lo:lo + n])
+        if n > 1:
+            assert a.last_step_form == MULTI_STEP_FORMS[(N, W, pool, wpw, pipe)], (lo, n)
         for t in range(lo, lo + n):
             b.step_autoreset(acts[t])
         assert torch.equal(a.obs, b.obs) and torch.equal(a.rewards, b.rewards), (lo, n)
@@ -133,6 +149,7 @@ def test_relay_kernel_short_launches_and_consumer_counts(N, W, nc, monkeypatch):
     lo = 0
     for n in (2, 3, 4, 5, 6, 2, 9, 33, 3, 53):
         a.step_autoreset_n(acts[lo:lo + n])
+        assert a.last_step_form == ("RELAY", nc), (lo, n)     # the relay ran, with the consumers asked for
         for t in range(lo, lo + n):
             b.step_autoreset(acts[t])
         assert torch.equal(a.obs, b.obs) and torch.equal(a.rewards, b.rewards), (lo, n)

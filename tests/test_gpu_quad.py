@@ -80,6 +80,7 @@ def test_cooperative_step_is_bit_identical_to_the_single_wavefront_step(N, M, W,
     acts = _acts(T, W, N, 5)
     for t in range(T):
         a.step_autoreset(acts[t]); b.step_autoreset(acts[t])
+        assert a.last_step_form == ("QUAD", 0) and b.last_step_form == ("STEP", 0), t
         _same_step(a, b, (t,))
         if t % 20 == 19:
             for x, y in zip(a.get_state(), b.get_state()):
@@ -98,6 +99,7 @@ def test_cooperative_step_writes_the_packed_record_too(monkeypatch):
     for t in range(80):
         ra, ga = a.step_autoreset_packed(acts[t], pa)
         rb, gb = b.step_autoreset_packed(acts[t], pb)
+        assert a.last_step_form == ("QUAD", 0) and b.last_step_form == ("STEP", 0), t
         assert torch.equal(ra, rb) and torch.equal(ga, gb), t
     a.close(); b.close()
 
@@ -114,6 +116,7 @@ def test_configurations_the_cooperative_form_does_not_carry_fall_back(over, monk
     acts = _acts(60, 300, 4, 8)
     for t in range(60):
         a.step_autoreset(acts[t]); b.step_autoreset(acts[t])
+        assert a.last_step_form == b.last_step_form == ("RVO", 0), t   # the instantiations that carry ORCA / the in-step generator
         _same_step(a, b, t)
     a.close(); b.close()
 
@@ -133,6 +136,7 @@ def test_cooperative_step_against_the_float64_oracle():
     for t in range(T):
         acts = rng.integers(0, 11, size=(W, N)).astype(np.int32)
         obs, rew, done, go = env.step_autoreset(torch.from_numpy(acts).cuda())
+        assert env.last_step_form == ("QUAD", 0), t
         oobs, orew, odone, ogo = co.step_autoreset(ocfg, ogen, seed, st, ep, acts)
         assert np.array_equal(done.cpu().numpy(), odone) and np.array_equal(go.cpu().numpy(), ogo), t
         d = np.abs(obs.cpu().numpy() - oobs)
