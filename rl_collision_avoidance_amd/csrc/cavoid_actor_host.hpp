@@ -33,19 +33,7 @@ static int launch_actor(cavoid_env *e, const SplitArgs &sa, const SplitArgs &fz,
 template <bool RVO, bool FROZEN = false>
 static int launch_actor_any(cavoid_env *e, const SplitArgs &sa, const SplitArgs &fz, const RolloutCfg &rc, const RolloutState &rs, const RolloutIO &rio, const ActorIO &io,
                             hipStream_t s) {
-#define CAVOID_ACTOR_CASE(NN) case NN: return launch_actor<NN, RVO, FROZEN>(e, sa, fz, rc, rs, rio, io, s);
-    switch (e->cfg.max_agents) {
-#ifdef CAVOID_DEV_ONLY_N
-        CAVOID_ACTOR_CASE(4) CAVOID_ACTOR_CASE(10)
-#else
-        CAVOID_ACTOR_CASE(1) CAVOID_ACTOR_CASE(2) CAVOID_ACTOR_CASE(3) CAVOID_ACTOR_CASE(4) CAVOID_ACTOR_CASE(5) CAVOID_ACTOR_CASE(6)
-        CAVOID_ACTOR_CASE(7) CAVOID_ACTOR_CASE(8) CAVOID_ACTOR_CASE(9) CAVOID_ACTOR_CASE(10) CAVOID_ACTOR_CASE(11) CAVOID_ACTOR_CASE(12)
-        CAVOID_ACTOR_CASE(13) CAVOID_ACTOR_CASE(14) CAVOID_ACTOR_CASE(15) CAVOID_ACTOR_CASE(16)
-#endif
-        default: break;
-    }
-#undef CAVOID_ACTOR_CASE
-    return CAVOID_EUNSUPPORTED;
+    return dispatch_n(e->cfg.max_agents, EnvNs{}, [&](auto n) { return launch_actor<decltype(n)::value, RVO, FROZEN>(e, sa, fz, rc, rs, rio, io, s); });
 }
 
 template <int N, bool RVO>
@@ -62,19 +50,7 @@ static int launch_step_push(cavoid_env *e, const RolloutCfg &rc, const RolloutSt
 template <bool RVO>
 static int launch_step_push_any(cavoid_env *e, const RolloutCfg &rc, const RolloutState &rs, const RolloutIO &rio, const ActorIO &io, int32_t step,
                                 hipStream_t s) {
-#define CAVOID_ACTOR_CASE(NN) case NN: return launch_step_push<NN, RVO>(e, rc, rs, rio, io, step, s);
-    switch (e->cfg.max_agents) {
-#ifdef CAVOID_DEV_ONLY_N
-        CAVOID_ACTOR_CASE(4) CAVOID_ACTOR_CASE(10)
-#else
-        CAVOID_ACTOR_CASE(1) CAVOID_ACTOR_CASE(2) CAVOID_ACTOR_CASE(3) CAVOID_ACTOR_CASE(4) CAVOID_ACTOR_CASE(5) CAVOID_ACTOR_CASE(6)
-        CAVOID_ACTOR_CASE(7) CAVOID_ACTOR_CASE(8) CAVOID_ACTOR_CASE(9) CAVOID_ACTOR_CASE(10) CAVOID_ACTOR_CASE(11) CAVOID_ACTOR_CASE(12)
-        CAVOID_ACTOR_CASE(13) CAVOID_ACTOR_CASE(14) CAVOID_ACTOR_CASE(15) CAVOID_ACTOR_CASE(16)
-#endif
-        default: break;
-    }
-#undef CAVOID_ACTOR_CASE
-    return CAVOID_EUNSUPPORTED;
+    return dispatch_n(e->cfg.max_agents, EnvNs{}, [&](auto n) { return launch_step_push<decltype(n)::value, RVO>(e, rc, rs, rio, io, step, s); });
 }
 
 }  // namespace cavoid

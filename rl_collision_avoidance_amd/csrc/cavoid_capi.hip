@@ -383,21 +383,11 @@ int cavoid_ahead_prepare(cavoid_env *e, int32_t n_steps, hipStream_t s, hipEvent
     uint32_t *hi_out = e->ahead_hi[in_place ? e->ahead_cur : (e->ahead_cur ^ 1)];
     hipEvent_t ev_fill = (timed_start && !capturing) ? *timed_start : nullptr;
     if (ev_fill) *timed_start = nullptr;                     // (the refill kernel opens the timed interval)
-#define CAVOID_AHEAD_CASE(NN) case NN: \
-        if (ev_fill) hipExtLaunchKernelGGL((ahead_fill_kernel<NN>), grid, block, 0, s, ev_fill, nullptr, 0, e->k, e->st.episode, hi_in, hi_out, e->pool, e->ahead_R); \
-        else hipLaunchKernelGGL((ahead_fill_kernel<NN>), grid, block, 0, s, e->k, e->st.episode, hi_in, hi_out, e->pool, e->ahead_R); \
-        break;
-    switch (e->cfg.max_agents) {
-#ifdef CAVOID_DEV_ONLY_N
-        CAVOID_AHEAD_CASE(4) CAVOID_AHEAD_CASE(10)
-#else
-        CAVOID_AHEAD_CASE(1) CAVOID_AHEAD_CASE(2) CAVOID_AHEAD_CASE(3) CAVOID_AHEAD_CASE(4) CAVOID_AHEAD_CASE(5) CAVOID_AHEAD_CASE(6)
-        CAVOID_AHEAD_CASE(7) CAVOID_AHEAD_CASE(8) CAVOID_AHEAD_CASE(9) CAVOID_AHEAD_CASE(10) CAVOID_AHEAD_CASE(11) CAVOID_AHEAD_CASE(12)
-        CAVOID_AHEAD_CASE(13) CAVOID_AHEAD_CASE(14) CAVOID_AHEAD_CASE(15) CAVOID_AHEAD_CASE(16)
-#endif
-        default: return CAVOID_EUNSUPPORTED;
-    }
-#undef CAVOID_AHEAD_CASE
+    const int rc = dispatch_n(e->cfg.max_agents, EnvNs{}, [&](auto n) -> int {
+        launch_kernel(ahead_fill_kernel<decltype(n)::value>, grid, block, 0, s, ev_fill, nullptr, e->k, e->st.episode, hi_in, hi_out, e->pool, e->ahead_R);
+        return CAVOID_OK;
+    });
+    if (rc != CAVOID_OK) return rc;
     HIP_TRY(hipGetLastError());
     if (!in_place) e->ahead_cur ^= 1;
     if (!capturing) { e->ahead_primed = true; e->ahead_budget = e->ahead_R; }
@@ -680,16 +670,13 @@ extern "C" int cavoid_policy_rows(cavoid_env *e, int32_t policy_id, int32_t only
 }
 
 #ifdef CAVOID_TRACE
-// development build only: point the kernels' phase-stamp buffer (u64 [waves][16]) somewhere
-int cavoid_debug_trace_multistep(unsigned long long *dev_ptr);
-int cavoid_debug_trace_rvo(unsigned long long *dev_ptr);
-int cavoid_debug_trace_relay(unsigned long long *dev_ptr);
+// development build only: point the env kernels' phase-stamp buffer (u64 [waves][16]) somewhere -- every env unit's copy of the pointer
 extern "C" int cavoid_debug_trace(unsigned long long *dev_ptr) {
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &dev_ptr, sizeof(dev_ptr)));
-    const int rc = cavoid_debug_trace_multistep(dev_ptr);
-    if (rc != CAVOID_OK) return rc;
-    const int rc2 = cavoid_debug_trace_rvo(dev_ptr);
-    return rc2 != CAVOID_OK ? rc2 : cavoid_debug_trace_relay(dev_ptr);
+    for (auto set : {set_trace, cavoid_debug_trace_multistep, cavoid_debug_trace_rvo, cavoid_debug_trace_relay, cavoid_debug_trace_quad}) {
+        const int rc = set(dev_ptr);
+        if (rc != CAVOID_OK) return rc;
+    }
+    return CAVOID_OK;
 }
 #endif
 

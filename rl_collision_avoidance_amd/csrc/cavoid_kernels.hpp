@@ -663,27 +663,29 @@ __device__ __forceinline__ void store16(float4 *p, const float4 &v) {
         *p = v;
     }
 }
-template <bool STREAM = false>
-__device__ __forceinline__ void flush_tile(const float *tile, float *dst, int n_floats, int lane) {
+// The strided write-out: thread tid of the nthreads that share the flush (a wavefront: lane / 64; the cooperative forms: their
+// workgroup's threads) moves the float4s tid, tid + nthreads, ..; UNROLL LDS reads in flight per thread, then their stores.
+template <int UNROLL, bool STREAM = false, bool WT = false>
+__device__ __forceinline__ void flush_tile(const float *tile, float *dst, int n_floats, int tid, int nthreads) {
     if ((n_floats & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
         const float4 *src4 = reinterpret_cast<const float4 *>(tile);
         float4 *dst4 = reinterpret_cast<float4 *>(dst);
         const int n4 = n_floats >> 2;
-        for (int k0 = lane; k0 < n4; k0 += 64 * 8) {       // 8 LDS reads in flight, then 8 stores
-            float4 v[8];
+        for (int k0 = tid; k0 < n4; k0 += nthreads * UNROLL) {
+            float4 v[UNROLL];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int k = k0 + 64 * u;
+            for (int u = 0; u < UNROLL; ++u) {
+                const int k = k0 + nthreads * u;
                 v[u] = k < n4 ? src4[k] : float4{0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int k = k0 + 64 * u;
-                if (k < n4) store16<STREAM>(dst4 + k, v[u]);
+            for (int u = 0; u < UNROLL; ++u) {
+                const int k = k0 + nthreads * u;
+                if (k < n4) store16<STREAM, WT>(dst4 + k, v[u]);
             }
         }
     } else {
-        for (int k = lane; k < n_floats; k += 64) dst[k] = tile[k];
+        for (int k = tid; k < n_floats; k += nthreads) dst[k] = tile[k];
     }
 }
 
@@ -766,6 +768,27 @@ __device__ __forceinline__ void flush_tile_fixed(const float *tile, float *dst, 
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+
+// E9: the head of an observation row (six values), the empty slots [zero_from, zero_to) and the packed record's reward / done.
+// (The empty slots go a slot -- seven floats -- per iteration: the loop runs as long as the emptiest row of the wavefront -- an absent
+//  agent's, all M slots -- so float by float it was 7 M dependent iterations per step at N = 10 with 2..10 agents present.  Measured and
+//  dropped there: straight-line predicated zero writes into the slots the not-kept neighbours rank at, +80 vector instructions per
+//  wavefront-step.)
+__device__ __forceinline__ void write_row_head(float *row, const Agent &a, const Ego &e, bool present, int kept, int zero_from, int zero_to,
+                                               bool packed, int width, float rew_f, float done_f) {
+    row[0] = (present && (a.flags & CAVOID_F_LEARNING)) ? 1.0f : 0.0f;
+    row[1] = (float)kept;                                       // 0 for an absent agent (others == 0)
+    row[2] = present ? (float)e.dist : 0.0f;
+    row[3] = present ? (float)e.heading_ego : 0.0f;
+    row[4] = present ? a.pref : 0.0f;
+    row[5] = present ? a.radius : 0.0f;
+    for (int sl = zero_from; sl < zero_to; ++sl) {
+        float *z = row + 6 + 7 * sl;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) z[q] = 0.0f;
+    }
+    if (packed) { row[width] = rew_f; row[width + 1] = done_f; }   // (obs | reward | done) gather record
 }
 
 // E9: neighbour ordering by counting ranks, the lane's observation row into the LDS tile, and the
@@ -916,12 +939,8 @@ __device__ __forceinline__ void assemble_obs(const KCfg &c, const Agent &a, cons
     if (!(CAVOID_SKIP & 4) && active && lane >= p0 && lane < p0 + rpp) {
         float *row = tile + (lane - p0) * ostride;
         if (Part::head) {
-        row[0] = (present && (a.flags & CAVOID_F_LEARNING)) ? 1.0f : 0.0f;
-        row[1] = (float)kept;                                   // 0 for an absent agent (others == 0)
-        row[2] = present ? (float)e.dist : 0.0f;
-        row[3] = present ? (float)e.heading_ego : 0.0f;
-        row[4] = present ? a.pref : 0.0f;
-        row[5] = present ? a.radius : 0.0f;
+            write_row_head(row, a, e, present, kept, zero_first ? M : kept, prev_kept ? *prev_kept : M, packed, width, rew_f, done_f);
+            if (prev_kept) *prev_kept = kept;
         }
         // r_host + r_other as ONE float32 add is bit for bit the float32 rounding of the float64 sum (the sum of two floats is
         // exact in float64).
@@ -939,20 +958,6 @@ __device__ __forceinline__ void assemble_obs(const KCfg &c, const Agent &a, cons
             }
             float *dst = row + 6 + 7 * (pos[o] - slot_bias);
             dst[0] = f[0]; dst[1] = f[1]; dst[2] = f[2]; dst[3] = f[3]; dst[4] = f[4]; dst[5] = a.radius + f[4]; dst[6] = gapf[o];
-        }
-        // unfilled slots, a slot (seven floats) per iteration: the loop runs as long as the emptiest row of the wavefront -- an absent
-        // agent's, all M slots -- so float by float it was 7 M dependent iterations per step at N = 10 with 2..10 agents present.
-        // (Measured and dropped there: straight-line predicated zero writes into the slots the not-kept neighbours rank at, +80
-        // vector instructions per wavefront-step.)
-        if (Part::head) {
-        const int zero_to = prev_kept ? *prev_kept : M;
-        for (int sl = zero_first ? M : kept; sl < zero_to; ++sl) {
-            float *z = row + 6 + 7 * sl;
-#pragma unroll
-            for (int q = 0; q < 7; ++q) z[q] = 0.0f;
-        }
-        if (packed) { row[width] = rew_f; row[width + 1] = done_f; }   // (obs | reward | done) gather record
-        if (prev_kept) *prev_kept = kept;
         }
     }
     wave_lds_sync();
@@ -975,12 +980,12 @@ __device__ __forceinline__ void assemble_obs(const KCfg &c, const Agent &a, cons
                 if (kPackedLines && lines) flush_tile_fixed<kPackedOk ? kRows * (kW + 2) : 4, true, kPackedLines>(tile, dst, lane);
                 else flush_tile_fixed<kPackedOk ? kRows * (kW + 2) : 4, true>(tile, dst, lane);
             } else {
-                flush_tile<true>(tile, dst, rows_here * ostride, lane);
+                flush_tile<8, true>(tile, dst, rows_here * ostride, lane, 64);
             }
         } else {
             if (kPlainOk && whole && ostride == kW) flush_tile_fixed<kPlainOk ? kRows * kW : 4>(tile, dst, lane);
             else if (kPackedOk && whole && ostride == kW + 2) flush_tile_fixed<kPackedOk ? kRows * (kW + 2) : 4>(tile, dst, lane);
-            else flush_tile(tile, dst, rows_here * ostride, lane);
+            else flush_tile<8>(tile, dst, rows_here * ostride, lane, 64);
         }
     }
     if (p0 + rpp < rows_active) wave_lds_sync();                 // the next pass overwrites the tile
@@ -1347,7 +1352,7 @@ __device__ __forceinline__ void env_tile(const KCfg &c, const KState &s, const P
             for (int k = 0; k < ostride; ++k) row[k] = (float)a.px + (float)k + (float)act_next;
         }
         wave_lds_sync();
-        if (io.obs && worlds_here > 0) flush_tile(tile, io.obs + w0 * N * ostride, (int)worlds_here * N * ostride, lane);
+        if (io.obs && worlds_here > 0) flush_tile<8>(tile, io.obs + w0 * N * ostride, (int)worlds_here * N * ostride, lane, 64);
         if (active) {
             if (io.rew) io.rew[a_idx] = (float)a.py;
             if (io.done) io.done[a_idx] = 0;

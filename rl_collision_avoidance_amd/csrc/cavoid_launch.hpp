@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "cavoid.h"
 #include "cavoid_host.hpp"
 #include "cavoid_kernels.hpp"
@@ -45,6 +47,44 @@ struct cavoid_env {
 
 namespace cavoid {
 
+// ---- the N-dispatch: the agents per world each launch form is instantiated for, written once per form ----------------------------------
+template <int... Ns>
+struct NList {};
+#ifdef CAVOID_DEV_ONLY_N   /* development builds: instantiate a few sizes only (compile time) */
+using EnvNs = NList<4, 10>;                 // env_kernel, env_pipe_kernel, ahead_fill_kernel, actor_kernel, step_push_kernel
+using RelayNs = NList<4>;                   // env_relay_kernel
+using QuadNs = NList<4>;                    // env_quad_kernel
+#else
+using EnvNs = NList<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>;
+using RelayNs = NList<1, 2, 3, 4, 5, 6>;    // 1 .. kRelayMaxAgents (cavoid_relay.hpp)
+using QuadNs = NList<2, 3, 4, 5, 6, 10>;
+#endif
+
+// f(std::integral_constant<int, N>{}) for the N of the list equal to n (decltype(arg)::value in f); CAVOID_EUNSUPPORTED for an n the list does not hold
+template <int... Ns, class F>
+static inline int dispatch_n(int n, NList<Ns...>, F &&f) {
+    int rc = CAVOID_EUNSUPPORTED;
+    (void)((n == Ns ? (rc = f(std::integral_constant<int, Ns>{}), true) : false) || ...);
+    return rc;
+}
+
+// one launch: the extension launch when the caller times it with events, else the plain launch (capturable into a hipGraph)
+template <class K, class... Args>
+static inline void launch_kernel(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                 const Args &...args) {
+    if (ev_start || ev_stop) hipExtLaunchKernelGGL(kernel, grid, block, lds, s, ev_start, ev_stop, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+}
+
+#ifdef CAVOID_TRACE
+// development build only: point THIS translation unit's copy of the phase-stamp pointer g_trace somewhere (every env unit has its own;
+// cavoid_debug_trace sets them all)
+static inline int set_trace(unsigned long long *dev_ptr) {
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &dev_ptr, sizeof(dev_ptr)));
+    return CAVOID_OK;
+}
+#endif
+
 // the dispatchers' bookkeeping for cavoid_last_step_form: a launch that succeeded records its form
 static inline int note_form(cavoid_env *e, int rc, int form, int relay_consumers = 0) {
     if (rc == CAVOID_OK) {
@@ -63,24 +103,11 @@ static inline int launch_on(cavoid_env *e, const KCfg &k, const KState &st, int 
     int tile = (k.tile_rows * row + 3) & ~3;
     if (tile < k.park_floats) tile = k.park_floats;
     const size_t lds = (size_t)(lds_floats_block() + e->waves_per_block * (lds_floats_fixed(e->cfg.max_agents) + k.rvo_lds_floats + tile)) * sizeof(float);
-#define CAVOID_CASE(NN) \
-    case NN:                                                                                                            \
-        if (ev_start || ev_stop)                                                                                        \
-            hipExtLaunchKernelGGL((env_kernel<NN, MODE, RVO>), grid, block, lds, s, ev_start, ev_stop, 0, k, st, e->pool, io); \
-        else /* plain launch: capturable into a hipGraph */                                                             \
-            hipLaunchKernelGGL((env_kernel<NN, MODE, RVO>), grid, block, lds, s, k, st, e->pool, io);                         \
-        break;
-    switch (e->cfg.max_agents) {
-#ifdef CAVOID_DEV_ONLY_N   /* development builds: instantiate two sizes only (compile time) */
-        CAVOID_CASE(4) CAVOID_CASE(10)
-#else
-        CAVOID_CASE(1) CAVOID_CASE(2) CAVOID_CASE(3) CAVOID_CASE(4) CAVOID_CASE(5) CAVOID_CASE(6)
-        CAVOID_CASE(7) CAVOID_CASE(8) CAVOID_CASE(9) CAVOID_CASE(10) CAVOID_CASE(11) CAVOID_CASE(12)
-        CAVOID_CASE(13) CAVOID_CASE(14) CAVOID_CASE(15) CAVOID_CASE(16)
-#endif
-        default: return CAVOID_EUNSUPPORTED;
-    }
-#undef CAVOID_CASE
+    const int rc = dispatch_n(e->cfg.max_agents, EnvNs{}, [&](auto n) -> int {
+        launch_kernel(env_kernel<decltype(n)::value, MODE, RVO>, grid, block, lds, s, ev_start, ev_stop, k, st, e->pool, io);
+        return CAVOID_OK;
+    });
+    if (rc != CAVOID_OK) return rc;
     HIP_TRY(hipGetLastError());
     return CAVOID_OK;
 }
@@ -103,27 +130,14 @@ static inline int launch_pipe(cavoid_env *e, const KIO &io, hipStream_t s, hipEv
     if (tile < k.park_floats) tile = k.park_floats;
     const size_t tail = (size_t)(tile + k.rvo_lds_floats) * sizeof(float);
     const dim3 grid((unsigned)tiles), block(128);
-#define CAVOID_PIPE_CASE(NN) \
-    case NN: {                                                                                                          \
-        const size_t lds = pipe_lds_fixed_bytes<NN>() + tail;                                                          \
-        if (lds > 65536) return CAVOID_EUNSUPPORTED;                                                                    \
-        if (ev_start || ev_stop)                                                                                        \
-            hipExtLaunchKernelGGL((env_pipe_kernel<NN, RVO>), grid, block, lds, s, ev_start, ev_stop, 0, k, e->st, e->pool, io); \
-        else                                                                                                            \
-            hipLaunchKernelGGL((env_pipe_kernel<NN, RVO>), grid, block, lds, s, k, e->st, e->pool, io);                  \
-        break;                                                                                                          \
-    }
-    switch (e->cfg.max_agents) {
-#ifdef CAVOID_DEV_ONLY_N
-        CAVOID_PIPE_CASE(4) CAVOID_PIPE_CASE(10)
-#else
-        CAVOID_PIPE_CASE(1) CAVOID_PIPE_CASE(2) CAVOID_PIPE_CASE(3) CAVOID_PIPE_CASE(4) CAVOID_PIPE_CASE(5) CAVOID_PIPE_CASE(6)
-        CAVOID_PIPE_CASE(7) CAVOID_PIPE_CASE(8) CAVOID_PIPE_CASE(9) CAVOID_PIPE_CASE(10) CAVOID_PIPE_CASE(11) CAVOID_PIPE_CASE(12)
-        CAVOID_PIPE_CASE(13) CAVOID_PIPE_CASE(14) CAVOID_PIPE_CASE(15) CAVOID_PIPE_CASE(16)
-#endif
-        default: return CAVOID_EUNSUPPORTED;
-    }
-#undef CAVOID_PIPE_CASE
+    const int rc = dispatch_n(e->cfg.max_agents, EnvNs{}, [&](auto n) -> int {
+        constexpr int N = decltype(n)::value;
+        const size_t lds = pipe_lds_fixed_bytes<N>() + tail;
+        if (lds > 65536) return CAVOID_EUNSUPPORTED;
+        launch_kernel(env_pipe_kernel<N, RVO>, grid, block, lds, s, ev_start, ev_stop, k, e->st, e->pool, io);
+        return CAVOID_OK;
+    });
+    if (rc != CAVOID_OK) return rc;
     HIP_TRY(hipGetLastError());
     return CAVOID_OK;
 }
@@ -145,3 +159,10 @@ int cavoid_launch_quad(cavoid_env *e, const cavoid::KIO &io, hipStream_t s, hipE
 int cavoid_launch_multistep(cavoid_env *e, const cavoid::KIO &io, bool prefetch, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
 // any stepping mode for an env with rvo_enabled (cavoid_rvo.hip: the instantiations that carry the ORCA policy)
 int cavoid_launch_rvo(cavoid_env *e, int mode, const cavoid::KIO &io, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
+#ifdef CAVOID_TRACE
+// development build only: cavoid::set_trace of the env units other than cavoid_capi.hip (cavoid_debug_trace calls them all)
+int cavoid_debug_trace_multistep(unsigned long long *dev_ptr);
+int cavoid_debug_trace_rvo(unsigned long long *dev_ptr);
+int cavoid_debug_trace_relay(unsigned long long *dev_ptr);
+int cavoid_debug_trace_quad(unsigned long long *dev_ptr);
+#endif

@@ -24,9 +24,5 @@ int cavoid_launch_multistep(cavoid_env *e, const KIO &io, bool prefetch, hipStre
 }
 
 #ifdef CAVOID_TRACE
-// development build only: this translation unit's copy of the phase-stamp pointer
-int cavoid_debug_trace_multistep(unsigned long long *dev_ptr) {
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &dev_ptr, sizeof(dev_ptr)));
-    return CAVOID_OK;
-}
+int cavoid_debug_trace_multistep(unsigned long long *dev_ptr) { return set_trace(dev_ptr); }
 #endif

@@ -20,33 +20,18 @@ int cavoid_launch_quad(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t e
     const int row = io.obs_stride;
     const int tile_floats = (k.tile_rows * row + 3) & ~3;
     const dim3 grid((unsigned)tiles), block(256);
-#define CAVOID_QUAD_CASE(NN) \
-    case NN: {                                                                                                          \
-        const size_t lds = quad_lds_bytes<NN>(tile_floats);                                                             \
-        if (lds > 65536) return CAVOID_EUNSUPPORTED;                                                                    \
-        if (ev_start || ev_stop)                                                                                        \
-            hipExtLaunchKernelGGL((env_quad_kernel<NN>), grid, block, lds, s, ev_start, ev_stop, 0, k, e->st, e->pool, io);  \
-        else                                                                                                            \
-            hipLaunchKernelGGL((env_quad_kernel<NN>), grid, block, lds, s, k, e->st, e->pool, io);                      \
-        break;                                                                                                          \
-    }
-    switch (e->cfg.max_agents) {
-#ifdef CAVOID_DEV_ONLY_N
-        CAVOID_QUAD_CASE(4)
-#else
-        CAVOID_QUAD_CASE(2) CAVOID_QUAD_CASE(3) CAVOID_QUAD_CASE(4) CAVOID_QUAD_CASE(5) CAVOID_QUAD_CASE(6) CAVOID_QUAD_CASE(10)
-#endif
-        default: return CAVOID_EUNSUPPORTED;
-    }
-#undef CAVOID_QUAD_CASE
+    const int rc = dispatch_n(e->cfg.max_agents, QuadNs{}, [&](auto n) -> int {
+        constexpr int N = decltype(n)::value;
+        const size_t lds = quad_lds_bytes<N>(tile_floats);
+        if (lds > 65536) return CAVOID_EUNSUPPORTED;
+        launch_kernel(env_quad_kernel<N>, grid, block, lds, s, ev_start, ev_stop, k, e->st, e->pool, io);
+        return CAVOID_OK;
+    });
+    if (rc != CAVOID_OK) return rc;
     HIP_TRY(hipGetLastError());
     return note_form(e, CAVOID_OK, CAVOID_FORM_QUAD);
 }
 
 #ifdef CAVOID_TRACE
-// development build only: this translation unit's copy of the phase-stamp pointer
-int cavoid_debug_trace_quad(unsigned long long *dev_ptr) {
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &dev_ptr, sizeof(dev_ptr)));
-    return CAVOID_OK;
-}
+int cavoid_debug_trace_quad(unsigned long long *dev_ptr) { return set_trace(dev_ptr); }
 #endif

@@ -114,30 +114,6 @@ __device__ __forceinline__ void quad_rows(const KCfg &c, QuadShared<N> &sh, cons
                                                                            PartOthers{pw, kQuadPairWaves});
 }
 
-// the tile's rows out of LDS by every wavefront of the workgroup: flush_tile with tid / nthreads for lane / 64
-__device__ __forceinline__ void quad_flush(const float *tile, float *dst, int n_floats, int tid, int nthreads) {
-    if ((n_floats & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
-        const float4 *src4 = reinterpret_cast<const float4 *>(tile);
-        float4 *dst4 = reinterpret_cast<float4 *>(dst);
-        const int n4 = n_floats >> 2;
-        for (int k0 = tid; k0 < n4; k0 += nthreads * 4) {       // up to 4 LDS reads in flight per lane, then the stores
-            float4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + nthreads * u;
-                v[u] = k < n4 ? src4[k] : float4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + nthreads * u;
-                if (k < n4) dst4[k] = v[u];
-            }
-        }
-    } else {
-        for (int k = tid; k < n_floats; k += nthreads) dst[k] = tile[k];
-    }
-}
-
 // One auto-reset step of tile `wave` by the four wavefronts (role = 0..3, wave-uniform) of a workgroup.  smem: quad_lds_bytes<N>(tile
 // floats) of the workgroup's LDS.  Contains workgroup barriers: every thread of the four wavefronts calls it.  out (role 0 only): what
 // env_tile hands a caller that goes on in the same kernel.
@@ -315,25 +291,13 @@ __device__ __forceinline__ void quad_env_tile(const KCfg &c, const KState &s, co
             s.flags[a_idx] = a.flags;
         }
         CAVOID_STAMP(6);
-        // ---- E9, the host's part: the head of the row and the empty slots (assemble_obs's statements) ------------------------------
+        // ---- E9, the host's part: the head of the row and the empty slots -----------------------------------------------------------
         if (active && lane < rows_active) {
             const int M = c.max_other;
             const int m = __popc(valid);
             const int first = m > M ? m - M : 0;
             const int kept = m - first;
-            float *row = tile + lane * ostride;
-            row[0] = (present && (a.flags & CAVOID_F_LEARNING)) ? 1.0f : 0.0f;
-            row[1] = (float)kept;
-            row[2] = present ? (float)e.dist : 0.0f;
-            row[3] = present ? (float)e.heading_ego : 0.0f;
-            row[4] = present ? a.pref : 0.0f;
-            row[5] = present ? a.radius : 0.0f;
-            for (int sl = kept; sl < M; ++sl) {
-                float *z = row + 6 + 7 * sl;
-#pragma unroll
-                for (int q = 0; q < 7; ++q) z[q] = 0.0f;
-            }
-            if (packed) { row[width] = rew_f; row[width + 1] = done_f; }
+            write_row_head(tile + lane * ostride, a, e, present, kept, kept, M, packed, width, rew_f, done_f);
         }
         __syncthreads();                                        // S3 (S5 after a restart): the rows are in the tile
     } else {
@@ -366,7 +330,7 @@ __device__ __forceinline__ void quad_env_tile(const KCfg &c, const KState &s, co
         }
     }
     // ---- every wavefront: its share of the tile flush --------------------------------------------------------------------------------
-    if (worlds_here > 0) quad_flush(tile, io.obs + w0 * N * ostride, rows_active * ostride, role * 64 + lane, 256);
+    if (worlds_here > 0) flush_tile<4>(tile, io.obs + w0 * N * ostride, rows_active * ostride, role * 64 + lane, 256);
     if (role == 0) { CAVOID_STAMP(7); CAVOID_STAMP(8); }
 }
 

@@ -6,6 +6,19 @@
 
 using namespace cavoid;
 
+// Beyond the default 64 KiB of dynamic LDS: opted into once per instantiation and process, at its first launch that needs it.  (The
+// attribute belongs to the function on the CURRENT device: a process that drives several would need it per device -- a change of
+// behaviour, left to its own change.)
+template <int N>
+static int relay_allow_lds() {
+    static bool allowed = false;
+    if (!allowed) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(env_relay_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRelayLdsLimit));
+        allowed = true;
+    }
+    return CAVOID_OK;
+}
+
 int cavoid_launch_relay(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     const KCfg &k = e->k;
     if (k.rvo_enabled || k.pool_size <= 0 || !io.obs || !io.actions || io.cont) return CAVOID_EUNSUPPORTED;
@@ -22,46 +35,26 @@ int cavoid_launch_relay(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t 
     if (k.tile_rows < k.wpw * e->cfg.max_agents) return CAVOID_EUNSUPPORTED;   // one pass per step only
     const dim3 grid((unsigned)tiles);
     int used_nc = 0;                                   // the consumer count the launch really uses (cavoid_last_step_form)
-#define CAVOID_RELAY_CASE(NN) \
-    case NN: {                                                                                                          \
-        int nc = e->relay_consumers;                                                                                    \
-        while (nc > 1 && relay_lds_fixed_bytes<NN>() + (size_t)nc * tile_floats * sizeof(float) > kRelayLdsLimit) --nc; \
-        const size_t lds = relay_lds_fixed_bytes<NN>() + (size_t)nc * tile_floats * sizeof(float);                      \
-        /* one observation wavefront cannot keep up with the loop: the two-wavefront pipeline is the better form then */  \
-        if (lds > kRelayLdsLimit || (nc < 2 && e->relay_consumers >= 2)) return CAVOID_EUNSUPPORTED;                    \
-        if (lds > 65536) {                        /* beyond the default dynamic-LDS limit: opted into once per instantiation */ \
-            static size_t allowed = 0;                                                                                  \
-            if (allowed < lds) {                                                                                        \
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(env_relay_kernel<NN>),                       \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRelayLdsLimit));          \
-                allowed = kRelayLdsLimit;                                                                               \
-            }                                                                                                           \
-        }                                                                                                               \
-        const dim3 block(64 * (3 + nc));                                                                                \
-        used_nc = nc;                                                                                                   \
-        if (ev_start || ev_stop)                                                                                        \
-            hipExtLaunchKernelGGL((env_relay_kernel<NN>), grid, block, lds, s, ev_start, ev_stop, 0, k, e->st, e->pool, io);  \
-        else                                                                                                            \
-            hipLaunchKernelGGL((env_relay_kernel<NN>), grid, block, lds, s, k, e->st, e->pool, io);                     \
-        break;                                                                                                          \
-    }
-    switch (e->cfg.max_agents) {
-#ifdef CAVOID_DEV_ONLY_N
-        CAVOID_RELAY_CASE(4)
-#else
-        CAVOID_RELAY_CASE(1) CAVOID_RELAY_CASE(2) CAVOID_RELAY_CASE(3) CAVOID_RELAY_CASE(4) CAVOID_RELAY_CASE(5) CAVOID_RELAY_CASE(6)
-#endif
-        default: return CAVOID_EUNSUPPORTED;
-    }
-#undef CAVOID_RELAY_CASE
+    const int rc = dispatch_n(e->cfg.max_agents, RelayNs{}, [&](auto n) -> int {
+        constexpr int N = decltype(n)::value;
+        int nc = e->relay_consumers;
+        while (nc > 1 && relay_lds_fixed_bytes<N>() + (size_t)nc * tile_floats * sizeof(float) > kRelayLdsLimit) --nc;
+        const size_t lds = relay_lds_fixed_bytes<N>() + (size_t)nc * tile_floats * sizeof(float);
+        // one observation wavefront cannot keep up with the loop: the two-wavefront pipeline is the better form then
+        if (lds > kRelayLdsLimit || (nc < 2 && e->relay_consumers >= 2)) return CAVOID_EUNSUPPORTED;
+        if (lds > 65536) {
+            const int rc_opt = relay_allow_lds<N>();
+            if (rc_opt != CAVOID_OK) return rc_opt;
+        }
+        used_nc = nc;
+        launch_kernel(env_relay_kernel<N>, grid, dim3(64 * (3 + nc)), lds, s, ev_start, ev_stop, k, e->st, e->pool, io);
+        return CAVOID_OK;
+    });
+    if (rc != CAVOID_OK) return rc;
     HIP_TRY(hipGetLastError());
     return note_form(e, CAVOID_OK, CAVOID_FORM_RELAY, used_nc);
 }
 
 #ifdef CAVOID_TRACE
-// development build only: this translation unit's copy of the phase-stamp pointer
-int cavoid_debug_trace_relay(unsigned long long *dev_ptr) {
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &dev_ptr, sizeof(dev_ptr)));
-    return CAVOID_OK;
-}
+int cavoid_debug_trace_relay(unsigned long long *dev_ptr) { return set_trace(dev_ptr); }
 #endif

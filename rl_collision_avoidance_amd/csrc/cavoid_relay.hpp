@@ -356,31 +356,6 @@ __device__ __forceinline__ void relay_pair_part(const KCfg &c, const Agent &a, c
         neighbour_features(e, (float)e.prll_x, (float)e.prll_y, rx, ry, q, feat[o]);
     }
 }
-// the tile's rows out of LDS by the three wavefronts (flush_tile with tid / nthreads for lane / 64)
-template <bool STREAM, bool WT = false>
-__device__ __forceinline__ void relay_flush_part(const float *tile, float *dst, int n_floats, int tid, int nthreads) {
-    if ((n_floats & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
-        const float4 *src4 = reinterpret_cast<const float4 *>(tile);
-        float4 *dst4 = reinterpret_cast<float4 *>(dst);
-        const int n4 = n_floats >> 2;
-        for (int k0 = tid; k0 < n4; k0 += nthreads * 4) {       // up to 4 LDS reads in flight per lane, then the stores
-            float4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + nthreads * u;
-                v[u] = k < n4 ? src4[k] : float4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + nthreads * u;
-                if (k < n4) store16<STREAM, WT>(dst4 + k, v[u]);
-            }
-        }
-    } else {
-        for (int k = tid; k < n_floats; k += nthreads) dst[k] = tile[k];
-    }
-}
-
 
 // Everything the three need they derive again from the kernel arguments and their thread ids, starting from two words D left in LDS at
 // kernel entry (the argument segment's address, the tile): nothing of it stays live in scalar registers across the role loops above
@@ -472,24 +447,12 @@ __device__ __forceinline__ void relay_coop_last(unsigned char *smem) {
     assemble_obs<N, false, true, ArrayStage<N>, NoHook, false, PartOthers>(c, ao, e, active, lane0, as, key, gapf, feat, valid, tile, nullptr,
                                                                            rows_active, ostride, false, 0.0f, 0.0f, wave, NoHook(), false, nullptr,
                                                                            PartOthers{pw, kRelayCoopWaves});
-    if (pw == 0 && active && lane0 < rows_active) {    // the head of the row and the empty slots (assemble_obs's statements)
+    if (pw == 0 && active && lane0 < rows_active) {    // the head of the row and the empty slots
         const int M = c.max_other;
         const int m = __popc(valid);
         const int first = m > M ? m - M : 0;
         const int kept = m - first;
-        float *row = tile + lane0 * ostride;
-        row[0] = (present && (ao.flags & CAVOID_F_LEARNING)) ? 1.0f : 0.0f;
-        row[1] = (float)kept;
-        row[2] = present ? (float)e.dist : 0.0f;
-        row[3] = present ? (float)e.heading_ego : 0.0f;
-        row[4] = present ? ao.pref : 0.0f;
-        row[5] = present ? ao.radius : 0.0f;
-        for (int sl = kept; sl < M; ++sl) {
-            float *z = row + 6 + 7 * sl;
-#pragma unroll
-            for (int q = 0; q < 7; ++q) z[q] = 0.0f;
-        }
-        if (packed) { row[c.width] = rew_c; row[c.width + 1] = done_c; }
+        write_row_head(tile + lane0 * ostride, ao, e, present, kept, kept, M, packed, c.width, rew_c, done_c);
     }
     relay_coop_arrive(&seq->coop[1], lane0);           // the rows are in the tile
     if (io.out_step_stride == 0)                       // one output buffer for every step: the last step's rows land last
@@ -499,9 +462,9 @@ __device__ __forceinline__ void relay_coop_last(unsigned char *smem) {
         float *dst = io.obs + (slot_w + w0) * N * ostride;
         // (whole 128-byte lines per tile, on a line boundary: the write-through form of the streaming store, like assemble_obs's flush)
         const bool lines = ((rows_active * ostride) & 31) == 0 && (reinterpret_cast<uintptr_t>(dst) & 127) == 0;
-        if (io.out_step_stride != 0 && lines) relay_flush_part<true, true>(tile, dst, rows_active * ostride, pw * 64 + lane0, 64 * kRelayCoopWaves);
-        else if (io.out_step_stride != 0) relay_flush_part<true>(tile, dst, rows_active * ostride, pw * 64 + lane0, 64 * kRelayCoopWaves);
-        else relay_flush_part<false>(tile, dst, rows_active * ostride, pw * 64 + lane0, 64 * kRelayCoopWaves);
+        if (io.out_step_stride != 0 && lines) flush_tile<4, true, true>(tile, dst, rows_active * ostride, pw * 64 + lane0, 64 * kRelayCoopWaves);
+        else if (io.out_step_stride != 0) flush_tile<4, true>(tile, dst, rows_active * ostride, pw * 64 + lane0, 64 * kRelayCoopWaves);
+        else flush_tile<4>(tile, dst, rows_active * ostride, pw * 64 + lane0, 64 * kRelayCoopWaves);
     }
     if (pw == 0 && active) {                           // the step's plain outputs
         if (!packed) {

@@ -25,8 +25,5 @@ int cavoid_launch_rvo(cavoid_env *e, int mode, const KIO &io, hipStream_t s, hip
 }
 
 #ifdef CAVOID_TRACE
-int cavoid_debug_trace_rvo(unsigned long long *dev_ptr) {
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &dev_ptr, sizeof(dev_ptr)));
-    return CAVOID_OK;
-}
+int cavoid_debug_trace_rvo(unsigned long long *dev_ptr) { return set_trace(dev_ptr); }
 #endif
