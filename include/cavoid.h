@@ -52,7 +52,12 @@ extern "C" {
 
 #define CAVOID_ABI_VERSION 3
 #define CAVOID_MAX_ACTIONS 32
-#define CAVOID_MAX_AGENTS 16
+/* Agents per world: 1..64.  Worlds of up to 16 agents run the tile forms below; 17..64 agents run ONE form,
+ * CAVOID_FORM_CROWD (the lanes of a world are its agents; a wavefront owns floor(64/N) whole worlds: three of 17..21 agents,
+ * two of 22..32, one of 33..64).
+ * What stops at 16 agents (CAVOID_EUNSUPPORTED for max_agents > 16): rvo_enabled and gen_lookahead > 0 (checked by
+ * cavoid_create), cavoid_actor_run, cavoid_actor_run_mix and cavoid_step_push (use the env step + cavoid_rollout_push). */
+#define CAVOID_MAX_AGENTS 64
 
 /* agent flag bits */
 #define CAVOID_F_AT_GOAL 0x01u
@@ -77,7 +82,7 @@ enum {
     CAVOID_EINVAL = -1,    /* bad argument / config */
     CAVOID_ENOMEM = -2,    /* device allocation failed */
     CAVOID_EHIP = -3,      /* a HIP runtime call failed (see cavoid_last_hip_error) */
-    CAVOID_EUNSUPPORTED = -4, /* max_agents outside the compiled range */
+    CAVOID_EUNSUPPORTED = -4, /* max_agents outside [1, CAVOID_MAX_AGENTS], or a feature that stops at 16 agents (see CAVOID_MAX_AGENTS) */
     CAVOID_ENODEVICE = -5, /* no usable gfx950 device */
     CAVOID_ECOMM = -6      /* an RCCL call failed (see cavoid_last_comm_error) */
 };
@@ -226,7 +231,8 @@ enum {
     CAVOID_FORM_LOOP_PF = 4,   /* env_kernel's in-launch step loop, next pool record in registers (MODE_STEP_AUTORESET_PF) */
     CAVOID_FORM_LOOP = 5,      /* env_kernel's in-launch step loop, restarts gathered on demand (MODE_STEP_AUTORESET_N) */
     CAVOID_FORM_PIPE = 6,      /* env_pipe_kernel: the step loop on two wavefronts per tile */
-    CAVOID_FORM_RELAY = 7      /* env_relay_kernel: the step loop cut into roles on 3 + relay_consumers wavefronts per tile */
+    CAVOID_FORM_RELAY = 7,     /* env_relay_kernel: the step loop cut into roles on 3 + relay_consumers wavefronts per tile */
+    CAVOID_FORM_CROWD = 8      /* crowd_kernel: every stepping mode of a world of 17..64 agents (one lane per agent, keys and ranks in LDS) */
 };
 int32_t cavoid_last_step_form(const cavoid_env *env, int32_t *relay_consumers);
 

@@ -14,7 +14,8 @@ from .build import LIB_PATH as _DEFAULT_LIB_PATH
 LIB_PATH = os.environ.get("CAVOID_LIB", _DEFAULT_LIB_PATH)
 
 MAX_ACTIONS = 32
-MAX_AGENTS = 16
+MAX_AGENTS = 64
+TILE_MAX_AGENTS = 16      # more agents per world: the crowd form (CAVOID_FORM_CROWD); no fused actor / step_push, no ORCA, no look-ahead
 ABI_VERSION = 3
 
 F_AT_GOAL, F_RAN_OUT, F_IN_COLL, F_WAS_AT_GOAL, F_WAS_IN_COLL, F_PRESENT, F_LEARNING = 1, 2, 4, 8, 16, 32, 64
@@ -24,7 +25,7 @@ POLICY_EXTERNAL, POLICY_STATIC, POLICY_NONCOOP, POLICY_RVO, POLICY_FROZEN_NET = 
 F_DONE_MASK = 7
 COMM_FORCE_RCCL = 1
 # CAVOID_FORM_* (cavoid_last_step_form): the kernel form a stepping launch ran, by enum value
-STEP_FORMS = ("NONE", "STEP", "QUAD", "RVO", "LOOP_PF", "LOOP", "PIPE", "RELAY")
+STEP_FORMS = ("NONE", "STEP", "QUAD", "RVO", "LOOP_PF", "LOOP", "PIPE", "RELAY", "CROWD")
 
 
 class CavoidCfg(C.Structure):

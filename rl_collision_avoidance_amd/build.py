@@ -13,9 +13,9 @@ LIB_PATH = os.path.join(PKG_DIR, "libcavoid_hip.so")
 SOURCES = [os.path.join(CSRC, "cavoid_capi.hip"), os.path.join(CSRC, "cavoid_multistep.hip"), os.path.join(CSRC, "cavoid_rvo.hip"),
            os.path.join(CSRC, "cavoid_relay.hip"), os.path.join(CSRC, "cavoid_quad.hip"), os.path.join(CSRC, "cavoid_rollout_capi.hip"),
            os.path.join(CSRC, "cavoid_policy_capi.hip"), os.path.join(CSRC, "cavoid_comm_capi.hip"), os.path.join(CSRC, "cavoid_actor.hip"),
-           os.path.join(CSRC, "cavoid_actor_rvo.hip"), os.path.join(CSRC, "cavoid_actor_frozen.hip")]
+           os.path.join(CSRC, "cavoid_actor_rvo.hip"), os.path.join(CSRC, "cavoid_actor_frozen.hip"), os.path.join(CSRC, "cavoid_crowd.hip")]
 HEADERS = {
-    "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
+    "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp"],
     "cavoid_multistep.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
     "cavoid_rvo.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
     "cavoid_relay.hip": ["cavoid_kernels.hpp", "cavoid_relay.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
@@ -29,6 +29,7 @@ HEADERS = {
     "cavoid_actor_frozen.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
                                 "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
     "cavoid_comm_capi.hip": ["cavoid_host.hpp"],
+    "cavoid_crowd.hip": ["cavoid_kernels.hpp", "cavoid_crowd.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
 }
 # per-file extra flags.  The multi-step env kernels run their step loop inside the launch; MachineLICM would hoist every
 # constant materialisation of the body (float64 polynomial coefficients, config scalars) out of that loop into
@@ -38,7 +39,9 @@ EXTRA_FLAGS = {"cavoid_multistep.hip": ["-mllvm", "-disable-machine-licm"], "cav
                # the fused actor kernel runs policy + env step + bookkeeping inside ONE step loop: same reason (without it the
                # GEMM loops' fragment addresses are hoisted across the loop: 256 VGPRs + 232 B/lane of scratch instead of 243 + 0)
                "cavoid_actor.hip": ["-mllvm", "-disable-machine-licm"], "cavoid_actor_rvo.hip": ["-mllvm", "-disable-machine-licm"],
-               "cavoid_actor_frozen.hip": ["-mllvm", "-disable-machine-licm"]}
+               "cavoid_actor_frozen.hip": ["-mllvm", "-disable-machine-licm"],
+               # the crowd form's step loop (cavoid_crowd.hpp): same reason
+               "cavoid_crowd.hip": ["-mllvm", "-disable-machine-licm"]}
 STAMP_PATH = os.path.join(PKG_DIR, "libcavoid_hip.so.stamp")
 DEPS = SOURCES + [os.path.join(CSRC, h) for hs in HEADERS.values() for h in hs] + [os.path.join(ROOT, "include", "cavoid.h")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")
@@ -176,10 +179,42 @@ def build_ulp_fault(kind: int, verbose: bool = False) -> str:
     return out
 
 
+def build_crowd_dev(verbose: bool = False) -> str:
+    """Development variant that routes EVERY agent count >= 2 to the crowd form (-DCAVOID_DEV_CROWD_FROM_N=2, dev-only N = 4, 10 for
+    the tile forms): tests/test_gpu_crowd.py holds its outputs bitwise to the product's tile forms at N = 4 and 10 -- the guard on the
+    crowd kernel's copies of env_tile's statements.  Built like the ulp-fault variants; never loaded by the product."""
+    import glob
+    from concurrent.futures import ThreadPoolExecutor
+    out = variant_path("crowd2")
+    if os.path.exists(out):
+        return out
+    build()
+    objs = _compile_objects([], "", False, verbose)
+    jobs, swap = [], {}
+    for name in ("cavoid_capi.hip", "cavoid_multistep.hip", "cavoid_crowd.hip"):     # (the units that route by agent count)
+        src = os.path.join(CSRC, name)
+        obj = os.path.join(OBJ_DIR, name.replace(".hip", ".crowd2.o"))
+        jobs.append([hipcc()] + FLAGS + EXTRA_FLAGS.get(name, []) + ["-DCAVOID_DEV_CROWD_FROM_N=2", "-DCAVOID_DEV_ONLY_N", "-c", src, "-o", obj])
+        swap[os.path.join(OBJ_DIR, name.replace(".hip", ".o"))] = obj
+    if verbose:
+        for j in jobs:
+            print(" ".join(j), flush=True)
+    with ThreadPoolExecutor(max_workers=len(jobs)) as pool:
+        list(pool.map(subprocess.check_call, jobs))
+    for old in glob.glob(os.path.join(FAULT_DIR, "libcavoid_hip_crowd2-*.so")):
+        os.remove(old)
+    tmp = out + ".tmp"
+    _link([swap.get(o, o) for o in objs], tmp, verbose)
+    os.replace(tmp, out)
+    return out
+
+
 if __name__ == "__main__":
     import sys
     if "--trace" in sys.argv:
         print(build_trace(verbose=True))
+    elif "--crowd-dev" in sys.argv:
+        print(build_crowd_dev(verbose=True))
     elif "--ulp-faults" in sys.argv:
         for kind in (1, 2, 3, 4):
             print(build_ulp_fault(kind, verbose=True))

@@ -28,6 +28,7 @@ static int actor_run(cavoid_env *e, cavoid_policy *h, cavoid_policy *frozen, cav
     // or a non-default number of split products (the kernel carries the default form of cavoid_policy_forward, so that both stay
     // bit-identical); frozen-network agents need a second network (BatchedRollout keeps those on the step-by-step path)
     if (e->cfg.dynamics == CAVOID_DYN_HOLONOMIC || !h->use_split || h->split_products != kSpDefaultProducts) return CAVOID_EUNSUPPORTED;
+    if (e->cfg.max_agents > kTileMaxAgents) return CAVOID_EUNSUPPORTED;   // (the crowd form has no fused actor: env step + cavoid_rollout_push)
     // frozen-network agents act by THEIR network: without it this entry point would hand them the learner's sample
     if (!frozen && e->cfg.gen_frozen_fraction > 0.0 && e->cfg.gen_nonlearning_fraction > 0.0) return CAVOID_EUNSUPPORTED;
     if (frozen && (!frozen->loaded || frozen->device != e->device || frozen->in_size != h->in_size || frozen->max_other != h->max_other ||
@@ -104,6 +105,7 @@ extern "C" int cavoid_step_push(cavoid_env *e, cavoid_rollout *r, const cavoid_r
         return CAVOID_EINVAL;
     if (r->device != e->device || r->c.num_slots != e->A || r->c.max_agents != e->cfg.max_agents || r->c.obs_width != e->k.width) return CAVOID_EINVAL;
     if (e->cfg.dynamics == CAVOID_DYN_HOLONOMIC) return CAVOID_EUNSUPPORTED;       // (velocity actions: cavoid_step_continuous + cavoid_rollout_push)
+    if (e->cfg.max_agents > kTileMaxAgents) return CAVOID_EUNSUPPORTED;   // (the crowd form: cavoid_step_autoreset + cavoid_rollout_push)
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc_a = cavoid_ahead_prepare(e, 1, s)) return rc_a;

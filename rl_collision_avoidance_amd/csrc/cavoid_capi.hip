@@ -13,6 +13,7 @@
 #include "cavoid_host.hpp"
 #include "cavoid_kernels.hpp"
 #include "cavoid_launch.hpp"
+#include "cavoid_crowd.hpp"
 
 using namespace cavoid;
 
@@ -28,7 +29,7 @@ extern "C" const char *cavoid_strerror(int code) {
         case CAVOID_EINVAL: return "invalid argument or configuration";
         case CAVOID_ENOMEM: return "device memory allocation failed";
         case CAVOID_EHIP: return "HIP runtime call failed (see cavoid_last_hip_error)";
-        case CAVOID_EUNSUPPORTED: return "max_agents outside the compiled range [1,16]";
+        case CAVOID_EUNSUPPORTED: return "max_agents outside [1,64], or a feature that stops at 16 agents per world";
         case CAVOID_ENODEVICE: return "no usable HIP device";
         case CAVOID_ECOMM: return "RCCL call failed (see cavoid_last_comm_error)";
         default: return "unknown error";
@@ -124,6 +125,7 @@ static int validate(const cavoid_cfg *c) {
     if (c->gen_frozen_fraction < 0.0 || c->gen_frozen_fraction > 1.0) return CAVOID_EINVAL;
     if (c->gen_rvo_fraction > 0.0 && !c->rvo_enabled) return CAVOID_EINVAL;    /* the generator would create agents the step cannot drive */
     if (c->rvo_enabled && !(c->rvo_time_horizon > 0.0 && c->rvo_radius_scale > 0.0)) return CAVOID_EINVAL;
+    if (crowd_form(c->max_agents) && (c->rvo_enabled || c->gen_lookahead > 0)) return CAVOID_EUNSUPPORTED;   /* (stop at kTileMaxAgents) */
     return CAVOID_OK;
 }
 
@@ -283,6 +285,22 @@ extern "C" int cavoid_create(const cavoid_cfg *cfg, int64_t num_worlds, int64_t 
         const int v = std::atoi(ov);
         if (v >= 1 && v <= cavoid::kRelayMaxConsumers) e->relay_consumers = v;
     }
+    if (crowd_form(N)) {
+        // the crowd form (cavoid_crowd.hpp): one wavefront per workgroup, floor(64/N) worlds per wavefront; the obs tile shares the
+        // sort keys' region (N-1 x 64 x 8 bytes) and takes as many whole rows of 4 as that holds -- the rows go out in passes
+        k.rvo_lds_floats = 0;
+        k.park_floats = 0;
+        int rows = (crowd_key_floats(N) / (k.width + 2)) & ~3;
+        if (rows < 4) rows = 4;
+        if (rows > lanes) rows = lanes;
+        if (const char *ov = std::getenv("CAVOID_TILE_ROWS")) { int v = std::atoi(ov); if (v >= 1 && v <= lanes) rows = v; }
+        k.tile_rows = rows;
+        if ((size_t)(lds_floats_block() + crowd_wave_floats(N, rows, k.width + 2)) * sizeof(float) > 65536) { cavoid_destroy(e); return CAVOID_EUNSUPPORTED; }
+        e->waves_per_block = 1;
+        e->grid = grid_for(e, num_worlds);
+        *out = e;
+        return CAVOID_OK;
+    }
     // obs tile (rows of width + 2 floats: the packed record is the widest row): the wavefront's rows in ONE pass when
     // the batch is latency bound or when they fit ~9 KiB; else several passes of a multiple of 4 rows, so that the LDS
     // footprint (and the wavefronts resident per CU) does not scale with N*(1+D)   [N=10: +7 % at saturation]
@@ -338,6 +356,10 @@ template <int MODE>
 static int launch(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
     constexpr bool stepping = MODE == MODE_STEP || MODE == MODE_STEP_AUTORESET;     // (reset / observe leave cavoid_last_step_form alone)
     if (stepping) e->last_form = CAVOID_FORM_NONE;
+    if (crowd_form(e->cfg.max_agents)) {                  // more than kTileMaxAgents agents per world: the crowd form carries every mode
+        const int rc = cavoid_launch_crowd(e, MODE, e->k, e->st, e->W, io, s, ev_start, ev_stop);
+        return stepping ? note_form(e, rc, CAVOID_FORM_CROWD) : rc;
+    }
     // the 'everything' instantiations (cavoid_rvo.hip): ORCA agents; box scenarios generated inside the auto-reset step
     if ((stepping && e->k.rvo_enabled) || (MODE == MODE_STEP_AUTORESET && e->k.gen_mode == 1 && e->k.pool_size <= 0))
         return cavoid_launch_rvo(e, MODE, io, s, ev_start, ev_stop);
@@ -419,6 +441,7 @@ static int fill_pool(cavoid_env *e, hipStream_t s) {
     KIO io{};
     io.pool_out = e->pool;
     io.n_steps = 1; io.obs_stride = k.width;
+    if (crowd_form(e->cfg.max_agents)) return cavoid_launch_crowd(e, MODE_RESET, k, st, e->pool_size, io, s, nullptr, nullptr);
     return launch_on<MODE_RESET>(e, k, st, grid_for(e, e->pool_size), io, s, nullptr, nullptr);
 }
 

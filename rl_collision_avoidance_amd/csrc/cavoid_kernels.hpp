@@ -56,6 +56,9 @@ __device__ unsigned long long *g_trace = nullptr;
 #endif
 
 constexpr double kPi = 3.14159265358979323846;
+// the largest world the tile forms (env_kernel, pipe, relay, quad, the actor) carry; 17..CAVOID_MAX_AGENTS agents run the crowd
+// form (cavoid_crowd.hpp)
+constexpr int kTileMaxAgents = 16;
 constexpr int kRelayMaxConsumers = 4;   // observation wavefronts per tile of env_relay_kernel (cavoid_relay.hpp)
 
 // Create-time constants of the rarely taken paths (scenario generators, a fresh agent's time budget, the ORCA policy, the
@@ -699,7 +702,7 @@ struct Slots {
     __device__ __forceinline__ void set(int o, int slot) { bump(o, (uint32_t)slot); }
     __device__ __forceinline__ int get(int o) const { return (int)(((o < 8 ? lo : hi) >> (4 * (o & 7))) & 15u); }
 };
-static_assert(CAVOID_MAX_AGENTS - 1 <= 15, "a slot number must fit 4 bits");
+static_assert(kTileMaxAgents - 1 <= 15, "a slot number must fit 4 bits");
 
 // Ranking by a round-robin tournament in integer arithmetic.  For every unordered pair (p, q), p < q, the sign of the 64-bit
 // difference of their keys says "p comes first"; the position of a neighbour in the order = the number of pairs it lost:

@@ -60,6 +60,15 @@ using RelayNs = NList<1, 2, 3, 4, 5, 6>;    // 1 .. kRelayMaxAgents (cavoid_rela
 using QuadNs = NList<2, 3, 4, 5, 6, 10>;
 #endif
 
+// the agent counts the crowd form (cavoid_crowd.hip) carries: kTileMaxAgents + 1 .. CAVOID_MAX_AGENTS.  The development build
+// -DCAVOID_DEV_CROWD_FROM_N=k routes every N >= k there (the drift test holds it bitwise to the tile forms at small N).
+#ifdef CAVOID_DEV_CROWD_FROM_N
+constexpr int kCrowdFromN = CAVOID_DEV_CROWD_FROM_N;
+#else
+constexpr int kCrowdFromN = kTileMaxAgents + 1;
+#endif
+static inline bool crowd_form(int max_agents) { return max_agents >= kCrowdFromN; }
+
 // f(std::integral_constant<int, N>{}) for the N of the list equal to n (decltype(arg)::value in f); CAVOID_EUNSUPPORTED for an n the list does not hold
 template <int... Ns, class F>
 static inline int dispatch_n(int n, NList<Ns...>, F &&f) {
@@ -159,6 +168,10 @@ int cavoid_launch_quad(cavoid_env *e, const cavoid::KIO &io, hipStream_t s, hipE
 int cavoid_launch_multistep(cavoid_env *e, const cavoid::KIO &io, bool prefetch, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
 // any stepping mode for an env with rvo_enabled (cavoid_rvo.hip: the instantiations that carry the ORCA policy)
 int cavoid_launch_rvo(cavoid_env *e, int mode, const cavoid::KIO &io, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
+// any mode of an env of more than kTileMaxAgents agents per world (cavoid_crowd.hip): `worlds` of k (the env's, or the pool's for the
+// pool fill) in ceil(worlds / k.wpw) one-wavefront workgroups; CAVOID_EUNSUPPORTED for a configuration the form does not carry
+int cavoid_launch_crowd(cavoid_env *e, int mode, const cavoid::KCfg &k, const cavoid::KState &st, int64_t worlds, const cavoid::KIO &io,
+                        hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
 #ifdef CAVOID_TRACE
 // development build only: cavoid::set_trace of the env units other than cavoid_capi.hip (cavoid_debug_trace calls them all)
 int cavoid_debug_trace_multistep(unsigned long long *dev_ptr);

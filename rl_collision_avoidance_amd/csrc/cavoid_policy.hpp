@@ -36,6 +36,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kPolStride = 260;        // LDS row stride in floats (260 % 64 == 4)
 constexpr int kPolHidden = 64, kPolWidth = 256, kPolHost = 4, kPolOther = 7;
 constexpr int kPolMaxOthers = 19;      // the padded input row parked at LDS columns 80.. must fit: 80 + 16 + 8M + 8 <= 260
+                                        // (mirrored by ga3c/policy_kernel.py MAX_OTHERS; tests/test_crowd_host.py holds the two equal)
 constexpr int kPolCuSlots = 4096;      // (XCC id, SE, SH, CU) keys
 constexpr int kPolXCol = 80;           // first LDS column of the normalised input row
 

@@ -16,6 +16,10 @@ from .. import _lib
 from .network import NetworkVP_rnn, split_k_factor
 
 
+# the most observed neighbours the fused policy kernels carry (kPolMaxOthers, cavoid_policy.hpp -- tests/test_crowd_host.py holds the
+# two equal): wider rows run the PyTorch network
+MAX_OTHERS = 19
+
 class FusedPolicy(object):
     accepts_strided_obs = True          # BatchedRollout hands over the env's obs tensor itself, no slice copy
 

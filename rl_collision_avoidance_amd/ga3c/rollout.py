@@ -180,7 +180,7 @@ class BatchedRollout(object):
         values = env._want(values, (env.num_worlds, env.max_agents), torch.float32, "values")
         nxt = self._obs_buffers[1 - self._cur]
         p = BatchedCollisionAvoidanceEnv._ptr
-        if self.fuse_env_push and env.cfg.dynamics != 2:
+        if self.fuse_env_push and env.cfg.dynamics != 2 and env.max_agents <= _lib.TILE_MAX_AGENTS:   # (cavoid_step_push stops at 16 agents)
             # env.step + Experience bookkeeping as ONE launch (cavoid_step_push: the fused actor's env phase as a kernel of its own)
             _lib.check(self._lib.cavoid_step_push(self._h_env(), self._h, C.byref(self._actor_buffers()), p(obs), p(nxt), p(actions), p(values),
                                                   p(env.rewards), p(env.done), p(env.game_over), -1, env._stream()), "cavoid_step_push")
@@ -212,6 +212,8 @@ class BatchedRollout(object):
         # (skip_finished -- the step-by-step path's row list of the agents that still need an action -- does not matter here: the
         #  kernel packs the rows that still need an action to the front of their tile itself and skips the empty row tiles -- unless the
         #  re-flush quirk or frozen-network agents make every row count -- and hands the others action 0 / value 0 like the row-list pass)
+        if self.env.max_agents > _lib.TILE_MAX_AGENTS:
+            return "more than 16 agents per world (the crowd step form has no fused actor kernel)"
         if not getattr(self.policy, "accepts_strided_obs", False):
             return "the policy is not a FusedPolicy"
         if cfg.rvo_enabled and cfg.max_agents > 12:

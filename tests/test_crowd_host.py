@@ -1,0 +1,104 @@
+"""CPU tests of the crowd step form's host side (worlds of 17..64 agents, CAVOID_FORM_CROWD): the agent range cavoid_create accepts,
+what it refuses above 16 agents, the header's declarations, and the built library's crowd kernels (zero scratch)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "rl_collision_avoidance_amd", "libcavoid_hip.so")
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+
+def _no_gpu():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("this test is about the GPU-less box")
+
+
+def _create(cfg):
+    from rl_collision_avoidance_amd import _lib
+    h = C.c_void_p()
+    return _lib.lib().cavoid_create(C.byref(cfg), 16, 0, 0, C.byref(h))
+
+
+def _cfg(n, m=None):
+    from rl_collision_avoidance_amd import _lib
+    cfg = _lib.CavoidCfg()
+    assert _lib.lib().cavoid_default_cfg(C.byref(cfg), n, n - 1 if m is None else m) == 0
+    return cfg
+
+
+@pytest.mark.parametrize("n", [17, 20, 33, 64])
+def test_create_accepts_up_to_64_agents(n):
+    _no_gpu()
+    assert _create(_cfg(n)) == -5            # CAVOID_ENODEVICE: the configuration passed, only the device is missing
+
+
+def test_create_refuses_65_agents():
+    _no_gpu()
+    assert _create(_cfg(65, 63)) == -4       # CAVOID_EUNSUPPORTED
+
+
+def test_features_that_stop_at_16_agents():
+    _no_gpu()
+    cfg = _cfg(20)
+    cfg.rvo_enabled = 1
+    assert _create(cfg) == -4
+    cfg = _cfg(20)
+    cfg.gen_pool_size = 0
+    cfg.gen_lookahead = 8
+    assert _create(cfg) == -4
+    cfg = _cfg(16)                           # ... which the tile forms keep
+    cfg.gen_pool_size = 0
+    cfg.gen_lookahead = 8
+    assert _create(cfg) == -5
+
+
+def test_header_declares_the_crowd_range_and_form():
+    from rl_collision_avoidance_amd import _lib
+    header = open(os.path.join(ROOT, "include", "cavoid.h")).read()
+    assert re.search(r"#define\s+CAVOID_MAX_AGENTS\s+64\b", header)
+    m = re.search(r"CAVOID_FORM_CROWD\s*=\s*(\d+)", header)
+    assert m and _lib.STEP_FORMS[int(m.group(1))] == "CROWD"
+    assert re.search(r"#define\s+CAVOID_ABI_VERSION\s+3\b", header)
+    assert _lib.MAX_AGENTS == 64
+
+
+def _kernel_notes():
+    work = tempfile.mkdtemp(prefix="cavoid_notes_")
+    try:
+        local = os.path.join(work, "lib.so")
+        shutil.copy(LIB, local)
+        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], cwd=work, check=True, stdout=subprocess.DEVNULL,
+                       stderr=subprocess.DEVNULL)
+        text = ""
+        for name in sorted(os.listdir(work)):
+            if "amdgcn-amd-amdhsa--gfx950" in name:
+                text += subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(work, name)], check=True,
+                                       stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True).stdout
+        return text
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+
+
+@pytest.mark.skipif(not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))),
+                    reason="llvm-objdump / llvm-readelf of the ROCm toolchain not present")
+def test_crowd_kernels_use_no_scratch():
+    text = _kernel_notes()
+    # every kernel's metadata block: .name, then .private_segment_fixed_size
+    found = re.findall(r"\.name:\s+(\S*crowd_kernel\S*)\s*\n\s*\.private_segment_fixed_size:\s+(\d+)", text)
+    assert len(found) == 8, found            # two buckets (32, 64) x four modes
+    assert all(int(size) == 0 for _, size in found), found
+
+
+def test_policy_neighbour_limit_mirrors_the_kernel():
+    """ga3c.train picks the PyTorch network above the fused policy kernels' neighbour limit: the Python constant is the kernel's"""
+    from rl_collision_avoidance_amd.ga3c.policy_kernel import MAX_OTHERS
+    src = open(os.path.join(ROOT, "rl_collision_avoidance_amd", "csrc", "cavoid_policy.hpp")).read()
+    m = re.search(r"constexpr\s+int\s+kPolMaxOthers\s*=\s*(\d+)\s*;", src)
+    assert m and int(m.group(1)) == MAX_OTHERS

@@ -17,6 +17,8 @@ def main():
     ap.add_argument("--plain", action="store_true", help="also launch 60 plain (no auto-reset) steps per size")
     ap.add_argument("--gen-min", type=int, default=None)
     ap.add_argument("--spl", type=int, nargs="+", default=[1, 32], help="steps per launch")
+    ap.add_argument("--slices", type=int, default=32, help="distinct pre-generated action slices = the most steps one launch can take")
+    ap.add_argument("--slots", action="store_true", help="every step of a launch writes its outputs into its own slot (the bench's form)")
     args = ap.parse_args()
     import torch
     from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
@@ -32,20 +34,24 @@ def main():
     for W in args.worlds:
         over = {} if args.gen_min is None else {"gen_min_agents": args.gen_min}
         env = BatchedCollisionAvoidanceEnv(W, Cfg(), seed=7, **over)
-        acts = torch.randint(0, 11, (32, W, N), device="cuda", dtype=torch.int32)
+        acts = torch.randint(0, 11, (args.slices, W, N), device="cuda", dtype=torch.int32)
         env.reset()
         env.step_autoreset_n(acts)
         env.step_autoreset_n(acts)
         for spl in args.spl:
-            ms = env.kernel_time_ms(acts, args.steps, spl) / min(spl, 32)
-            rec = {"W": W, "N": N, "spl": spl, "us_per_step": round(ms * 1e3, 3), "Gagent_steps_s": round(W * N / ms / 1e6, 3),
+            spl_run = min(spl, args.slices)                    # (kernel_time_ms launches at most one step per action slice)
+            slots = env.new_step_slots(spl_run) if args.slots else None
+            ms = env.kernel_time_ms(acts, args.steps, spl_run, slots=slots) / spl_run
+            del slots
+            rec = {"W": W, "N": N, "spl": spl_run, "slots": bool(args.slots), "us_per_step": round(ms * 1e3, 3),
+                   "Gagent_steps_s": round(W * N / ms / 1e6, 3),
                    "GBps": round(bytes_as * W * N / ms / 1e6, 1), "wpw": os.environ.get("CAVOID_WPW", "auto")}
             out.append(rec)
             print(json.dumps(rec), flush=True)
         if args.plain:
             env.reset()
             for t in range(60):
-                env.step(acts[t % 32])
+                env.step(acts[t % args.slices])
             torch.cuda.synchronize()
         env.close()
 
