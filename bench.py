@@ -20,12 +20,18 @@ region; the shard-only rate is reported under "extra".  Weak scaling: every rank
 (RNG keyed on global world ids).  `python bench.py --gpus N` without a launcher starts its own N ranks
 (torch.distributed.run, 127.0.0.1).  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, pre-roll and warm-up, the timed repetitions of the K steps, --dump-outputs
+when given, and the JSON line (metric, value, unit, ms_per_step, timing, config).  `--full` adds everything else the bench measures,
+after the timed region: the roofline (HIP-event kernel figures of both launch forms, the null-launch round trip, the device-copy
+ceiling, PMC traffic), the N > 1 hand-over forms beside `value`, the configs[3] extra, the other scenario sources, the brief
+configs[4] loop, the CPU baselines and the evidence legs (--evidence).  `--sweep` and `--full-loop` add their legs to any run.
+
 N > 1 forms: `--gather all` (default: every rank receives every shard, configs[2]), `--gather root` (only the trainer rank
 receives), `--gather none` (shard-only: no exchange); `--gather-every K` = env steps per launch-and-gather block.  Whatever form
-`value` is, the other two are measured briefly in the same run and all three are reported under extra.configs2_gather.forms with
+`value` is, --full measures the other two briefly in the same run and reports all three under extra.configs2_gather.forms with
 their xGMI link figures (bytes per link and step, the link-bound time at 153 GB/s per link and direction, achieved fraction).
 
-roofline: `achieved` / `frac` (= `frac_contract`) are SURVEY section 8d's contract figure -- 192 / 360 algorithmic bytes per
+roofline (--full): `achieved` / `frac` (= `frac_contract`) are SURVEY section 8d's contract figure -- 192 / 360 algorithmic bytes per
 agent-step x the agent-steps of one launch / the launch's HIP-event duration / 8 TB/s; `achieved_moved` / `frac_moved` are priced
 on the bytes the timed launch form really moves per agent-step (K-step launch: action in, observation row + reward + done
 (+ game_over) out; the world state stays in registers: 117.25 B at N = 4), `traffic` is the PMC measurement of the same
@@ -614,12 +620,15 @@ def main() -> None:
     ap.add_argument("--force-rccl", action="store_true",
                     help="N=1: put the exchange inside the timed region too, through a forced ONE-rank RCCL communicator (development: "
                          "executes ncclAllGather / the grouped send-recv on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beyond the headline: roofline, the N>1 hand-over forms, configs[3], "
+                         "the other scenario sources, the brief configs[4] loop, CPU baselines, evidence legs (trimmed by the --no-* options)")
     ap.add_argument("--sweep", action="store_true", help="add a worlds-per-GPU saturation sweep to the JSON line")
     ap.add_argument("--full-loop", action="store_true",
                     help="also time BASELINE configs[4]: batched env + NetworkVP_rnn policy + rollout bookkeeping + Adam steps")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-full-loop", action="store_true", help="skip the brief configs[4] extra of the default N = 1 run")
+    ap.add_argument("--no-full-loop", action="store_true", help="skip the brief configs[4] extra of a --full run")
     ap.add_argument("--no-configs3", action="store_true", help="skip the brief configs[3] (10 agents x 8192 worlds) extra")
     ap.add_argument("--scenarios", default="lookahead", choices=["lookahead", "pool", "instep"],
                     help="where a restarting world's scenario comes from in the HEADLINE: lookahead (default) = a fresh generator scenario per episode -- "
@@ -639,7 +648,7 @@ def main() -> None:
     ap.add_argument("--pmc-child", default="", choices=["", "step", "mfma"], help=argparse.SUPPRESS)
     ap.add_argument("--evidence", default="auto", choices=["auto", "off", "full"],
                     help="the slow evidence legs -- rocprofv3 --pmc child passes (roofline.traffic, SQ_INSTS_MFMA of the policy / actor kernels) and the "
-                         "all-host-cores CPU baselines: auto (default) = at N = 1 only, inside a 60 s budget, most important first; off; full = no "
+                         "all-host-cores CPU baselines, part of --full: auto (default) = at N = 1 only, inside a 60 s budget, most important first; off; full = no "
                          "budget, + PMC traffic of the configs[3] extra")
     ap.add_argument("--min-agents", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--reps", type=int, default=31, help="repetitions of the K-step timed region (value = the median one; capped at ~5 s of timed work)")
@@ -777,7 +786,7 @@ def main() -> None:
         return fig
 
     # ---- the slow evidence legs share one budget (--evidence): most important first, what does not fit is skipped and named ----
-    evidence_on = args.evidence == "full" or (args.evidence == "auto" and world_size == 1 and not args.no_pmc)
+    evidence_on = args.full and (args.evidence == "full" or (args.evidence == "auto" and world_size == 1 and not args.no_pmc))
     evidence = {"mode": args.evidence, "budget_s": None if args.evidence == "full" else 60.0, "spent_s": 0.0, "ran": [], "skipped": []}
 
     def evidence_left():
@@ -1021,27 +1030,29 @@ def main() -> None:
                 ts.append(time.perf_counter() - t0)
         return sorted(ts)[len(ts) // 2] * 1e6
 
-    # ---- roofline of the dominant (only) kernel ------------------------------------------------------
-    if slots is None and not args.overwrite_outputs:
-        slots = env.new_step_slots(min(args.slices, max(args.steps, 1)))
-    roofline = kernel_figures(env, acts, N, W, args.steps, slots)
-    launches = -(-args.steps // min(args.slices, max(args.steps, 1)))
-    null_us = null_roundtrip_us()
-    wall_us, kern_us = ms_per_step * 1e3, roofline["kernel_us_per_step"]
-    roofline["wall_clock"] = {
-        "us_per_step": wall_us, "kernel_us_per_step": kern_us, "wall_over_kernel": wall_us / kern_us, "launches_per_repetition": launches,
-        "null_launch_roundtrip_us": null_us,
-        "explained_us_per_step": kern_us + null_us / args.steps,
-        "note": ("within 15 % of the kernel time" if wall_us <= 1.15 * kern_us else
-                 "the K = %d timed steps are %d launch(es) bracketed by host synchronisation: the region pays one host launch + completion "
-                 "round trip (%.1f us for an empty kernel on this box) on top of %.1f us of kernel -- %.0f %% of the gap; use --steps >= 1000 "
-                 "(back-to-back launches) for a wall clock that is the kernel's" % (
-                     args.steps, launches, null_us, kern_us * args.steps,
-                     100.0 * min(1.0, null_us / max(1e-9, (wall_us - kern_us) * args.steps)))) if not gather_in_metric else
-                "with the gather inside the timed region the wall clock is step + exchange, not the step kernel alone"}
+    # ---- --full: roofline of the dominant (only) kernel ------------------------------------------------
+    roofline = None
+    if args.full:
+        if slots is None and not args.overwrite_outputs:
+            slots = env.new_step_slots(min(args.slices, max(args.steps, 1)))
+        roofline = kernel_figures(env, acts, N, W, args.steps, slots)
+        launches = -(-args.steps // min(args.slices, max(args.steps, 1)))
+        null_us = null_roundtrip_us()
+        wall_us, kern_us = ms_per_step * 1e3, roofline["kernel_us_per_step"]
+        roofline["wall_clock"] = {
+            "us_per_step": wall_us, "kernel_us_per_step": kern_us, "wall_over_kernel": wall_us / kern_us, "launches_per_repetition": launches,
+            "null_launch_roundtrip_us": null_us,
+            "explained_us_per_step": kern_us + null_us / args.steps,
+            "note": ("within 15 % of the kernel time" if wall_us <= 1.15 * kern_us else
+                     "the K = %d timed steps are %d launch(es) bracketed by host synchronisation: the region pays one host launch + completion "
+                     "round trip (%.1f us for an empty kernel on this box) on top of %.1f us of kernel -- %.0f %% of the gap; use --steps >= 1000 "
+                     "(back-to-back launches) for a wall clock that is the kernel's" % (
+                         args.steps, launches, null_us, kern_us * args.steps,
+                         100.0 * min(1.0, null_us / max(1e-9, (wall_us - kern_us) * args.steps)))) if not gather_in_metric else
+                    "with the gather inside the timed region the wall clock is step + exchange, not the step kernel alone"}
 
     value_path = sh.gather_form if (sh is not None and gather_in_metric) else "no exchange inside the timed region"
-    if sh is not None:
+    if sh is not None and args.full:
         # every hand-over form beside the one `value` is: the same K steps, barrier + synchronize on both sides, MAX over ranks,
         # median of 3 -- all (every rank receives), root (the trainer rank receives), none (shard-only, no exchange) -- each with its
         # xGMI link figures, so that a SCALE run shows the three curves and what the wire allows
@@ -1122,21 +1133,22 @@ def main() -> None:
             return 5 * 2 * n * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
         except Exception:      # noqa: BLE001 -- a reporting aid
             return None
-    if rank == 0:
-        copy_gbps = measured_copy_GBps()
-        if copy_gbps:
-            roofline["measured_copy_GBps"] = copy_gbps
-            roofline["frac_of_measured_copy"] = roofline["achieved"] / copy_gbps
-            roofline["one_step_launch"]["frac_of_measured_copy"] = roofline["one_step_launch"]["achieved"] / copy_gbps
-    if rank == 0 and evidence_on:
-        add_traffic(roofline, N, W)
-    for form in (roofline, roofline["one_step_launch"]):
-        form.setdefault("bound", bound_of(form, W, N))
-    roofline["bound_note"] = ("latency = the dependent float64 chain of the wavefront(s) that own a tile (<= 2 wavefronts per SIMD at this "
-                              "batch size); valu-issue = vector issue rate at saturation; hbm only when the measured traffic exceeds half "
-                              "the 8 TB/s pipe.  `frac` is still the HBM-roofline fraction the contract asks for.")
+    if roofline is not None:
+        if rank == 0:
+            copy_gbps = measured_copy_GBps()
+            if copy_gbps:
+                roofline["measured_copy_GBps"] = copy_gbps
+                roofline["frac_of_measured_copy"] = roofline["achieved"] / copy_gbps
+                roofline["one_step_launch"]["frac_of_measured_copy"] = roofline["one_step_launch"]["achieved"] / copy_gbps
+        if rank == 0 and evidence_on:
+            add_traffic(roofline, N, W)
+        for form in (roofline, roofline["one_step_launch"]):
+            form.setdefault("bound", bound_of(form, W, N))
+        roofline["bound_note"] = ("latency = the dependent float64 chain of the wavefront(s) that own a tile (<= 2 wavefronts per SIMD at this "
+                                  "batch size); valu-issue = vector issue rate at saturation; hbm only when the measured traffic exceeds half "
+                                  "the 8 TB/s pipe.  `frac` is still the HBM-roofline fraction the contract asks for.")
 
-    if rank == 0 and not args.no_configs3 and N != 10:
+    if args.full and rank == 0 and not args.no_configs3 and N != 10:
         # BASELINE configs[3] beside the headline: 10 agents (TrainPhase2 shape, 2..10 agents per world, M = 9) x 8192 worlds
         try:
             e3, a3 = make(8192, 10, gen_min_agents=2)
@@ -1163,7 +1175,7 @@ def main() -> None:
         except Exception as exc:      # noqa: BLE001
             extra["configs3_n10"] = {"error": repr(exc)}
 
-    if rank == 0 and not args.no_fresh_scenarios:
+    if args.full and rank == 0 and not args.no_fresh_scenarios:
         # the reference's reset semantics (TEST_CASE_FN = get_testcase_random, run-ws/config.yaml:281-283: a NEW random scenario at every
         # reset, ProcessAgent.py:107): the same K-step timed region with NO scenario pool -- every restart generates its scenario inside the
         # step kernel, exact (seed, global world id, episode) streams -- for GEN v1 (rings) and GEN v2 (boxes, rejection sampling)
@@ -1210,8 +1222,8 @@ def main() -> None:
                          "pre-generated outside the timed region.  Same K, same per-step output slots as the headline, this rank's GPU only")
         extra["scenario_sources"] = fresh
 
-    if args.full_loop or not args.no_full_loop:
-        # configs[4] beside the headline (a brief version: actors only + the fused-trainer loop, ~15 s; the PyTorch comparison
+    if args.full_loop or (args.full and not args.no_full_loop):
+        # configs[4] beside the headline (--full: a brief version, actors only + the fused-trainer loop, ~15 s; the PyTorch comparison
         # legs only with --full-loop).  At N > 1 every rank runs it on its own shard and policy replica, concurrently and
         # without any collective; rank 0 reports its own per-GPU figures.
         try:
@@ -1247,7 +1259,7 @@ def main() -> None:
         "dtype": "f64", "data": "synthetic",
         "config": {"workload": "BASELINE %s: %d agents x %d worlds per GPU, unicycle dynamics, GEN v1 synthetic scenarios, "
                                "uniform random actions pre-staged on the device, in-kernel auto-reset -- %s (the other scenario sources, "
-                               "GEN v1 and GEN v2: extra.scenario_sources); launches of up to %d steps "
+                               "GEN v1 and GEN v2, with --full: extra.scenario_sources); launches of up to %d steps "
                                "(world state in registers between the steps of a launch); %s%s"
                                % (which, N, W, SCEN_TEXT[args.scenarios], args.slices,
                                   "every step overwrites one output slot" if args.overwrite_outputs else
@@ -1260,9 +1272,11 @@ def main() -> None:
                                    "with-gather rate (wire-bound: see wire_bound_agent_steps_per_s), scaling is judged on value_shard_only"
                                    % (world_size, "every rank" if gather_root < 0 else "rank 0"))
                                   if gather_in_metric else ("worlds sharded over %d GPU(s), no data-path collective" % world_size)},
-        "roofline": roofline, "timing": timing,
+        "timing": timing,
     }
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if roofline is not None:
+        line["roofline"] = roofline
+    if args.full and rank == 0 and world_size == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(N, W, args.cpu_seconds, int(env.cfg.gen_pool_size))
         line["cpu_baseline"]["host_cpus"] = os.cpu_count()
         extra["python_reference_style_baseline"] = python_baseline(N, min(2.0, args.cpu_seconds))
@@ -1289,11 +1303,11 @@ def main() -> None:
                            "mfma_count_source": "rocprofv3 --pmc SQ_INSTS_MFMA per dispatch / steps per launch",
                            "issued_TFLOPs": per_step * MFMA_FLOP / ar["kernel_us_per_env_step"] * 1e-6,
                            "frac": per_step * MFMA_FLOP / ar["kernel_us_per_env_step"] * 1e-6 / MFMA_PEAK_TFLOPS, "pmc": m["actor_kernel"]})
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_size == 1 and not args.no_cpu_baseline:
         r = evidence_leg("python_reference_style_baseline_all_cores", 14.0, lambda left: python_baseline_all_cores(N, 2.0))
         if r is not None:
             extra["python_reference_style_baseline_all_cores"] = r
-    if rank == 0:
+    if args.full and rank == 0:
         evidence["spent_s"] = round(evidence["spent_s"], 1)
         extra["evidence"] = evidence
     # ---- what `value` is, spelled out at the top level (N > 1: which hand-over form, what the wire allows, what the >= 6x target is judged on) ----

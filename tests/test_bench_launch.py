@@ -52,7 +52,7 @@ def test_bench_refuses_a_mismatched_launcher_environment():
 @pytest.mark.gpu
 def test_bench_two_rank_dry_run_on_one_device():
     line = _run(["--gpus", "2", "--backend", "gloo", "--share-device", "--steps", "40", "--warmup", "8", "--worlds", "2048", "--reps", "5",
-                 "--no-cpu-baseline", "--no-full-loop", "--no-configs3", "--no-pmc"], 900)
+                 "--full", "--no-cpu-baseline", "--no-full-loop", "--no-configs3", "--no-pmc"], 900)
     assert line["n_gpus"] == 2 and line["steps"] == 40 and line["scaling"] == "weak"
     assert line["value"] > 0 and abs(line["value"] - 2 * 2048 * 4 * 40 / (line["ms_per_step"] * 40e-3)) / line["value"] < 1e-6
     # N > 1: the gather of the packed records is INSIDE the timed region (BASELINE configs[2]); the shard-only rate is the extra
@@ -102,7 +102,7 @@ def test_bench_eight_rank_dry_run_on_one_device():
     if have < need:
         pytest.skip("8 ranks at most 4 per device: needs %d GPUs, found %d" % (need, have))
     line = _run(["--gpus", "8", "--backend", "gloo", "--share-device", "--steps", "20", "--warmup", "5", "--worlds", "1024", "--reps", "3",
-                 "--no-cpu-baseline", "--no-full-loop", "--no-configs3", "--no-pmc", "--no-fresh-scenarios"], 1500)
+                 "--full", "--no-cpu-baseline", "--no-full-loop", "--no-configs3", "--no-pmc", "--no-fresh-scenarios"], 1500)
     assert line["n_gpus"] == 8 and line["steps"] == 20 and line["scaling"] == "weak" and line["value"] > 0
     g = line["extra"]["configs2_gather"]
     assert "error" not in g, g
@@ -118,7 +118,7 @@ def test_bench_eight_rank_dry_run_on_one_device():
 @pytest.mark.parametrize("mode", ["root", "none"])
 def test_bench_two_rank_dry_run_other_gather_forms(mode):
     line = _run(["--gpus", "2", "--backend", "gloo", "--share-device", "--steps", "40", "--warmup", "8", "--worlds", "1024", "--reps", "3",
-                 "--gather", mode, "--gather-every", "8", "--no-cpu-baseline", "--no-full-loop", "--no-configs3", "--no-pmc",
+                 "--gather", mode, "--gather-every", "8", "--full", "--no-cpu-baseline", "--no-full-loop", "--no-configs3", "--no-pmc",
                  "--no-fresh-scenarios"], 900)
     g = line["extra"]["configs2_gather"]
     assert "error" not in g, g
@@ -132,7 +132,7 @@ def test_bench_two_rank_dry_run_other_gather_forms(mode):
 def test_bench_one_gpu_with_the_exchange_through_forced_rccl():
     """N = 1 development form: the gather inside the timed region through a forced one-rank RCCL communicator (ncclAllGather on the
     communicator's stream) -- the N > 1 code path of the bench with the native transport, on the one GPU there is."""
-    line = _run(["--gpus", "1", "--force-rccl", "--steps", "40", "--warmup", "8", "--worlds", "2048", "--reps", "5", "--no-cpu-baseline",
+    line = _run(["--gpus", "1", "--force-rccl", "--steps", "40", "--warmup", "8", "--worlds", "2048", "--reps", "5", "--full", "--no-cpu-baseline",
                  "--no-full-loop", "--no-configs3", "--no-pmc", "--no-fresh-scenarios"], 900)
     g = line["extra"]["configs2_gather"]
     assert "error" not in g, g
@@ -175,12 +175,26 @@ def test_bench_falls_back_to_the_pool_when_the_lookahead_cannot_be_had():
 
 
 @pytest.mark.gpu
-def test_the_default_one_gpu_line_carries_its_evidence_and_the_mfma_rooflines():
-    """Round 6: the N = 1 line holds `roofline.traffic` (PMC), `cpu_baseline` and -- for BASELINE configs[4] -- MFMA rooflines of the policy
+def test_a_plain_run_measures_only_the_headline(tmp_path):
+    """Without --full a run sets up, warms up, times the K steps, dumps what they returned and prints the line: no roofline, no
+    baselines, no extras"""
+    out = str(tmp_path / "dump")
+    line = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--worlds", "2048", "--reps", "3", "--dump-outputs", out], 900)
+    assert line["unit"] == "agent-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["metric"] == "agent-steps/sec (env.step) at 4 agents x 2048 worlds per GPU"
+    assert line["value"] > 0 and abs(line["value"] - 2048 * 4 * 20 / (line["ms_per_step"] * 20e-3)) / line["value"] < 1e-6
+    assert line["timing"]["timed_reps"] == 3 and line["timing"]["restarts_in_timed_region"] > 0
+    assert not {"roofline", "cpu_baseline", "extra"} & set(line), sorted(line)
+    assert sorted(os.listdir(out)) == ["done.npy", "game_over.npy", "obs.npy", "rewards.npy"]
+
+
+@pytest.mark.gpu
+def test_the_full_one_gpu_line_carries_its_evidence_and_the_mfma_rooflines():
+    """Round 6: the N = 1 --full line holds `roofline.traffic` (PMC), `cpu_baseline` and -- for BASELINE configs[4] -- MFMA rooflines of the policy
     kernel and of the fused actor kernel that FOLLOW the kernels: issued flop = the matrix instructions the hardware counted
     (SQ_INSTS_MFMA) x 16 384, and the static count bench.py derives from the kernel's loop structure agrees with that count exactly for
     the stand-alone kernel (every row tile computed) and to within the live-row statistics for the actor kernel."""
-    line = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--reps", "3", "--cpu-seconds", "1", "--no-configs3", "--no-fresh-scenarios"], 900)
+    line = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--reps", "3", "--full", "--cpu-seconds", "1", "--no-configs3", "--no-fresh-scenarios"], 900)
     r = line["roofline"]
     assert r["traffic"] and 0.5 < r["traffic_over_moved"] < 2.0 and r["one_step_launch"]["traffic"]
     assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["cores"] == 1

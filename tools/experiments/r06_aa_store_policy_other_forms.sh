@@ -3,7 +3,7 @@
 # the pipeline / single-wavefront loops) and the saturated shapes, bench.py's slot form.   ms_sc1 = TU=cavoid_multistep tools/mkrelayvariant.sh ms_sc1 -DCAVOID_STREAM_POLICY=1
 o=$PWD/gpurun_out/r06_aa; mkdir -p $o
 ( timeout 300 python tools/launch_latency.py 2>&1 | grep -v "amdgpu.ids\|^RCCL\|^HIP ver\|^ROCm\|^Hostname\|^Librccl" ) > $o/launch_latency.txt
-bn() { echo -n "$1 bench $2: "; if [ "$1" = product ]; then L=""; else L=$PWD/.ab/lib$1.so; fi; env ${L:+CAVOID_LIB=$L} timeout 400 python bench.py $2 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc --evidence off 2>/dev/null | python -c "
+bn() { echo -n "$1 bench $2: "; if [ "$1" = product ]; then L=""; else L=$PWD/.ab/lib$1.so; fi; env ${L:+CAVOID_LIB=$L} timeout 400 python bench.py $2 --full --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc --evidence off 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('value %.4e wall_us_per_step %.4f kernel_us %.3f frac %.4f %s' % (d['value'], d['ms_per_step'] * 1e3, r['kernel_us'], r['frac'], r['kernel'][:60]))"; }

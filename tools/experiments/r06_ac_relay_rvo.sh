@@ -9,7 +9,7 @@ db=$(find /tmp/rp_orca -name "*.db" | head -1); [ -n "$db" ] && python tools/roc
 ( timeout 900 python -m pytest tests/test_gpu_packed.py tests/test_gpu_parity.py tests/test_gpu_relay_fault.py tests/test_gpu_lookahead.py tests/test_gpu_actor.py -x -q --tb=short 2>&1 | flt | tail -15 ) > $o/tests.txt
 ( RELAY_SOAK_RVO_P=0.6 timeout 300 python tools/relay_soak.py 90 2>&1 | grep -a "soak\|MISMATCH" ) > $o/relay_soak.txt
 for a in "--steps 20 --warmup 5" ""; do
-( timeout 600 python bench.py $a --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc 2>/dev/null | python -c "
+( timeout 600 python bench.py $a --full --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('bench $a: value %.4e wall_us_per_step %.4f kernel_us %.3f frac %.4f' % (d['value'], d['ms_per_step'] * 1e3, r['kernel_us'], r['frac']))

@@ -8,7 +8,7 @@ for rep in 1 2 3; do
   kb dev1 "HIP_FORCE_DEV_KERNARG=1"
 done
 for v in "CAVOID_X=0" "HIP_FORCE_DEV_KERNARG=0" "HIP_FORCE_DEV_KERNARG=1"; do
-  echo -n "bench K=20 [$v]: "; env $v timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc --no-fresh-scenarios --evidence off 2>/dev/null | python -c "
+  echo -n "bench K=20 [$v]: "; env $v timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc --no-fresh-scenarios --evidence off 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('value %.4e wall_us_per_step %.4f kernel_us %.3f one-step %.3f null_roundtrip %.1f' % (d['value'], d['ms_per_step'] * 1e3, r['kernel_us'], r['one_step_launch']['kernel_us'], r['wall_clock']['null_launch_roundtrip_us']))"

@@ -3,8 +3,8 @@ o=$PWD/gpurun_out/r06_final_check; mkdir -p $o
 flt() { grep -av "amdgpu.ids\|^RCCL\|^HIP ver\|^ROCm\|^Hostname\|^Librccl"; }
 ( timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | flt | tail -3 ) > $o/smoke.txt
 ( timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | flt | tail -6 ) > $o/pytest_gpu.txt
-( timeout 600 python bench.py --steps 20 --warmup 5 > $o/bench_k20.json 2> $o/bench_k20.err; echo "rc=$?" ) > $o/bench_rc.txt
-( /usr/bin/time -v timeout 900 python bench.py > $o/bench.json 2> $o/bench.err; echo "rc=$?" ) >> $o/bench_rc.txt 2>&1
+( timeout 600 python bench.py --full --steps 20 --warmup 5 > $o/bench_k20.json 2> $o/bench_k20.err; echo "rc=$?" ) > $o/bench_rc.txt
+( /usr/bin/time -v timeout 900 python bench.py --full > $o/bench.json 2> $o/bench.err; echo "rc=$?" ) >> $o/bench_rc.txt 2>&1
 grep -a "Elapsed" $o/bench.err >> $o/bench_rc.txt
 cat $o/smoke.txt $o/pytest_gpu.txt $o/bench_rc.txt
 python - <<PY

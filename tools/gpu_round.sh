@@ -1,9 +1,9 @@
 #!/bin/bash
-# One GPU session: the whole -m gpu suite, the default bench line, kernel sweeps.  usage: bash tools/gpu_round.sh <tag>
+# One GPU session: the whole -m gpu suite, the --full bench lines, kernel sweeps.  usage: bash tools/gpu_round.sh <tag>
 tag=${1:-r03x}; out=gpurun_out/$tag; mkdir -p $out
 timeout 1500 python -m pytest tests -x -q -m gpu > $out/pytest.log 2>&1; echo "pytest rc=$?" >> $out/pytest.log
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" >> $out/bench.err
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc > $out/bench_k20.json 2>> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" >> $out/bench.err
+timeout 600 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc > $out/bench_k20.json 2>> $out/bench.err
 timeout 300 python tools/kbench.py --worlds 8192 --agents 4 --spl 1 20 32 > $out/kbench.log 2>&1
 timeout 300 python tools/kbench.py --worlds 8192 --agents 10 --spl 1 20 32 >> $out/kbench.log 2>&1
 tail -3 $out/pytest.log; tail -2 $out/bench.err; grep -v amdgpu.ids $out/kbench.log

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The part of tools/profile_round.sh that concerns the K-step relay kernel (4 x 8192): rocprofv3 kernel-trace stats of the default line and of the
+# The part of tools/profile_round.sh that concerns the K-step relay kernel (4 x 8192): rocprofv3 kernel-trace stats of the --full line and of the
 # driver's K = 20 form, PMC traffic of the 64-step and one-step launches, the driver's command line itself, and the role timeline.
 # usage: bash tools/profile_relay.sh <tag>   (on the GPU box)
 tag=${1:-r06_e}; out=$PWD/gpurun_out/prof_$tag; mkdir -p $out; repo=$PWD
@@ -11,8 +11,8 @@ prof() {   # prof <name> <bench args...>
   db=$(find /tmp/rp_$name -name "*.db" | head -1)
   if [ -n "$db" ]; then python $repo/tools/rocprof_summary.py $db $out/${tag}_${name}.csv "rocprofv3 --kernel-trace --stats -- python bench.py $*" > /dev/null; else echo "no db for $name" >> $out/errors.txt; find /tmp/rp_$name | head >> $out/errors.txt; fi
 }
-prof kernel_trace_stats --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
-prof kernel_trace_stats_k20 --steps 20 --warmup 5 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
+prof kernel_trace_stats --full --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
+prof kernel_trace_stats_k20 --full --steps 20 --warmup 5 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
 for spec in "4 8192 64" "4 8192 1"; do set -- $spec
   python - <<PY > $out/${tag}_pmc_traffic_n$1_w$2_k$3.json 2>> $out/errors.txt
 import json, sys

@@ -10,12 +10,12 @@ prof() {   # prof <name> <bench args...>
   db=$(find /tmp/rp_$name -name "*.db" | head -1)
   if [ -n "$db" ]; then python $repo/tools/rocprof_summary.py $db $out/${tag}_${name}.csv "rocprofv3 --kernel-trace --stats -- python bench.py $*" > /dev/null; else echo "no db for $name" >> $out/errors.txt; find /tmp/rp_$name | head >> $out/errors.txt; fi
 }
-prof kernel_trace_stats --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
-prof kernel_trace_stats_k20 --steps 20 --warmup 5 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
-prof kernel_trace_stats_n10 --agents 10 --no-cpu-baseline --no-full-loop --no-pmc
-prof kernel_trace_stats_w1048576 --worlds 1048576 --slices 16 --steps 128 --warmup 32 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
-prof kernel_trace_stats_n10_w262144 --agents 10 --worlds 262144 --slices 16 --steps 128 --warmup 32 --no-cpu-baseline --no-full-loop --no-pmc
-prof full_loop_kernel_trace_stats --steps 256 --warmup 64 --no-cpu-baseline --no-configs3 --no-pmc
+prof kernel_trace_stats --full --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
+prof kernel_trace_stats_k20 --full --steps 20 --warmup 5 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
+prof kernel_trace_stats_n10 --full --agents 10 --no-cpu-baseline --no-full-loop --no-pmc
+prof kernel_trace_stats_w1048576 --full --worlds 1048576 --slices 16 --steps 128 --warmup 32 --no-cpu-baseline --no-full-loop --no-configs3 --no-pmc
+prof kernel_trace_stats_n10_w262144 --full --agents 10 --worlds 262144 --slices 16 --steps 128 --warmup 32 --no-cpu-baseline --no-full-loop --no-pmc
+prof full_loop_kernel_trace_stats --full --steps 256 --warmup 64 --no-cpu-baseline --no-configs3 --no-pmc
 # PMC traffic (separate passes per counter, --kernel-trace only beside --pmc)
 for spec in "4 8192 64" "4 8192 1" "10 8192 64" "10 8192 1" "4 1048576 16" "10 262144 16"; do set -- $spec
   python - <<PY > $out/${tag}_pmc_traffic_n$1_w$2_k$3.json 2>> $out/errors.txt
@@ -41,8 +41,8 @@ timeout 900 python tools/pmc.py actor_kernel $out/${tag}_actor_pmc.json "SQ_BUSY
 (hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/ubench/cu_scaling.hip -o /tmp/cus 2>/dev/null && /tmp/cus > $out/${tag}_cu_scaling.txt) 2>> $out/errors.txt
 (hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/ubench/wave_placement.hip -o /tmp/wp 2>/dev/null && /tmp/wp > $out/${tag}_wave_placement.txt) 2>> $out/errors.txt
 for n in 16384 32768; do CAVOID_LIB=tests/_variants/libcavoid_hip_trace.so python tools/trace_policy.py $n 2>&1 | grep -v "amdgpu.ids\|pair " ; done > $out/${tag}_policy_phase_trace.txt
-timeout 1500 python bench.py --sweep --full-loop > $out/${tag}_bench.json 2>> $out/errors.txt
-timeout 900 python bench.py --agents 10 --sweep --no-full-loop > $out/${tag}_bench_n10.json 2>> $out/errors.txt
+timeout 1500 python bench.py --full --sweep --full-loop > $out/${tag}_bench.json 2>> $out/errors.txt
+timeout 900 python bench.py --full --agents 10 --sweep --no-full-loop > $out/${tag}_bench_n10.json 2>> $out/errors.txt
 timeout 300 python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_k20.json 2>> $out/errors.txt   # the driver's command line
 ls -la $out; cat $out/errors.txt 2>/dev/null | tail -5
 head -c 1500 $out/${tag}_kernel_trace_stats.csv; head -c 900 $out/${tag}_pmc_traffic_n4_w8192_k64.json
