@@ -360,8 +360,8 @@ int cavoid_rollout_push(cavoid_rollout *r, const float *prev_obs, const int32_t 
  * Worlds with ORCA agents (rvo_enabled) and GEN v2 scenarios generated inside the step run over the env step's ORCA instantiation,
  * as in cavoid_step_autoreset.
  * CAVOID_EUNSUPPORTED (use the step-by-step entry points): holonomic dynamics, CAVOID_POLICY_F32 / a non-default
- * CAVOID_POLICY_PRODUCTS, rvo_enabled with so many agents per world (> 12) that the ORCA lines do not fit into the LDS the
- * policy lends the env step.  Frozen-network agents (CAVOID_POLICY_FROZEN_NET) act by a SECOND network: cavoid_actor_run_mix carries it;
+ * CAVOID_POLICY_PRODUCTS, a policy (or frozen) handle of more than 19 observed agents (a crowd handle: an env of <= 16 agents padded
+ * wider), rvo_enabled with so many agents per world (> 12) that the ORCA lines do not fit into the LDS the policy lends the env step.  Frozen-network agents (CAVOID_POLICY_FROZEN_NET) act by a SECOND network: cavoid_actor_run_mix carries it;
  * this entry point refuses an env whose generator makes such agents (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0).  The
  * refusal looks at the GENERATOR's fractions only: frozen-network agents put into the worlds some other way -- cavoid_set_state, or a
  * scenario pool filled under another configuration -- are NOT detected here and would be handed the learner's sampled action; callers
@@ -430,7 +430,15 @@ int cavoid_rollout_active_rows(cavoid_rollout *r, const float *obs, const uint8_
  *                          p_out float [rows, num_actions] (softmax_p incl. MIN_POLICY), v_out float [rows].
  *                          actions_out (nullable) int32 [rows]: greedy != 0 -> argmax p (PLAY_MODE /
  *                          EVALUATE_MODE), else one inverse-CDF sample per row from Philox4x32-10 keyed on
- *                          (seed, row, launch counter); the counter lives on the device (hipGraph replays). */
+ *                          (seed, row, launch counter); the counter lives on the device (hipGraph replays).
+ * Observed agents: cavoid_policy_create takes max_other 1..64 (the env's own limit); 65 and up is CAVOID_EINVAL.
+ *   max_other <= 19: every kernel below -- the inference forms (CAVOID_POLICY_F32 / _PRODUCTS / _FORM), the trainer pass, the fused actor.
+ *   20..64, a CROWD handle: inference only, on one kernel that streams the observed agents through a ring of input slots; a row of
+ *     <= 19 observed agents gets bit for bit what a handle of max_other <= 19 gives it.  Two product forms: the default (float16 pieces) and
+ *     CAVOID_POLICY_PRODUCTS=3 (bf16 pieces, float32's range); CAVOID_POLICY_F32=1 or _PRODUCTS=4 / 5 make cavoid_policy_create return
+ *     CAVOID_EUNSUPPORTED, CAVOID_POLICY_FORM is ignored.  cavoid_policy_forward / _rows take a row_stride up to 455 floats (1 + 6 + 7 * 64:
+ *     the widest env observation row; 256 for max_other <= 19).  cavoid_policy_train and cavoid_actor_run / _run_mix return
+ *     CAVOID_EUNSUPPORTED: the trainer pass and the actor kernel park the whole input row and stop at 19. */
 typedef struct cavoid_policy_weights {
     int32_t struct_size;             /* sizeof(cavoid_policy_weights) */
     float min_policy;                /* Config.MIN_POLICY */
@@ -454,7 +462,7 @@ int cavoid_policy_seed(cavoid_policy *p, uint64_t seed, void *stream);
  * weight beyond that (after the LSTM gate columns' scale of log2 e / 2 log2 e) is CLAMPED at load and the network then differs from the
  * reference's float32 predictor; clamped_weights = how many weights of the last cavoid_policy_load were (0 for every sane checkpoint;
  * reading it synchronises `stream`).  A caller that finds it non-zero should re-create the handle with CAVOID_POLICY_PRODUCTS=3 (bf16
- * pieces: float32's range) or CAVOID_POLICY_F32=1.  Inputs and hidden activations beyond +-65504 saturate in the kernel the same way.
+ * pieces: float32's range) or, for max_other <= 19 only, CAVOID_POLICY_F32=1.  Inputs and hidden activations beyond +-65504 saturate in the kernel the same way.
  * Any out pointer may be NULL. */
 int cavoid_policy_info(cavoid_policy *p, void *stream, int32_t *use_split, int32_t *split_products, int32_t *clamped_weights);
 int cavoid_policy_forward(cavoid_policy *p, const float *x, int64_t rows, int64_t row_stride, float *p_out, float *v_out,

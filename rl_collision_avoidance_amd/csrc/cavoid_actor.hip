@@ -29,6 +29,8 @@ static int actor_run(cavoid_env *e, cavoid_policy *h, cavoid_policy *frozen, cav
     // bit-identical); frozen-network agents need a second network (BatchedRollout keeps those on the step-by-step path)
     if (e->cfg.dynamics == CAVOID_DYN_HOLONOMIC || !h->use_split || h->split_products != kSpDefaultProducts) return CAVOID_EUNSUPPORTED;
     if (e->cfg.max_agents > kTileMaxAgents) return CAVOID_EUNSUPPORTED;   // (the crowd form has no fused actor: env step + cavoid_rollout_push)
+    // the actor kernel parks the whole input row (kPolMaxOthers): a crowd policy handle, M > 19 (an env of <= 16 agents padded wider), runs step by step
+    if (h->max_other > kPolMaxOthers || (frozen && frozen->max_other > kPolMaxOthers)) return CAVOID_EUNSUPPORTED;
     // frozen-network agents act by THEIR network: without it this entry point would hand them the learner's sample
     if (!frozen && e->cfg.gen_frozen_fraction > 0.0 && e->cfg.gen_nonlearning_fraction > 0.0) return CAVOID_EUNSUPPORTED;
     if (frozen && (!frozen->loaded || frozen->device != e->device || frozen->in_size != h->in_size || frozen->max_other != h->max_other ||

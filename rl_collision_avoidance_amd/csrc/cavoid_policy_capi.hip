@@ -11,6 +11,7 @@
 #include <cstring>
 #include "cavoid_policy_split.hpp"
 #include "cavoid_policy_split8.hpp"
+#include "cavoid_policy_crowd.hpp"
 #include "cavoid_policy_host.hpp"
 
 #include <cstdlib>
@@ -20,7 +21,8 @@ using namespace cavoid;
 extern "C" int cavoid_policy_create(int32_t max_other, int32_t num_actions, int device, cavoid_policy **out) {
     if (!out) return CAVOID_EINVAL;
     *out = nullptr;
-    if (max_other < 1 || max_other > kPolMaxOthers || num_actions < 1 || num_actions > 15) return CAVOID_EINVAL;
+    // M <= kPolMaxOthers: every kernel; up to kPolMaxOthersInference: a CROWD handle -- inference only, on policy_crowd_forward_kernel
+    if (max_other < 1 || max_other > kPolMaxOthersInference || num_actions < 1 || num_actions > 15) return CAVOID_EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return CAVOID_ENODEVICE;
     HIP_TRY(hipSetDevice(device));
@@ -48,6 +50,10 @@ extern "C" int cavoid_policy_create(int32_t max_other, int32_t num_actions, int 
     // locked one barrier apart (policy_forward_split_duo_kernel)
     // Default (-1): duo once the launch has at least two tiles per compute unit (below that a paired workgroup would leave CUs idle), else quad.
     if (const char *ov = std::getenv("CAVOID_POLICY_FORM")) h->form = !std::strcmp(ov, "oct") ? 1 : (!std::strcmp(ov, "duo") ? 2 : (!std::strcmp(ov, "pipe") ? 3 : (!std::strcmp(ov, "quad") ? 0 : -1)));
+    h->crowd = max_other > kPolMaxOthers;
+    if (h->crowd && (!h->use_split || (h->split_products != kSpF16 && h->split_products != 3))) {   // (the crowd kernel's two product forms)
+        (void)hipFree(h->slab); delete h; return CAVOID_EUNSUPPORTED;
+    }
     if (hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->num_cus <= 0) h->num_cus = 256;
     h->avg = reinterpret_cast<float *>(b + o_avg); h->std = reinterpret_cast<float *>(b + o_std);
     h->step_counter = reinterpret_cast<int32_t *>(b + o_step); h->blocks_done = reinterpret_cast<uint32_t *>(b + o_done);
@@ -73,7 +79,11 @@ extern "C" int cavoid_policy_create(int32_t max_other, int32_t num_actions, int 
         hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)policy_split_lds_bytes()) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split_duo_kernel<kSpF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_duo_lds_bytes()) != hipSuccess) {
+                            (int)policy_split_duo_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_crowd_forward_kernel<kSpF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)policy_split_lds_bytes()) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_crowd_forward_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)policy_split_lds_bytes()) != hipSuccess) {
         g_last_hip_error = (int)hipGetLastError(); (void)hipFree(h->slab); delete h; return CAVOID_EHIP;
     }
     *out = h;
@@ -151,7 +161,7 @@ extern "C" int cavoid_policy_seed(cavoid_policy *h, uint64_t seed, void *stream)
 
 static int policy_forward(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const int32_t *row_index,
                           const int32_t *row_count, float *p_out, float *v_out, int32_t *actions_out, int32_t greedy, void *stream) {
-    if (!h || !x || !p_out || !v_out || rows < 0 || row_stride < h->in_size || row_stride > 256) return CAVOID_EINVAL;
+    if (!h || !x || !p_out || !v_out || rows < 0 || row_stride < h->in_size || row_stride > (h->crowd ? kPolCrowdMaxStride : 256)) return CAVOID_EINVAL;
     if (!h->loaded) return CAVOID_EINVAL;
     if (rows == 0) return CAVOID_OK;
     PolicyArgs a{};
@@ -165,7 +175,12 @@ static int policy_forward(cavoid_policy *h, const float *x, int64_t rows, int64_
     const int tile = 16 * h->row_tiles;
     const int64_t blocks = (rows + tile - 1) / tile;
     if (blocks > 0x7fffffffLL) return CAVOID_EINVAL;
-    if (h->use_split) {
+    if (h->crowd) {                                        // (one form: CAVOID_POLICY_FORM does not apply)
+        const SplitArgs sa{a, h->sfrags, h->sbias};
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (h->split_products == kSpF16) hipLaunchKernelGGL(policy_crowd_forward_kernel<kSpF16>, dim3((unsigned)blocks), dim3(256), policy_split_lds_bytes(), s, sa);
+        else hipLaunchKernelGGL(policy_crowd_forward_kernel<3>, dim3((unsigned)blocks), dim3(256), policy_split_lds_bytes(), s, sa);
+    } else if (h->use_split) {
         SplitArgs sa{a, h->sfrags, h->sbias};
         hipStream_t s = static_cast<hipStream_t>(stream);
         const int form = h->form >= 0 ? h->form : (blocks >= 2 * (int64_t)h->num_cus ? 2 : 0);
@@ -201,6 +216,7 @@ extern "C" int cavoid_policy_train(cavoid_policy *h, const float *x, int64_t row
                                    const int32_t *a_idx, float beta, float log_epsilon, const cavoid_policy_train_buffers *b,
                                    void *stream) {
     if (!h || !x || !y_r || !a_idx || !b || b->struct_size != (int32_t)sizeof(cavoid_policy_train_buffers)) return CAVOID_EINVAL;
+    if (h->crowd) return CAVOID_EUNSUPPORTED;              // (the trainer pass parks the whole row: kPolMaxOthers)
     if (!h->loaded || !h->backward_loaded || rows < 0 || row_stride < h->in_size) return CAVOID_EINVAL;
     const int64_t rows64 = (rows + 63) / 64 * 64;
     if (b->capacity_rows < rows64 || b->capacity_rows % 64 != 0 || !b->z1 || !b->z2 || !b->z3 || !b->l1_in || !b->h_in || !b->save || !b->gh || !b->loss ||

@@ -23,6 +23,7 @@ struct cavoid_policy {
     int form = -1;                   // CAVOID_POLICY_FORM = quad (0) / oct (1) / duo (2) / unset (-1: duo from two tiles per CU on, else quad): the stand-alone inference
                                      // launch's tile-to-wavefront mapping (same results in every form)
     int num_cus = 256;
+    bool crowd = false;              // max_other > kPolMaxOthers: inference on policy_crowd_forward_kernel only (cavoid_policy_crowd.hpp)
     bool use_split = true;           // CAVOID_POLICY_F32=1: run inference on the float32-MFMA kernel instead (A/B runs)
     float *bias = nullptr, *avg = nullptr, *std = nullptr;
     int32_t *step_counter = nullptr;

@@ -240,6 +240,24 @@ struct SpSomeRows { static constexpr bool dyn = true; int n; __device__ __forcei
 // picks one per tile and step by ONE scalar branch -- scalar tests around every group of matrix instructions cost more than the skipped
 // row tiles saved: profiles/r05_l_row_compaction.txt)
 template <int NRT> struct SpFirstRows { static constexpr bool dyn = true; __device__ __forceinline__ constexpr bool has(int nt) const { return nt < NRT; } };
+// Which input slot holds observed agent t during the LSTM (policy_split_tile's Ring parameter).  SpNoRing: the whole row is parked at staging,
+// agent t in slot 1 + t (M <= kSpMaxOthers).  SpRing<R>: slots 1..R are a ring -- agent t in slot 1 + t % R; staging parks agents 0..R-1, and
+// agent t + R is fetched from global memory at the start of LSTM step t and written into slot 1 + t % R behind the barrier that ends step t's
+// GEMM (cavoid_policy_crowd.hpp).  Same statements on the same values: only the slot column differs.
+struct SpNoRing {
+    static constexpr bool on = false;
+    static constexpr int slots = 0;
+    __device__ __forceinline__ static int slot(int t) { return 1 + t; }
+};
+template <int R> struct SpRing {
+    static_assert(R >= 1 && R <= kSpMaxOthers, "the ring's slots must fit columns 64..255");
+    static constexpr bool on = true;
+    static constexpr int slots = R;
+    __device__ __forceinline__ static int slot(int t) { return 1 + t % R; }
+};
+// the ring's fetched values, live across a step's GEMM (an empty type without the ring: the plain pass compiles to the instructions it had)
+struct SpRingRegs { float v[2], avg[2], sd[2]; };
+struct SpNoRingRegs {};
 struct SplitYes { static constexpr bool value = true; };
 struct SplitNo { static constexpr bool value = false; };
 struct SplitW { uint4 w[3][4]; };                            // weight fragments of one chunk: plane x column tile
@@ -616,13 +634,15 @@ namespace cavoid {
 // wavefront; at least one bit, at most 16 NRT) comes from the caller, which picks the instantiation.
 // PIPE: the LSTM steps and layer1 run as a software pipeline over row halves, their cell updates / epilogue inside the other half's matrix
 // instructions (cavoid_policy_pipe.hpp); same results.
-template <int P, int NRT = 0, bool PIPE = false, class Load, class Emit>
+// Ring: where observed agent t sits during the LSTM (SpNoRing / SpRing<R>, above): a ring of R slots lets M exceed kSpMaxOthers.
+template <int P, int NRT = 0, bool PIPE = false, class Ring = SpNoRing, class Load, class Emit>
 __device__ __forceinline__ void policy_split_tile(const SplitArgs &sa, unsigned char *planes, float *len_f, int *wave_max, int rows_here,
                                                   int tid, Load load, Emit emit, unsigned long long live_mask = ~0ull, int *rmap = nullptr,
                                                   int steps_total = -1) {
     const PolicyArgs &p = sa.p;
     constexpr bool F16 = SplitFmt<P>::f16;
     constexpr bool COMPACT = NRT > 0;
+    static_assert(!Ring::on || (!COMPACT && !PIPE), "the slot ring is carried by the plain four-wavefront pass");
     using RT = typename std::conditional<COMPACT, SpFirstRows<(NRT > 0 ? NRT : 4)>, SpAllRows>::type;
     // (wave in a scalar register: every weight / bias address is then a uniform base + this lane's constant 32-bit offset, and the
     //  fragment loads need no vector address arithmetic)
@@ -674,7 +694,8 @@ __device__ __forceinline__ void policy_split_tile(const SplitArgs &sa, unsigned 
         }
         if (tid < 128)                                      // the zero column (256..263) of every row of both planes
             *reinterpret_cast<uint4 *>(planes + (tid >> 6) * kSpPlaneB + (tid & 63) * kSpStrideB + kSpZeroCol * 2) = uint4{0u, 0u, 0u, 0u};
-        const int items = 64 * (M + 1);                    // (row, slot): slot 0 = host (4 values), slot s = observed agent s-1 (7)
+        const int staged = Ring::on && M > Ring::slots ? Ring::slots : M;   // observed agents parked here (the ring: the first R)
+        const int items = 64 * (staged + 1);               // (row, slot): slot 0 = host (4 values), slot s = observed agent s-1 (7)
         for (int it = tid; it < items; it += 256) {
             const int r = it & 63, s = it >> 6;
             const int n_in = s == 0 ? kPolHost : kPolOther, sc0 = s == 0 ? 1 : 1 + kPolHost + kPolOther * (s - 1);
@@ -797,12 +818,47 @@ __device__ __forceinline__ void policy_split_tile(const SplitArgs &sa, unsigned 
             constexpr bool ALL_LIVE = decltype(all_live_c)::value;
             f32x4 acc[4][4];
             if (t == 1) POLICY_STAMP(8);
-            split_gemm<P>(planes, src, w_lstm, t == 0 ? 2 : 0, kSpChLstm, 2, kSpSlotCol + 8 * (1 + t), wave, lane, f0, acc,
+            // RING: agent t + R of every tile row -- thread (wavefront w, lane l) fetches elements 2w, 2w + 1 of tile row l now, while this
+            // step's GEMM still reads the slot, and normalises, splits and parks them there behind the barrier (the staging's statements)
+            typename std::conditional<Ring::on, SpRingRegs, SpNoRingRegs>::type rg;
+            if constexpr (Ring::on) {
+                if (t + Ring::slots < steps) {
+                    const int sc0 = 1 + kPolHost + kPolOther * (t + Ring::slots), e1 = 2 * wave + 1;
+                    const int k0 = sc0 + 2 * wave, k1 = e1 < kPolOther ? sc0 + e1 : sc0;
+                    const int rr = lane < rows_here ? lane : 0;
+                    rg.v[0] = load(rr, k0); rg.v[1] = load(rr, k1);
+                    if (p.avg) { rg.avg[0] = p.avg[k0]; rg.avg[1] = p.avg[k1]; rg.sd[0] = p.std[k0]; rg.sd[1] = p.std[k1]; }
+                }
+            }
+            split_gemm<P>(planes, src, w_lstm, t == 0 ? 2 : 0, kSpChLstm, 2, kSpSlotCol + 8 * Ring::slot(t), wave, lane, f0, acc,
                           t + 1 < steps ? w_lstm : (int)kSpOffL1, 0, kBiasLstm, b4,
                           t + 1 < steps ? kBiasLstm : kBiasL1, rt);             // (requests the next step's / layer1's first fragments and bias)
             if (t == 1) POLICY_STAMP(9);
             __syncthreads();                                   // every wavefront has read h
             if (t == 1) POLICY_STAMP(10);
+            if constexpr (Ring::on) {
+                if (t + Ring::slots < steps) {
+                    const bool row_ok = lane < rows_here;
+                    float v[2];
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) v[e] = rg.v[e];
+                    if (p.avg) {
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) v[e] = (v[e] - rg.avg[e]) * __builtin_amdgcn_rcpf(rg.sd[e]);
+                    }
+                    v[0] = row_ok ? v[0] : 0.0f;
+                    v[1] = (row_ok && 2 * wave + 1 < kPolOther) ? v[1] : 0.0f;
+                    if constexpr (F16) {
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], -kSpF16Max, kSpF16Max);
+                    }
+                    uint32_t hi, lo;
+                    split2<F16>(v[0], v[1], hi, lo);
+                    unsigned char *d = planes + lane * kSpStrideB + sp_phys(kSpSlotCol + 8 * Ring::slot(t)) + 4 * wave;   // (elements 2w, 2w + 1 of the slot)
+                    *reinterpret_cast<uint32_t *>(d) = hi;
+                    *reinterpret_cast<uint32_t *>(d + kSpPlaneB) = lo;
+                }
+            }
             // lane: row 16nt + l%16, hidden units 16w + 4g + r; column tile = gate (i, j, f, o).  dynamic_rnn: rows past their own
             // length keep (c, h)
     #pragma unroll

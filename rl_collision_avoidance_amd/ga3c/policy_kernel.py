@@ -16,9 +16,12 @@ from .. import _lib
 from .network import NetworkVP_rnn, split_k_factor
 
 
-# the most observed neighbours the fused policy kernels carry (kPolMaxOthers, cavoid_policy.hpp -- tests/test_crowd_host.py holds the
-# two equal): wider rows run the PyTorch network
+# the most observed neighbours the fused trainer and the fused actor kernel carry (kPolMaxOthers, cavoid_policy.hpp -- tests/test_crowd_host.py
+# holds the two equal): wider rows train through autograd and act step by step
 MAX_OTHERS = 19
+# ... and fused inference (FusedPolicy: predict_p_and_v + select_action), on the crowd kernel above MAX_OTHERS (kPolMaxOthersInference,
+# cavoid_policy_crowd.hpp)
+MAX_OTHERS_INFERENCE = 64
 
 class FusedPolicy(object):
     accepts_strided_obs = True          # BatchedRollout hands over the env's obs tensor itself, no slice copy
@@ -32,6 +35,9 @@ class FusedPolicy(object):
         self.net, self.device = net, dev
         self.num_actions, self.max_others, self.input_size = net.num_actions, net.max_others, net.input_size
         self.forget_bias = float(forget_bias)
+        if self.max_others > MAX_OTHERS_INFERENCE:
+            raise ValueError("FusedPolicy carries up to %d observed neighbours, the network observes %d" % (MAX_OTHERS_INFERENCE, self.max_others))
+        self.crowd = self.max_others > MAX_OTHERS      # the crowd handle: inference only, float16 or bf16 pieces (include/cavoid.h)
         self._lib = _lib.lib()
         h = C.c_void_p()
         _lib.check(self._lib.cavoid_policy_create(self.max_others, self.num_actions, dev.index or 0, C.byref(h)), "cavoid_policy_create")
@@ -89,9 +95,10 @@ class FusedPolicy(object):
         if check_range and self.inference_form == ("split", 16):
             bad = self.clamped_weights()
             if bad:
+                escape = ("CAVOID_POLICY_PRODUCTS=3 (bf16 pieces, float32's range; the one other form above %d observed neighbours)" % MAX_OTHERS
+                          if self.crowd else "CAVOID_POLICY_PRODUCTS=3 (bf16 pieces, float32's range) or CAVOID_POLICY_F32=1")
                 raise ValueError("%d weight(s) lie beyond +-65504 (after the LSTM gates' log2 e scale): the default float16-split inference "
-                                 "form would clamp them.  Create the policy with CAVOID_POLICY_PRODUCTS=3 (bf16 pieces, float32's range) or "
-                                 "CAVOID_POLICY_F32=1 in the environment." % bad)
+                                 "form would clamp them.  Create the policy with %s in the environment." % (bad, escape))
 
     def _f32(self, t: torch.Tensor) -> torch.Tensor:
         t = t.detach()
@@ -150,6 +157,9 @@ class FusedA3CTrainer(object):
     def __init__(self, net: NetworkVP_rnn, policy: Optional[FusedPolicy] = None, learning_rate: float = 2e-5, group=None,
                  distributed: Optional[bool] = None):
         from .network import A3CTrainer
+        if net.max_others > MAX_OTHERS:
+            raise ValueError("the fused trainer carries up to %d observed neighbours (kPolMaxOthers), the network observes %d: "
+                             "train with A3CTrainer (autograd)" % (MAX_OTHERS, net.max_others))
         self.net = net
         self.policy = policy if policy is not None else FusedPolicy(net)
         self._base = A3CTrainer(net, learning_rate=learning_rate, group=group, distributed=distributed)

@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib
 from ..batched_env import BatchedCollisionAvoidanceEnv
+from .policy_kernel import MAX_OTHERS as POLICY_MAX_OTHERS
 
 Policy = Callable[[torch.Tensor], Tuple[torch.Tensor, torch.Tensor]]   # x[B, D] -> (p[B, A], v[B])
 
@@ -216,6 +217,10 @@ class BatchedRollout(object):
             return "more than 16 agents per world (the crowd step form has no fused actor kernel)"
         if not getattr(self.policy, "accepts_strided_obs", False):
             return "the policy is not a FusedPolicy"
+        for who, pol in (("policy", self.policy), ("frozen policy", self.frozen_policy)):
+            if getattr(pol, "max_others", 0) > POLICY_MAX_OTHERS:
+                return "the %s observes %d neighbours (the fused actor kernel carries up to %d; the crowd policy kernel acts step by step)" % (
+                    who, pol.max_others, POLICY_MAX_OTHERS)
         if cfg.rvo_enabled and cfg.max_agents > 12:
             return "ORCA agents with more than 12 agents per world (the line scratch does not fit the lent LDS)"
         if cfg.dynamics == 2:

@@ -1,0 +1,43 @@
+"""CPU tests of the crowd policy handle's host side (20..64 observed agents, cavoid_policy_crowd.hpp): the neighbour range
+cavoid_policy_create accepts, the Python mirror of the kernel's limit, and the built library's crowd policy kernels (zero scratch)."""
+import ctypes as C
+import os
+import re
+
+import pytest
+
+from tests.test_crowd_host import LLVM, ROOT, _kernel_notes, _no_gpu
+
+
+def _policy_create(m):
+    from rl_collision_avoidance_amd import _lib
+    h = C.c_void_p()
+    return _lib.lib().cavoid_policy_create(m, 11, 0, C.byref(h))
+
+
+@pytest.mark.parametrize("m", [20, 31, 63, 64])
+def test_policy_create_accepts_crowd_rows(m):
+    _no_gpu()
+    assert _policy_create(m) == -5           # CAVOID_ENODEVICE: the range check passed, only the device is missing
+
+
+def test_policy_create_refuses_65_neighbours():
+    _no_gpu()
+    assert _policy_create(65) == -1          # CAVOID_EINVAL
+
+
+def test_inference_neighbour_limit_mirrors_the_kernel():
+    from rl_collision_avoidance_amd.ga3c.policy_kernel import MAX_OTHERS, MAX_OTHERS_INFERENCE
+    src = open(os.path.join(ROOT, "rl_collision_avoidance_amd", "csrc", "cavoid_policy_crowd.hpp")).read()
+    m = re.search(r"constexpr\s+int\s+kPolMaxOthersInference\s*=\s*(\d+)\s*;", src)
+    assert m and int(m.group(1)) == MAX_OTHERS_INFERENCE == 64
+    assert MAX_OTHERS == 19                  # the fused trainer and actor keep theirs
+
+
+@pytest.mark.skipif(not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))),
+                    reason="llvm-objdump / llvm-readelf of the ROCm toolchain not present")
+def test_crowd_policy_kernels_use_no_scratch():
+    text = _kernel_notes()
+    found = re.findall(r"\.name:\s+(\S*policy_crowd_forward_kernel\S*)\s*\n\s*\.private_segment_fixed_size:\s+(\d+)", text)
+    assert len(found) == 2, found            # the float16 and the bf16 product form
+    assert all(int(size) == 0 for _, size in found), found

@@ -1,5 +1,6 @@
 """Time the fused policy kernel against the PyTorch-ROCm graph of the same network (development aid).
-usage: python tools/polbench.py [rows] [max_other]"""
+usage: python tools/polbench.py [rows] [max_other]      (max_other 1..64: above 19 the handle runs the crowd kernel, cavoid_policy_crowd.hpp)
+Every row observes max_other agents.  fused_us: predict + sampled select_action (act); forward_us: predict only; torch_us: predict_p_and_v."""
 import os
 import sys
 
@@ -38,12 +39,15 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / n
     t_fused = timeit(lambda: pol.act(x))
+    t_forward = timeit(lambda: pol(x))
     t_torch = timeit(lambda: net.predict_p_and_v(x))
     t_load = timeit(pol.refresh)
     chunks = (1 + 5 * (M - 1)) + 5 + 16 + 16
     flop = B * (chunks * 16 * 256 * 2 + 256 * 16 * 2)
     useful = B * 2 * ((7 + 64 * (M - 1) + 7 * (M - 1)) * 256 + 68 * 256 + 2 * 256 * 256 + 256 * 12)
-    print({"form": os.environ.get("CAVOID_POLICY_FORM", "quad"), "rows": B, "max_other": M, "fused_us": round(t_fused, 1), "torch_us": round(t_torch, 1), "pack_us": round(t_load, 1),
+    form = "crowd" if pol.crowd else os.environ.get("CAVOID_POLICY_FORM", "quad")
+    print({"form": form, "products": pol.inference_form[1], "rows": B, "max_other": M, "fused_us": round(t_fused, 1), "forward_us": round(t_forward, 1),
+           "torch_us": round(t_torch, 1), "speedup_act": round(t_torch / t_fused, 2), "pack_us": round(t_load, 1),
            "issued_TFLOPs": round(flop / t_fused * 1e-6, 1), "useful_TFLOPs": round(useful / t_fused * 1e-6, 1),
            "frac_of_157TF_issued": round(flop / t_fused * 1e-6 / 157.3, 3)})
 
