@@ -502,6 +502,41 @@ typedef struct cavoid_policy_train_buffers {
 int cavoid_policy_train(cavoid_policy *p, const float *x, int64_t rows, int64_t row_stride, const float *y_r, const int32_t *a_idx,
                         float beta, float log_epsilon, const cavoid_policy_train_buffers *buffers, void *stream);
 
+/* ---- the weight-sharing network (MULTI_AGENT_ARCH 'weight_sharing', ga3c/GA3C/NetworkVP_rnn.py:69-92) ----------------------
+ * Every observed-agent slot i < max_other goes through ONE shared dense filter, also past the row's own count:
+ *   f_i = relu([xn_i (7) | is_on_i] . other_kernel[8, 64] + other_bias[64]),  is_on_i = (x[:,0] >= i + 1) on the RAW count,
+ *   layer1 = relu([host(4) | f_0 .. f_{max_other-1}] . layer1_kernel[4 + 64 max_other, 256] + layer1_bias), then layer2,
+ *   fullyconnected1 and the heads as for the LSTM network.  Float32 MFMA (no split form; the products are exact float32).
+ *   cavoid_policy_create_ws: max_other 1..19 (the kernel parks the whole input row); 20..64 is CAVOID_EUNSUPPORTED, outside 1..64
+ *       CAVOID_EINVAL (the range is checked before the device).
+ *   cavoid_policy_load_ws  : w as for cavoid_policy_load, except that w->layer1_kernel is [4 + 64 max_other, 256] (rows: host, then
+ *       slot-major) and the lstm fields and forget_bias are ignored; other_kernel [8, 64], other_bias [64].
+ *   cavoid_policy_forward / _forward_rows / _seed / _info / _destroy take either kind of handle (same arguments, same action draw;
+ *       _info reports use_split = 0, split_products = 0).  cavoid_policy_load / _train on a weight-sharing handle, and _load_ws /
+ *       _train_ws on an LSTM handle, are CAVOID_EINVAL; cavoid_actor_run / _run_mix with one (as policy or frozen) are
+ *       CAVOID_EUNSUPPORTED.  CAVOID_POLICY_F32 / _PRODUCTS / _FORM do not apply.
+ *   cavoid_policy_train_ws : the trainer pass of cavoid_policy_train for this network (load with with_backward = 1).  The caller's GEMMs:
+ *       d fullyconnected1 = z2^T g3,  d layer2 = z1^T g2,  d [logits_p | logits_v] = z3^T gh,
+ *       d layer1 = l1_in^T g1 (rows in the checkpoint's order),  d other_kernel = f_in^T gf over all max_other * capacity_rows rows;
+ *       bias gradients in db: other_bias at 0..63, then layer1 / layer2 / fullyconnected1 / heads at 256 / 512 / 768 / 1024. */
+typedef struct cavoid_policy_train_ws_buffers {
+    int32_t struct_size;             /* sizeof(cavoid_policy_train_ws_buffers) */
+    int32_t reserved;
+    int64_t capacity_rows;           /* a multiple of 64, >= rows rounded up to 64; every row is written (past `rows`: zero gradients) */
+    float *z1, *z2, *z3;             /* [capacity_rows, 256] */
+    float *l1_in;                    /* [capacity_rows, 4 + 64 max_other]: [host | f_0 .. f_{max_other-1}] */
+    float *f_in;                     /* [max_other, capacity_rows, 8]: [xn_i | is_on_i] */
+    float *gh;                       /* [capacity_rows, 16] */
+    float *loss;                     /* [2] cost_p, cost_v */
+    float *g1, *g2, *g3;             /* [capacity_rows, 256] */
+    float *gf;                       /* [max_other, capacity_rows, 64]: d cost / d f_i, masked by the filter's relu */
+    float *db;                       /* [1040] */
+} cavoid_policy_train_ws_buffers;
+int cavoid_policy_create_ws(int32_t max_other, int32_t num_actions, int device, cavoid_policy **out);
+int cavoid_policy_load_ws(cavoid_policy *p, const cavoid_policy_weights *w, const float *other_kernel, const float *other_bias, void *stream);
+int cavoid_policy_train_ws(cavoid_policy *p, const float *x, int64_t rows, int64_t row_stride, const float *y_r, const int32_t *a_idx,
+                           float beta, float log_epsilon, const cavoid_policy_train_ws_buffers *buffers, void *stream);
+
 /* kernel timing helper: HIP events recorded on `stream` around the launches of the calls made
  * between begin and end; end synchronises and returns elapsed milliseconds */
 int cavoid_timer_begin(cavoid_env *env, void *stream);

@@ -67,6 +67,12 @@ class CavoidPolicyTrainBuffers(C.Structure):
         (n, C.c_void_p) for n in ("z1", "z2", "z3", "l1_in", "h_in", "save", "gh", "loss", "g1", "g2", "g3", "gl", "db")]
 
 
+class CavoidPolicyTrainWsBuffers(C.Structure):
+    """Mirror of ``struct cavoid_policy_train_ws_buffers`` (include/cavoid.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("capacity_rows", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("z1", "z2", "z3", "l1_in", "f_in", "gh", "loss", "g1", "g2", "g3", "gf", "db")]
+
+
 class CavoidRolloutBuffers(C.Structure):
     """Mirror of ``struct cavoid_rollout_buffers`` (include/cavoid.h): the experience store handed to ``cavoid_actor_run``."""
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32)] + [
@@ -145,6 +151,9 @@ SYMBOLS = [
     ("cavoid_policy_info", C.c_int, [_P, _P] + [C.POINTER(C.c_int32)] * 3),
     ("cavoid_policy_forward", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int32, _P]),
     ("cavoid_policy_train", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_float, C.POINTER(CavoidPolicyTrainBuffers), _P]),
+    ("cavoid_policy_create_ws", C.c_int, [C.c_int32, C.c_int32, C.c_int, C.POINTER(_P)]),
+    ("cavoid_policy_load_ws", C.c_int, [_P, C.POINTER(CavoidPolicyWeights), _P, _P, _P]),
+    ("cavoid_policy_train_ws", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_float, C.POINTER(CavoidPolicyTrainWsBuffers), _P]),
     ("cavoid_timer_begin", C.c_int, [_P, _P]),
     ("cavoid_timer_end", C.c_int, [_P, _P, C.POINTER(C.c_float)]),
 ]

@@ -18,6 +18,8 @@ static int actor_run(cavoid_env *e, cavoid_policy *h, cavoid_policy *frozen, cav
     if (!b->x || !b->val || !b->ret || !b->act || !b->emit_t || !b->dup_x || !b->dup_r || !b->dup_a || !b->dup_src || !b->dup_count ||
         !b->ep_out || !b->ep_count || b->dup_capacity < 1 || b->ep_capacity < 1)
         return CAVOID_EINVAL;
+    // the actor kernel embeds the LSTM pass: a weight-sharing handle (cavoid_policy_create_ws) acts step by step
+    if (h->ws || (frozen && frozen->ws)) return CAVOID_EUNSUPPORTED;
     if (n_steps == 0) return CAVOID_OK;
     if (!h->loaded) return CAVOID_EINVAL;
     // the three handles must describe the same batch

@@ -98,6 +98,7 @@ extern "C" void cavoid_policy_destroy(cavoid_policy *h) {
 
 extern "C" int cavoid_policy_load(cavoid_policy *h, const cavoid_policy_weights *w, void *stream) {
     if (!h || !w || w->struct_size != (int32_t)sizeof(cavoid_policy_weights)) return CAVOID_EINVAL;
+    if (h->ws) return CAVOID_EINVAL;                       // (a weight-sharing handle loads with cavoid_policy_load_ws)
     if (!w->lstm_kernel || !w->lstm_bias || !w->layer1_kernel || !w->layer1_bias || !w->layer2_kernel || !w->layer2_bias ||
         !w->fc1_kernel || !w->fc1_bias || !w->p_kernel || !w->p_bias || !w->v_kernel || !w->v_bias)
         return CAVOID_EINVAL;
@@ -139,7 +140,7 @@ extern "C" int cavoid_policy_load(cavoid_policy *h, const cavoid_policy_weights 
 extern "C" int cavoid_policy_info(cavoid_policy *h, void *stream, int32_t *use_split, int32_t *split_products, int32_t *clamped_weights) {
     if (!h) return CAVOID_EINVAL;
     if (use_split) *use_split = h->use_split ? 1 : 0;
-    if (split_products) *split_products = h->split_products;
+    if (split_products) *split_products = h->ws ? 0 : h->split_products;   // (a weight-sharing handle: float32 MFMA, no split)
     if (clamped_weights) {                                  // (the one host read-back: waits for the load enqueued on `stream`)
         uint32_t n = 0;
         if (h->loaded) {
@@ -175,6 +176,7 @@ static int policy_forward(cavoid_policy *h, const float *x, int64_t rows, int64_
     const int tile = 16 * h->row_tiles;
     const int64_t blocks = (rows + tile - 1) / tile;
     if (blocks > 0x7fffffffLL) return CAVOID_EINVAL;
+    if (h->ws) return cavoid_policy_ws_launch(h, a, blocks, static_cast<hipStream_t>(stream));
     if (h->crowd) {                                        // (one form: CAVOID_POLICY_FORM does not apply)
         const SplitArgs sa{a, h->sfrags, h->sbias};
         hipStream_t s = static_cast<hipStream_t>(stream);
@@ -216,6 +218,7 @@ extern "C" int cavoid_policy_train(cavoid_policy *h, const float *x, int64_t row
                                    const int32_t *a_idx, float beta, float log_epsilon, const cavoid_policy_train_buffers *b,
                                    void *stream) {
     if (!h || !x || !y_r || !a_idx || !b || b->struct_size != (int32_t)sizeof(cavoid_policy_train_buffers)) return CAVOID_EINVAL;
+    if (h->ws) return CAVOID_EINVAL;                       // (a weight-sharing handle trains with cavoid_policy_train_ws)
     if (h->crowd) return CAVOID_EUNSUPPORTED;              // (the trainer pass parks the whole row: kPolMaxOthers)
     if (!h->loaded || !h->backward_loaded || rows < 0 || row_stride < h->in_size) return CAVOID_EINVAL;
     const int64_t rows64 = (rows + 63) / 64 * 64;

@@ -24,6 +24,7 @@ struct cavoid_policy {
                                      // launch's tile-to-wavefront mapping (same results in every form)
     int num_cus = 256;
     bool crowd = false;              // max_other > kPolMaxOthers: inference on policy_crowd_forward_kernel only (cavoid_policy_crowd.hpp)
+    bool ws = false;                 // MULTI_AGENT_ARCH 'weight_sharing' (cavoid_policy_create_ws): frags / bias hold the pack of cavoid_policy_ws.hpp
     bool use_split = true;           // CAVOID_POLICY_F32=1: run inference on the float32-MFMA kernel instead (A/B runs)
     float *bias = nullptr, *avg = nullptr, *std = nullptr;
     int32_t *step_counter = nullptr;
@@ -32,3 +33,6 @@ struct cavoid_policy {
     int row_tiles = 4;               // 16-row tiles per workgroup (64 rows, 2 workgroups per CU); the 32-row / 4-per-CU
                                      // instantiation was measured and dropped: 175 vs 132 us
 };
+
+// the inference launch of a weight-sharing handle (cavoid_policy_ws.hip): cavoid_policy_forward / _rows route there
+int cavoid_policy_ws_launch(cavoid_policy *h, const cavoid::PolicyArgs &a, int64_t blocks, hipStream_t stream);

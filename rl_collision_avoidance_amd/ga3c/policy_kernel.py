@@ -1,6 +1,6 @@
 """``FusedPolicy`` -- the actors' ``predict_p_and_v`` (+ ``select_action``) as one MFMA kernel launch.
 
-Host mirror of ``cavoid_policy_*`` (include/cavoid.h): takes a ``NetworkVP_rnn`` (arch 'rnn'), hands its
+Host mirror of ``cavoid_policy_*`` (include/cavoid.h): takes a ``NetworkVP_rnn`` (arch 'rnn' or 'weight_sharing'), hands its
 parameters to the library in the reference checkpoint's layout, and is then callable like
 ``NetworkVPCore.predict_p_and_v`` (/root/reference/ga3c/GA3C/NetworkVPCore.py:175-176).  The network module stays
 the single owner of the weights (the trainer updates it); call ``refresh()`` after an optimiser step.
@@ -22,25 +22,34 @@ MAX_OTHERS = 19
 # ... and fused inference (FusedPolicy: predict_p_and_v + select_action), on the crowd kernel above MAX_OTHERS (kPolMaxOthersInference,
 # cavoid_policy_crowd.hpp)
 MAX_OTHERS_INFERENCE = 64
+# the most observed neighbours the weight-sharing kernels carry, inference and trainer alike (kWsMaxOthers, cavoid_policy_ws.hpp --
+# tests/test_policy_ws_host.py holds the two equal): wider weight-sharing rows act and train through PyTorch
+MAX_OTHERS_WS = 19
 
 class FusedPolicy(object):
     accepts_strided_obs = True          # BatchedRollout hands over the env's obs tensor itself, no slice copy
 
     def __init__(self, net: NetworkVP_rnn, seed: int = 0, forget_bias: float = 1.0):
-        if net.arch != "rnn":
-            raise ValueError("FusedPolicy implements MULTI_AGENT_ARCH 'rnn' (the recorded configuration)")
+        if net.arch not in ("rnn", "weight_sharing"):
+            raise ValueError("FusedPolicy implements MULTI_AGENT_ARCH 'rnn' and 'weight_sharing', not %r" % (net.arch,))
+        self.arch = net.arch
         dev = net.layer1_kernel.device
         if dev.type != "cuda":
             raise ValueError("FusedPolicy needs the network on the GPU")
         self.net, self.device = net, dev
         self.num_actions, self.max_others, self.input_size = net.num_actions, net.max_others, net.input_size
         self.forget_bias = float(forget_bias)
+        self.ws = self.arch == "weight_sharing"      # the weight-sharing kernels (cavoid_policy_create_ws): float32 MFMA, no split form
+        if self.ws and self.max_others > MAX_OTHERS_WS:
+            raise ValueError("FusedPolicy carries the weight_sharing network up to %d observed neighbours (kWsMaxOthers), the network "
+                             "observes %d" % (MAX_OTHERS_WS, self.max_others))
         if self.max_others > MAX_OTHERS_INFERENCE:
             raise ValueError("FusedPolicy carries up to %d observed neighbours, the network observes %d" % (MAX_OTHERS_INFERENCE, self.max_others))
         self.crowd = self.max_others > MAX_OTHERS      # the crowd handle: inference only, float16 or bf16 pieces (include/cavoid.h)
         self._lib = _lib.lib()
         h = C.c_void_p()
-        _lib.check(self._lib.cavoid_policy_create(self.max_others, self.num_actions, dev.index or 0, C.byref(h)), "cavoid_policy_create")
+        create = self._lib.cavoid_policy_create_ws if self.ws else self._lib.cavoid_policy_create
+        _lib.check(create(self.max_others, self.num_actions, dev.index or 0, C.byref(h)), "cavoid_policy_create" + ("_ws" if self.ws else ""))
         self._h = h
         # the inference form is fixed at creation (CAVOID_POLICY_F32 / CAVOID_POLICY_PRODUCTS are read by cavoid_policy_create only)
         use_split, products = C.c_int32(), C.c_int32()
@@ -88,6 +97,13 @@ class FusedPolicy(object):
         self._keep = []                  # tensors that had to be made contiguous stay alive until the next refresh
         if n.normalize:
             w.avg, w.std = ptr(n.avg), ptr(n.std)
+        if self.ws:                      # (the lstm fields stay NULL: cavoid_policy_load_ws ignores them)
+            for name in ("layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel", "fc1_bias", "p_kernel", "p_bias",
+                         "v_kernel", "v_bias"):
+                setattr(w, name, ptr(getattr(n, name)))
+            _lib.check(self._lib.cavoid_policy_load_ws(self._h, C.byref(w), ptr(n.other_kernel), ptr(n.other_bias), self._stream()),
+                       "cavoid_policy_load_ws")
+            return
         for name in ("lstm_kernel", "lstm_bias", "layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias",
                      "fc1_kernel", "fc1_bias", "p_kernel", "p_bias", "v_kernel", "v_bias"):
             setattr(w, name, ptr(getattr(n, name)))
@@ -157,7 +173,8 @@ class FusedA3CTrainer(object):
     def __init__(self, net: NetworkVP_rnn, policy: Optional[FusedPolicy] = None, learning_rate: float = 2e-5, group=None,
                  distributed: Optional[bool] = None):
         from .network import A3CTrainer
-        if net.max_others > MAX_OTHERS:
+        self.ws = net.arch == "weight_sharing"          # cavoid_policy_train_ws (limit: FusedPolicy's MAX_OTHERS_WS)
+        if not self.ws and net.max_others > MAX_OTHERS:
             raise ValueError("the fused trainer carries up to %d observed neighbours (kPolMaxOthers), the network observes %d: "
                              "train with A3CTrainer (autograd)" % (MAX_OTHERS, net.max_others))
         self.net = net
@@ -167,6 +184,9 @@ class FusedA3CTrainer(object):
         self.device = self.policy.device
         self._buffers = {}
         H, A = net.HIDDEN, net.num_actions
+        if self.ws:
+            self.policy.refresh(with_backward=True)
+            return
         # packed gate column k = 64w + 16 gate + u  <->  checkpoint column c = 64 gate + 16w + u
         c = torch.arange(4 * H, device=self.device)
         gate, w, u = c // H, (c % H) // 16, c % 16
@@ -183,6 +203,19 @@ class FusedA3CTrainer(object):
 
     def _scratch(self, rows64: int):
         b = self._buffers.get(rows64)
+        if b is None and self.ws:
+            M, dev = self.net.max_others, self.device
+            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+            t = {"z1": f(rows64, 256), "z2": f(rows64, 256), "z3": f(rows64, 256), "l1_in": f(rows64, 4 + 64 * M), "f_in": f(M, rows64, 8),
+                 "gh": f(rows64, 16), "loss": f(2), "g1": f(rows64, 256), "g2": f(rows64, 256), "g3": f(rows64, 256),
+                 "gf": f(M, rows64, 64), "db": f(1040)}
+            c = _lib.CavoidPolicyTrainWsBuffers()
+            c.struct_size, c.capacity_rows = C.sizeof(_lib.CavoidPolicyTrainWsBuffers), rows64
+            for k, v in t.items():
+                setattr(c, k, C.c_void_p(v.data_ptr()))
+            b = self._buffers[rows64] = (t, c)
+            if len(self._buffers) > 4:
+                self._buffers.pop(next(iter(self._buffers)))
         if b is None:
             M, dev = self.net.max_others, self.device
             f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -227,6 +260,8 @@ class FusedA3CTrainer(object):
         rows64 = (n + 2047) // 2048 * 2048 if n >= 2048 else (n + 63) // 64 * 64
         t, cbuf = self._scratch(rows64)
         ptr = lambda v: C.c_void_p(v.data_ptr())
+        if self.ws:
+            return self._train_ws(x, y_r, a_idx, n, rows64, t, cbuf)
         _lib.check(pol._lib.cavoid_policy_train(pol._h, ptr(x), n, x.stride(0), ptr(y_r), ptr(a_idx), float(net.beta),
                                                 float(net.log_epsilon), C.byref(cbuf), pol._stream()), "cavoid_policy_train")
         A, H, M = net.num_actions, net.HIDDEN, net.max_others
@@ -251,4 +286,30 @@ class FusedA3CTrainer(object):
         self._base.training_step += 1
         self._base.frame_counter += n
         pol.refresh(with_backward=True)                    # actors and the next training pass see the new weights
+        return loss
+
+    def _train_ws(self, x, y_r, a_idx, n, rows64, t, cbuf) -> torch.Tensor:
+        """The weight-sharing network's step: cavoid_policy_train_ws, then the weight-gradient GEMMs it leaves the operands of."""
+        net, pol = self.net, self.policy
+        ptr = lambda v: C.c_void_p(v.data_ptr())
+        _lib.check(pol._lib.cavoid_policy_train_ws(pol._h, ptr(x), n, x.stride(0), ptr(y_r), ptr(a_idx), float(net.beta),
+                                                   float(net.log_epsilon), C.byref(cbuf), pol._stream()), "cavoid_policy_train_ws")
+        A, M = net.num_actions, net.max_others
+        xtg = self._xtg
+        d_head = xtg(t["z3"], t["gh"])
+        net.p_kernel.grad, net.v_kernel.grad = d_head[:, :A].contiguous(), d_head[:, A:A + 1].contiguous()
+        db = t["db"]                                       # packed bias order: other_bias 64 (of 256) | layer1 | layer2 | fc1 | heads 16
+        loss = t["loss"].sum()
+        net.p_bias.grad, net.v_bias.grad = db[1024:1024 + A], db[1024 + A:1025 + A]
+        net.fc1_kernel.grad, net.fc1_bias.grad = xtg(t["z2"], t["g3"]), db[768:1024]
+        net.layer2_kernel.grad, net.layer2_bias.grad = xtg(t["z1"], t["g2"]), db[512:768]
+        net.layer1_kernel.grad, net.layer1_bias.grad = xtg(t["l1_in"], t["g1"]), db[256:512]     # rows: host 4, then slot-major
+        net.other_kernel.grad = xtg(t["f_in"].view(M * rows64, 8), t["gf"].view(M * rows64, 64))  # one GEMM over every slot's rows
+        net.other_bias.grad = db[:64]
+        if self._base.distributed:
+            self._base._allreduce_grads()
+        self.opt.step()
+        self._base.training_step += 1
+        self._base.frame_counter += n
+        pol.refresh(with_backward=True)
         return loss

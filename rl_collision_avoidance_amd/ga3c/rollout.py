@@ -218,6 +218,9 @@ class BatchedRollout(object):
         if not getattr(self.policy, "accepts_strided_obs", False):
             return "the policy is not a FusedPolicy"
         for who, pol in (("policy", self.policy), ("frozen policy", self.frozen_policy)):
+            if getattr(pol, "arch", "rnn") != "rnn":
+                return "the %s is the %s network (the fused actor kernel embeds the LSTM pass; its kernel acts step by step)" % (who, pol.arch)
+        for who, pol in (("policy", self.policy), ("frozen policy", self.frozen_policy)):
             if getattr(pol, "max_others", 0) > POLICY_MAX_OTHERS:
                 return "the %s observes %d neighbours (the fused actor kernel carries up to %d; the crowd policy kernel acts step by step)" % (
                     who, pol.max_others, POLICY_MAX_OTHERS)
