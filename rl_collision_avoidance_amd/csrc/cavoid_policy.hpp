@@ -696,6 +696,7 @@ struct PolicyBackArgs {
     float *g1, *g2, *g3;               // [rows64, 256]
     float *gl;                         // [M, rows64, 256], gate columns in packed order (64w + 16 gate + u)
     float *db;                         // [kBiasFloats] bias gradients, accumulated with atomics (packed bias order)
+    float *h_in;                       // [M, rows64, 72] the forward pass's: zeroed here for the steps no row of a tile took
 };
 
 // g = acc where the layer's relu was active, else 0 -> LDS (the next GEMM's A operand) and global memory
@@ -824,6 +825,10 @@ __global__ void __launch_bounds__(256, 2) policy_backward_kernel(const PolicyBac
         float *glt = p.gl + ((int64_t)t * p.rows64 + row0) * kPolWidth;
         if (t >= steps) {                                  // no row of this tile took step t
             for (int e = tid; e < kRows * kPolWidth; e += 256) glt[e] = 0.0f;
+            // ... so the forward pass left h_in[t] of this tile as the caller allocated it, and d lstm = sum_t h_in[t]^T gl[t] runs
+            // over it: 0 x NaN is NaN, whatever the bytes were
+            float *hit = p.h_in + ((int64_t)t * p.rows64 + row0) * 72;
+            for (int e = tid; e < kRows * 72; e += 256) hit[e] = 0.0f;
             continue;
         }
         policy_load_b(n0, p.frags + kOffTLstm, wave, lane, 0);

@@ -243,7 +243,7 @@ extern "C" int cavoid_policy_train(cavoid_policy *h, const float *x, int64_t row
     HIP_TRY(hipGetLastError());
     PolicyBackArgs k{};
     k.x = x; k.rows = rows; k.stride = row_stride; k.rows64 = cap; k.max_other = h->max_other; k.frags = h->frags;
-    k.z1 = b->z1; k.z2 = b->z2; k.z3 = b->z3; k.save = b->save; k.gh = b->gh; k.g1 = b->g1; k.g2 = b->g2; k.g3 = b->g3; k.gl = b->gl; k.db = b->db;
+    k.z1 = b->z1; k.z2 = b->z2; k.z3 = b->z3; k.save = b->save; k.gh = b->gh; k.g1 = b->g1; k.g2 = b->g2; k.g3 = b->g3; k.gl = b->gl; k.db = b->db; k.h_in = b->h_in;
     hipLaunchKernelGGL((policy_backward_kernel<4>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, k);
     HIP_TRY(hipGetLastError());
     return CAVOID_OK;

@@ -1,0 +1,286 @@
+"""Shared helpers of the tests that take the fused loss heads and the action draw out of the one regime every other test runs in
+(freshly initialised weights: a nearly uniform softmax, no probability anywhere near LOG_EPSILON, beta = 1e-4).  A plain module:
+tests/test_gpu_policy_loss_heads.py (GPU) and tests/test_policy_regimes_host.py (CPU) build the SAME cases from it, so that what the
+host test asserts about a case -- both sides of the log clamp are populated, few rows sit on the threshold, a wrong epilogue would move
+the gradients -- holds for the batch the kernels are run on.
+
+The regimes:
+  beta       default weights, beta in {0, 3e-3, 1}: at the default 1e-4 the entropy term is below the tolerances;
+  wide       LOG_EPSILON = 0.08 at default weights (p = 0.02 .. 0.3): the clamp cuts through every row, so `lp + 1` vs `lp` and
+             `sel > eps` take both sides;
+  confident  the p head scaled by 40 (logit spread ~100): most probabilities are far below LOG_EPSILON = 1e-6, as in a trained policy.
+"""
+import collections
+import copy
+from unittest import mock
+
+import torch
+
+GAIN_TRAINER = 40.0        # p down to 1e-35 .. 1e-48: nothing underflows in float32
+GAIN_DRAW = 150.0          # over half of the float32 probabilities are exactly 0
+GAIN_ACTOR = 1000.0        # tests/test_gpu_actor._make's networks have zero biases: the same effect needs a larger gain
+WIDE_EPS = 0.08
+BAND = 1e-3                # |p / eps - 1| <= BAND: the row may take the other clamp branch in float32
+RELU_BAND = 1e-5           # |pre-activation| <= RELU_BAND: the row may take the other side of a relu in float32 (clear_of_relu_kinks)
+MAX_EXCLUDED = 0.08        # conditions, not measurements: see assert_conditions
+MIN_SIDE = 0.10
+CANDIDATES = 1.25          # candidate rows drawn per kept row
+
+ARCH_M = (("rnn", 3), ("rnn", 9), ("weight_sharing", 3), ("weight_sharing", 7))
+
+
+def build_net(arch, M, seed=0, min_policy=0.0, A=11, normalize=True):
+    """tests/test_gpu_policy._net / tests/test_gpu_policy_ws._ws_net (same generators, hence the same weights), left on the CPU"""
+    from rl_collision_avoidance_amd.config import EnvConfig
+    from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
+
+    class Cfg(EnvConfig):
+        def __init__(self):
+            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = M + 1
+            EnvConfig.__init__(self)
+    cfg = Cfg()
+    cfg.MIN_POLICY = min_policy
+    cfg.NORMALIZE_INPUT = normalize
+    net = NetworkVP_rnn(cfg, num_actions=A, seed=seed, arch=arch)
+    g = torch.Generator().manual_seed(seed + 100)
+    with torch.no_grad():
+        for name, prm in net.named_parameters():
+            if name.endswith("_bias"):
+                prm.copy_(torch.rand(prm.shape, generator=g) - 0.5)
+    return net
+
+
+def inputs(net, B, seed, scale=1.0):
+    """tests/test_gpu_policy._inputs on the network's own device"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((B, net.input_size), generator=g) * scale * net.std.cpu() + net.avg.cpu()
+    x[:, 0] = torch.randint(0, net.max_others + 1, (B,), generator=g).to(torch.float32)
+    return x.to(net.avg.device)
+
+
+def confident(net, gain):
+    """a trained policy's head: the logits' spread times `gain`, in place"""
+    with torch.no_grad():
+        net.p_kernel.mul_(gain)
+        net.p_bias.mul_(gain)
+    return net
+
+
+def forward64(net, x):
+    """(p, v) of the same network evaluated in float64"""
+    with torch.no_grad():
+        _, p, v = copy.deepcopy(net).double().forward(x.double())
+    return p, v
+
+
+def clear_of_threshold(net, x, eps, rel=BAND):
+    """mask of the rows in which NO p_j lies within |p_j / eps - 1| <= rel (float64 network).  A row inside that band may
+    legitimately take the other clamp branch in float32, and one such row changes a batch-summed gradient by far more than rounding."""
+    p, _ = forward64(net, x)
+    return ~((p / eps - 1.0).abs() <= rel).any(dim=1)
+
+
+def relu_inputs64(net, x):
+    """every relu pre-activation of the float64 network, [B, units]"""
+    seen, relu = [], torch.relu
+
+    def spy(t):
+        seen.append(t.detach())
+        return relu(t)
+    with mock.patch.object(torch, "relu", spy), torch.no_grad():
+        copy.deepcopy(net).double().forward(x.double())
+    return torch.cat([t.reshape(x.shape[0], -1) for t in seen], dim=1)
+
+
+def clear_of_relu_kinks(net, x, band=RELU_BAND):
+    """mask of the rows in which no relu pre-activation (float64 network) lies within `band` of 0.  Such a unit may sit on the other
+    side of 0 in float32 -- float32 and float64 then take different sub-gradients, and ONE unit's contribution to every weight
+    gradient below it flips: the fused trainer did that to one unit of 10 M at weight_sharing M = 7, B = 8192 (pre-activation 2.0e-7
+    in float64; its activations are within 1.6e-6 of float64's everywhere), PyTorch's float32 autograd does it at B = 1000.  That is
+    float32, not the epilogue, and far more than rounding in a 512-entry gradient such as other_kernel's.  A pre-activation is a
+    float32 dot product of up to 452 terms of order 1: rounding of the order of 1e-6; the band is ten times that."""
+    return ~(relu_inputs64(net, x).abs() <= band).any(dim=1)
+
+
+# ---- the networks of the inference and action-draw tests: (arch, M), all with this seed (the p head's spread depends on it: with
+#      seed 43 only 10 % of the probabilities are 0 at gain 150; the conditions pick the seed, see confident_shares) -----------------
+FORM_SEED = 40
+FORM_NETS = {"default": ("rnn", 3), "f32": ("rnn", 3), "crowd": ("rnn", 31), "weight_sharing": ("weight_sharing", 7)}
+ACCURACY_ROWS, DRAW_ROWS = 4096, 32768
+
+
+def form_net(form, gain):
+    arch, M = FORM_NETS[form]
+    return confident(build_net(arch, M, seed=FORM_SEED), gain)
+
+
+def confident_shares(form):
+    """(share of the float64 probabilities <= 1e-6 and share >= 1e-30 on the accuracy test's rows at GAIN_TRAINER, share of PyTorch's
+    float32 probabilities that are exactly 0 on the draw test's rows at GAIN_DRAW)"""
+    net = form_net(form, GAIN_TRAINER)
+    p64, _ = forward64(net, inputs(net, ACCURACY_ROWS, seed=7))
+    net = form_net(form, GAIN_DRAW)
+    with torch.no_grad():
+        _, p32, _ = net.forward(inputs(net, DRAW_ROWS, seed=8))
+    return (p64 <= 1e-6).float().mean().item(), (p64 >= 1e-30).float().mean().item(), (p32 == 0.0).float().mean().item()
+
+
+# ---- the trainer cases ------------------------------------------------------------------------------------------------------
+Case = collections.namedtuple("Case", "regime arch M B beta log_eps min_policy gain y_near_v A")
+
+
+def _case(regime, arch, M, B, beta, log_eps=1e-6, min_policy=0.0, gain=0.0, y_near_v=False, A=11):
+    return Case(regime, arch, M, B, beta, log_eps, min_policy, gain, y_near_v, A)
+
+
+def case_id(c):
+    return "%s-%s%d-B%d-beta%g-eps%g-minp%g%s%s" % (c.regime, "ws" if c.arch == "weight_sharing" else "rnn", c.M, c.B, c.beta, c.log_eps,
+                                                   c.min_policy, "-ynearv" if c.y_near_v else "", "-A%d" % c.A if c.A != 11 else "")
+
+
+def _cases():
+    out = []
+    for arch, M in ARCH_M:
+        for beta in (0.0, 3e-3, 1.0):
+            for B in (1000, 8192):
+                out.append(_case("beta", arch, M, B, beta))
+        out.append(_case("beta", arch, M, 1000, 1.0, y_near_v=True))     # the entropy gradient is the whole gradient at the policy head
+        for beta in (1e-4, 1.0):
+            for min_policy in (0.0, 0.02):
+                out.append(_case("wide", arch, M, 1000, beta, log_eps=WIDE_EPS, min_policy=min_policy))
+            # MIN_POLICY = 1e-3: nothing is clamped, but most probabilities sit at the floor (the `* scale` path of dp)
+            for min_policy in (0.0, 1e-3):
+                out.append(_case("confident", arch, M, 1000, beta, min_policy=min_policy, gain=GAIN_TRAINER))
+    for arch, M in (("rnn", 3), ("weight_sharing", 7)):                   # one large batch per arch and clamp regime
+        out.append(_case("wide", arch, M, 8192, 1.0, log_eps=WIDE_EPS))
+        out.append(_case("confident", arch, M, 8192, 1.0, gain=GAIN_TRAINER))
+    return out
+
+
+TRAINER_CASES = _cases()
+# the weight-sharing trainer's own copy of the epilogue with MIN_POLICY > 0 (the LSTM trainer's test has such a case) ...
+WS_MIN_POLICY_CASES = [_case("beta", "weight_sharing", M, 1000, 1e-4, min_policy=1e-3) for M in (3, 7)]
+# ... and one trainer, two calls, beta = 0 then beta = 1
+BETA_SWITCH_CASES = [_case("beta", arch, M, 1000, 0.0) for arch, M in ARCH_M]
+ALL_CASES = TRAINER_CASES + WS_MIN_POLICY_CASES + BETA_SWITCH_CASES
+
+
+def clamps(case):
+    """the regimes in which the log clamp is meant to cut through the batch"""
+    return case.regime == "wide" or (case.regime == "confident" and case.min_policy == 0.0)
+
+
+def build_case(case, device="cpu"):
+    """(net, x [B], y [B], a [B], info): the network in its regime and the first B rows clear of the clamp threshold and of the relu
+    kinks among 1.25 B candidates, with their targets and actions.  Everything is drawn on the CPU, so every device sees the same batch."""
+    net = build_net(case.arch, case.M, seed=20 + case.M, min_policy=case.min_policy, A=case.A)
+    if case.gain:
+        confident(net, case.gain)
+    net.beta, net.log_epsilon = float(case.beta), float(case.log_eps)
+    n = int(CANDIDATES * case.B)
+    x = inputs(net, n, seed=case.B + 1)
+    g = torch.Generator().manual_seed(case.B)
+    y = torch.randn(n, generator=g)
+    a = torch.randint(0, case.A, (n,), generator=g)
+    clear = clear_of_threshold(net, x, case.log_eps) & clear_of_relu_kinks(net, x)
+    keep = torch.nonzero(clear).flatten()[:case.B]
+    x, y, a = x[keep], y[keep], a[keep]
+    p, v = forward64(net, x)
+    if case.y_near_v:
+        y = (v + 0.01 * torch.randn(keep.numel(), generator=g).double()).float()
+    sel = p.gather(1, a.unsqueeze(1)).squeeze(1)
+    info = {"rows": int(keep.numel()), "excluded": 1.0 - clear.float().mean().item(),
+            "below": (p <= case.log_eps).float().mean().item(), "below_selected": (sel <= case.log_eps).float().mean().item(),
+            "p_min": p.min().item()}
+    return net.to(device), x.to(device), y.to(device), a.to(device), info
+
+
+def assert_conditions(case, info):
+    """Conditions on a case's batch, fixed before any kernel ran: enough clear rows, the bands exclude at most 8 % of the candidates,
+    and -- where the clamp is the point -- at least 10 % of all probabilities and of the selected probabilities on EACH side of eps.
+    If a seed misses one, another seed is picked; the condition stays."""
+    assert info["rows"] == case.B, (case, info)
+    assert info["excluded"] <= MAX_EXCLUDED, (case, info)
+    if clamps(case):
+        for key in ("below", "below_selected"):
+            assert MIN_SIDE <= info[key] <= 1.0 - MIN_SIDE, (case, key, info)
+    else:
+        assert info["below"] == 0.0 and info["below_selected"] == 0.0, (case, info)
+
+
+# ---- the gradient criterion of test_fused_trainer_gradients_match_autograd (the one copy) -------------------------------------
+def assert_gradients_match(net, want, torch32, B, report=None):
+    """net's .grad (the fused trainer's) against the float64 gradients `want`, as close as PyTorch's own float32 autograd
+    (`torch32`) is (x3), or 1e-4 of the gradient's largest entry."""
+    for k, v in net.named_parameters():
+        ref = want[k]
+        assert v.grad is not None and v.grad.shape == ref.shape, k
+        assert torch.isfinite(v.grad).all(), k                 # (a NaN compares false with every bound below)
+        scale = ref.abs().max().item() + 1e-6
+        err = (v.grad.double() - ref).abs().max().item()
+        err32 = (torch32[k].double() - ref).abs().max().item()
+        if report is not None:
+            report.append((k, err, err32, scale))
+        # as close to the float64 gradient as PyTorch's own float32 autograd is (x3), or 1e-4 of the largest entry ...
+        tight = max(3.0 * err32, 1e-4 * scale)
+        if err > tight:
+            # ... except for the gradient paths behind a relu whose pre-activation is 0 to float32 rounding: among
+            # 25 M units (B = 32768) a handful sit there, float32 and float64 then take different sub-gradients, and
+            # one unit's contribution to the weight gradients flips.  The heads never see that.
+            assert B >= 8192 and not k.startswith(("p_", "v_")), (k, err, err32, scale)
+            bad = ((v.grad.double() - ref).abs() > tight).float().mean().item()
+            assert err <= 5e-3 * scale and bad <= 5e-3, (k, err, bad, scale)
+
+
+def assert_loss_matches(loss, total):
+    assert abs(loss - total) <= 2e-4 * max(1.0, abs(total)), (loss, total)
+
+
+def reference_gradients(net, x, y, a):
+    """float64 autograd of NetworkVP_rnn.loss (the yardstick) and PyTorch's float32 autograd on the same rows:
+    (total64, cost_p64, cost_v64, {name: grad64}, {name: grad32})"""
+    onehot = torch.nn.functional.one_hot(a.long(), net.num_actions)
+    ref_net = copy.deepcopy(net).double()
+    ref_net.zero_grad()
+    total, cost_p, cost_v = ref_net.loss(x.double(), y.double(), onehot.double())
+    total.backward()
+    want = {k: v.grad.clone() for k, v in ref_net.named_parameters()}
+    net.zero_grad()
+    net.loss(x, y, onehot.float())[0].backward()
+    torch32 = {k: v.grad.clone() for k, v in net.named_parameters()}
+    net.zero_grad()
+    return float(total.detach()), float(cost_p.detach()), float(cost_v.detach()), want, torch32
+
+
+# ---- what a wrong epilogue would do (float64, CPU): the loss with the trainer kernels' d cost / d p written out -----------------
+MUTATIONS = ("entropy_ignores_clamp", "policy_ignores_clamp", "no_entropy_gradient")
+
+
+def epilogue_gradients(net, x, y, a, mutation=None):
+    """{name: float64 gradient} of the loss whose gradient at p is the trainer epilogue's own formula
+        dp_j = beta * (p_j > eps ? lp_j + 1 : lp_j)  -  [j == a and p_a > eps] (y - v) / p_a,     lp = log(max(p, eps)),
+    with one of MUTATIONS applied, or none: then these are the gradients of NetworkVP_rnn.loss."""
+    assert mutation is None or mutation in MUTATIONS
+    net64 = copy.deepcopy(net).double()
+    net64.zero_grad()
+    eps, beta = net64.log_epsilon, net64.beta
+    onehot = torch.nn.functional.one_hot(a.long(), net64.num_actions).double()
+    _, p, v = net64.forward(x.double())
+    adv = y.double() - v.detach()
+    sel = (p * onehot).sum(dim=1)
+    lp = torch.log(torch.clamp_min(p, eps))
+    d_ent = beta * torch.where(p > eps, lp + 1.0, lp)
+    if mutation == "entropy_ignores_clamp":
+        d_ent = beta * (lp + 1.0)
+    elif mutation == "no_entropy_gradient":
+        d_ent = torch.zeros_like(lp)
+    live = torch.ones_like(sel) if mutation == "policy_ignores_clamp" else (sel > eps).double()
+    d_pol = -onehot * (live * adv / sel).unsqueeze(1)
+    surrogate = (p * (d_ent + d_pol).detach()).sum() + 0.5 * torch.sum((y.double() - v) ** 2)
+    surrogate.backward()
+    return {k: t.grad.clone() for k, t in net64.named_parameters()}
+
+
+def largest_move(got, want):
+    """max over the parameters of |got - want| / (largest entry of want)"""
+    return max((got[k] - want[k]).abs().max().item() / (want[k].abs().max().item() + 1e-6) for k in want)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle.cavoid_oracle import philox4x32
+from tests.policy_regimes import assert_gradients_match
 from tests.test_gpu_parity import _env
 from tests.test_gpu_policy import P_TOL, V_TOL, _inputs
 
@@ -225,17 +226,7 @@ def test_ws_fused_trainer_gradients_match_autograd(M, B):
     loss = float(tr.train(x, y, a))
     assert abs(loss - float(total.detach())) <= 2e-4 * max(1.0, abs(float(total.detach())))
     assert set(want) == {k for k, _ in net.named_parameters()} and "other_kernel" in want
-    for k, v in net.named_parameters():
-        ref = want[k]
-        assert v.grad is not None and v.grad.shape == ref.shape, k
-        scale = ref.abs().max().item() + 1e-6
-        err = (v.grad.double() - ref).abs().max().item()
-        err32 = (torch32[k].double() - ref).abs().max().item()
-        tight = max(3.0 * err32, 1e-4 * scale)
-        if err > tight:
-            assert B >= 8192 and not k.startswith(("p_", "v_")), (k, err, err32, scale)
-            bad = ((v.grad.double() - ref).abs() > tight).float().mean().item()
-            assert err <= 5e-3 * scale and bad <= 5e-3, (k, err, bad, scale)
+    assert_gradients_match(net, want, torch32, B)          # (tests/policy_regimes.py: the one copy of the criterion)
 
 
 def test_ws_fused_trainer_learns_like_the_autograd_trainer():
