@@ -537,6 +537,23 @@ int cavoid_policy_load_ws(cavoid_policy *p, const cavoid_policy_weights *w, cons
 int cavoid_policy_train_ws(cavoid_policy *p, const float *x, int64_t rows, int64_t row_stride, const float *y_r, const int32_t *a_idx,
                            float beta, float log_epsilon, const cavoid_policy_train_ws_buffers *buffers, void *stream);
 
+/* ---- the supervised start's trainer pass (train_regression_op on cost_regression, ga3c/GA3C/NetworkVPCore.py:90-100,123; the
+ * phase Regression.py runs for TRAIN_ONLY_REGRESSION and LOAD_REGRESSION_THEN_TRAIN_RL) ------------------------------------------
+ * cavoid_policy_train / cavoid_policy_train_ws with the other loss head, everything else the same: the same two launches, buffer
+ * structs, preconditions (with_backward = 1, max_other <= 19, capacity_rows), caller's GEMMs, db layout and error codes -- the LSTM
+ * call on a weight-sharing handle and the _ws call on an LSTM handle are CAVOID_EINVAL.  Per row, with z the A policy logits, v the
+ * value logit, a_idx the TEACHER's action and y_r the value target:
+ *   cost_p_regression = log sum_k exp(z_k) - z_a   (softmax cross-entropy on the logits, evaluated as log-sum-exp: finite and exact
+ *                                                   where float32 softmax entries are 0),   cost_v = 0.5 (y_r - v)^2,
+ *   gh[:, k] = softmax(z)_k - [k == a] for k < A,  gh[:, A] = v - y_r,  0 in the padding columns and in rows past `rows`.
+ * MIN_POLICY, beta and LOG_EPSILON play no part (the reference takes logits_p, not softmax_p).  loss[0] = cost_p_regression,
+ * loss[1] = cost_v, sums over rows.  Precondition, as for cavoid_policy_train / _train_ws: 0 <= a_idx[i] < num_actions for every
+ * row; the kernels do not check it (an index outside the range selects another head column of the row). */
+int cavoid_policy_train_regression(cavoid_policy *p, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
+                                   const int32_t *a_idx, const cavoid_policy_train_buffers *buffers, void *stream);
+int cavoid_policy_train_regression_ws(cavoid_policy *p, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
+                                      const int32_t *a_idx, const cavoid_policy_train_ws_buffers *buffers, void *stream);
+
 /* kernel timing helper: HIP events recorded on `stream` around the launches of the calls made
  * between begin and end; end synchronises and returns elapsed milliseconds */
 int cavoid_timer_begin(cavoid_env *env, void *stream);

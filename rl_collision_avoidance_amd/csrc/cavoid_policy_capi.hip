@@ -64,6 +64,8 @@ extern "C" int cavoid_policy_create(int32_t max_other, int32_t num_actions, int 
                             (int)policy_lds_bytes(4)) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)policy_lds_bytes(4)) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_regression_forward_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)policy_lds_bytes(4)) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(policy_backward_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)policy_lds_bytes(4)) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -214,9 +216,9 @@ extern "C" int cavoid_policy_forward_rows(cavoid_policy *h, const float *x, int6
     return policy_forward(h, x, rows, row_stride, row_index, row_count, p_out, v_out, actions_out, greedy, stream);
 }
 
-extern "C" int cavoid_policy_train(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
-                                   const int32_t *a_idx, float beta, float log_epsilon, const cavoid_policy_train_buffers *b,
-                                   void *stream) {
+// the trainer pass with either loss head (kLossA3C: cavoid_policy_train; kLossRegression: cavoid_policy_train_regression)
+static int policy_train(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const float *y_r, const int32_t *a_idx,
+                        float beta, float log_epsilon, const cavoid_policy_train_buffers *b, void *stream, int loss_kind) {
     if (!h || !x || !y_r || !a_idx || !b || b->struct_size != (int32_t)sizeof(cavoid_policy_train_buffers)) return CAVOID_EINVAL;
     if (h->ws) return CAVOID_EINVAL;                       // (a weight-sharing handle trains with cavoid_policy_train_ws)
     if (h->crowd) return CAVOID_EUNSUPPORTED;              // (the trainer pass parks the whole row: kPolMaxOthers)
@@ -239,7 +241,8 @@ extern "C" int cavoid_policy_train(cavoid_policy *h, const float *x, int64_t row
     // every tile of the buffers is processed (tiles past `rows` carry zero gradients), so that the caller can run its
     // weight-gradient GEMMs over a convenient row count without ever reading stale rows
     const unsigned blocks = (unsigned)(cap / 64);
-    hipLaunchKernelGGL((policy_forward_kernel<4, true>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, a);
+    if (loss_kind == kLossRegression) hipLaunchKernelGGL(policy_regression_forward_kernel<4>, dim3(blocks), dim3(256), policy_lds_bytes(4), s, a);
+    else hipLaunchKernelGGL((policy_forward_kernel<4, true>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, a);
     HIP_TRY(hipGetLastError());
     PolicyBackArgs k{};
     k.x = x; k.rows = rows; k.stride = row_stride; k.rows64 = cap; k.max_other = h->max_other; k.frags = h->frags;
@@ -247,6 +250,17 @@ extern "C" int cavoid_policy_train(cavoid_policy *h, const float *x, int64_t row
     hipLaunchKernelGGL((policy_backward_kernel<4>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, k);
     HIP_TRY(hipGetLastError());
     return CAVOID_OK;
+}
+
+extern "C" int cavoid_policy_train(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
+                                   const int32_t *a_idx, float beta, float log_epsilon, const cavoid_policy_train_buffers *b,
+                                   void *stream) {
+    return policy_train(h, x, rows, row_stride, y_r, a_idx, beta, log_epsilon, b, stream, kLossA3C);
+}
+
+extern "C" int cavoid_policy_train_regression(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
+                                              const int32_t *a_idx, const cavoid_policy_train_buffers *b, void *stream) {
+    return policy_train(h, x, rows, row_stride, y_r, a_idx, 0.0f, 0.0f, b, stream, kLossRegression);
 }
 
 #ifdef CAVOID_TRACE

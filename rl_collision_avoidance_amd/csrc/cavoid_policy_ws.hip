@@ -45,6 +45,8 @@ extern "C" int cavoid_policy_create_ws(int32_t max_other, int32_t num_actions, i
                             (int)policy_lds_bytes(4)) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(policy_ws_forward_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)policy_lds_bytes(4)) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_regression_ws_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)policy_lds_bytes(4)) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(policy_ws_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)policy_lds_bytes(4)) != hipSuccess) {
         g_last_hip_error = (int)hipGetLastError(); (void)hipFree(h->slab); delete h; return CAVOID_EHIP;
@@ -90,9 +92,9 @@ int cavoid_policy_ws_launch(cavoid_policy *h, const PolicyArgs &a, int64_t block
     return CAVOID_OK;
 }
 
-extern "C" int cavoid_policy_train_ws(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
-                                      const int32_t *a_idx, float beta, float log_epsilon, const cavoid_policy_train_ws_buffers *b,
-                                      void *stream) {
+// the trainer pass with either loss head (kLossA3C: cavoid_policy_train_ws; kLossRegression: cavoid_policy_train_regression_ws)
+static int policy_train_ws(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const float *y_r, const int32_t *a_idx,
+                           float beta, float log_epsilon, const cavoid_policy_train_ws_buffers *b, void *stream, int loss_kind) {
     if (!h || !x || !y_r || !a_idx || !b || b->struct_size != (int32_t)sizeof(cavoid_policy_train_ws_buffers) || !h->ws) return CAVOID_EINVAL;
     if (!h->loaded || !h->backward_loaded || rows < 0 || row_stride < h->in_size) return CAVOID_EINVAL;
     const int64_t rows64 = (rows + 63) / 64 * 64;
@@ -115,7 +117,8 @@ extern "C" int cavoid_policy_train_ws(cavoid_policy *h, const float *x, int64_t 
     wa.f_in = b->f_in;
     // every tile of the buffers (tiles past `rows` carry zero gradients): the caller's GEMMs may run over all capacity_rows
     const unsigned blocks = (unsigned)(cap / 64);
-    hipLaunchKernelGGL((policy_ws_forward_kernel<true>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, wa);
+    if (loss_kind == kLossRegression) hipLaunchKernelGGL(policy_regression_ws_forward_kernel, dim3(blocks), dim3(256), policy_lds_bytes(4), s, wa);
+    else hipLaunchKernelGGL((policy_ws_forward_kernel<true>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, wa);
     HIP_TRY(hipGetLastError());
     PolicyWsBackArgs k{};
     k.rows64 = cap; k.max_other = h->max_other; k.frags = h->frags;
@@ -123,4 +126,15 @@ extern "C" int cavoid_policy_train_ws(cavoid_policy *h, const float *x, int64_t 
     hipLaunchKernelGGL(policy_ws_backward_kernel, dim3(blocks), dim3(256), policy_lds_bytes(4), s, k);
     HIP_TRY(hipGetLastError());
     return CAVOID_OK;
+}
+
+extern "C" int cavoid_policy_train_ws(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
+                                      const int32_t *a_idx, float beta, float log_epsilon, const cavoid_policy_train_ws_buffers *b,
+                                      void *stream) {
+    return policy_train_ws(h, x, rows, row_stride, y_r, a_idx, beta, log_epsilon, b, stream, kLossA3C);
+}
+
+extern "C" int cavoid_policy_train_regression_ws(cavoid_policy *h, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
+                                                 const int32_t *a_idx, const cavoid_policy_train_ws_buffers *b, void *stream) {
+    return policy_train_ws(h, x, rows, row_stride, y_r, a_idx, 0.0f, 0.0f, b, stream, kLossRegression);
 }

@@ -168,7 +168,8 @@ class FusedA3CTrainer(object):
     (NetworkVPCore.py:71-100) and the row-local half of the backward pass as two MFMA kernel launches
     (``cavoid_policy_train``); the weight gradients are the library GEMMs ``X^T G`` over all rows (split-K batched), the
     optimiser is the same fused Adam as ``A3CTrainer``.  Gradients equal PyTorch autograd's on ``NetworkVP_rnn.loss`` to
-    float32 rounding (tests/test_gpu_policy.py)."""
+    float32 rounding (tests/test_gpu_policy.py).  ``train_regression`` is the supervised start's step on the same pair with the
+    regression loss head (``cavoid_policy_train_regression``; tests/test_gpu_policy_regression.py)."""
 
     def __init__(self, net: NetworkVP_rnn, policy: Optional[FusedPolicy] = None, learning_rate: float = 2e-5, group=None,
                  distributed: Optional[bool] = None):
@@ -240,6 +241,42 @@ class FusedA3CTrainer(object):
             return x.t() @ g
         return torch.bmm(x.view(S, R // S, -1).transpose(1, 2), g.view(S, R // S, -1)).sum(dim=0)
 
+    def _pass(self, x: torch.Tensor, y_r: torch.Tensor, a_idx: torch.Tensor, n: int, regression: bool = False):
+        """The launch pair on n > 0 rows -- forward + loss head (A3C, or ``regression``: cost_regression) + the row-local backward --
+        then the weight-gradient GEMMs it leaves the operands of: every parameter's ``.grad`` is set.  Returns the scratch tensors
+        (``loss`` = [cost_p, cost_v], sums over the rows).  x: float32 rows of stride >= input_size."""
+        net, pol = self.net, self.policy
+        # buffer rows: a multiple of 2048 (the split-K slice of the weight-gradient GEMMs) once the batch is that large;
+        # the kernels write every buffer row, rows past n with zero gradients
+        rows64 = (n + 2047) // 2048 * 2048 if n >= 2048 else (n + 63) // 64 * 64
+        t, cbuf = self._scratch(rows64)
+        ptr = lambda v: C.c_void_p(v.data_ptr())
+        name = "cavoid_policy_train" + ("_regression" if regression else "") + ("_ws" if self.ws else "")
+        loss_args = () if regression else (float(net.beta), float(net.log_epsilon))
+        _lib.check(getattr(pol._lib, name)(pol._h, ptr(x), n, x.stride(0), ptr(y_r), ptr(a_idx), *loss_args,
+                                           C.byref(cbuf), pol._stream()), name)
+        A, H, M = net.num_actions, net.HIDDEN, net.max_others
+        xtg = self._xtg
+        d_head = xtg(t["z3"], t["gh"])
+        net.p_kernel.grad, net.v_kernel.grad = d_head[:, :A].contiguous(), d_head[:, A:A + 1].contiguous()
+        db = t["db"]                     # packed bias order: lstm 256 (weight_sharing: other_bias 64) | layer1 | layer2 | fc1 | heads 16
+        net.p_bias.grad, net.v_bias.grad = db[1024:1024 + A], db[1024 + A:1025 + A]
+        net.fc1_kernel.grad, net.fc1_bias.grad = xtg(t["z2"], t["g3"]), db[768:1024]
+        net.layer2_kernel.grad, net.layer2_bias.grad = xtg(t["z1"], t["g2"]), db[512:768]
+        d_l1 = xtg(t["l1_in"], t["g1"])
+        net.layer1_bias.grad = db[256:512]
+        if self.ws:
+            net.layer1_kernel.grad = d_l1                                    # rows: host 4, then slot-major (the checkpoint's order)
+            net.other_kernel.grad = xtg(t["f_in"].view(M * rows64, 8), t["gf"].view(M * rows64, 64))  # one GEMM over every slot's rows
+            net.other_bias.grad = db[:64]
+        else:
+            net.layer1_kernel.grad = d_l1.index_select(0, self._l1_rows)     # rows: 64 hidden, 4 host, 4 padding
+            gl = t["gl"].view(M * rows64, 4 * H)
+            d_lstm = xtg(t["h_in"].view(M * rows64, 72), gl)                 # rows: 64 hidden, 7 inputs, 1 padding; packed gate columns
+            net.lstm_kernel.grad = d_lstm.reshape(-1).index_select(0, self._lstm_flat).view(H + net.OTHER, 4 * H)
+            net.lstm_bias.grad = db[:256].index_select(0, self._k_of_c)
+        return t
+
     def train(self, x: torch.Tensor, y_r: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
         """One optimiser step on the batch.  ``a``: action indices [n] or the reference's one-hot float [n, A].
         Returns the loss (cost_p + cost_v) as a 0-d device tensor: nothing here waits for the GPU."""
@@ -255,31 +292,7 @@ class FusedA3CTrainer(object):
         x = x.to(torch.float32).contiguous()
         y_r = y_r.to(torch.float32).contiguous()
         a_idx = (a.argmax(dim=1) if a.dim() == 2 else a).to(torch.int32).contiguous()
-        # buffer rows: a multiple of 2048 (the split-K slice of the weight-gradient GEMMs) once the batch is that large;
-        # the kernels write every buffer row, rows past n with zero gradients
-        rows64 = (n + 2047) // 2048 * 2048 if n >= 2048 else (n + 63) // 64 * 64
-        t, cbuf = self._scratch(rows64)
-        ptr = lambda v: C.c_void_p(v.data_ptr())
-        if self.ws:
-            return self._train_ws(x, y_r, a_idx, n, rows64, t, cbuf)
-        _lib.check(pol._lib.cavoid_policy_train(pol._h, ptr(x), n, x.stride(0), ptr(y_r), ptr(a_idx), float(net.beta),
-                                                float(net.log_epsilon), C.byref(cbuf), pol._stream()), "cavoid_policy_train")
-        A, H, M = net.num_actions, net.HIDDEN, net.max_others
-        xtg = self._xtg
-        d_head = xtg(t["z3"], t["gh"])
-        net.p_kernel.grad, net.v_kernel.grad = d_head[:, :A].contiguous(), d_head[:, A:A + 1].contiguous()
-        db = t["db"]                                       # packed bias order: lstm 256 | layer1 | layer2 | fc1 | heads 16
-        loss = t["loss"].sum()
-        net.p_bias.grad, net.v_bias.grad = db[1024:1024 + A], db[1024 + A:1025 + A]
-        net.fc1_kernel.grad, net.fc1_bias.grad = xtg(t["z2"], t["g3"]), db[768:1024]
-        net.layer2_kernel.grad, net.layer2_bias.grad = xtg(t["z1"], t["g2"]), db[512:768]
-        d_l1 = xtg(t["l1_in"], t["g1"])                                     # rows: 64 hidden, 4 host, 4 padding
-        net.layer1_kernel.grad = d_l1.index_select(0, self._l1_rows)
-        net.layer1_bias.grad = db[256:512]
-        gl = t["gl"].view(M * rows64, 4 * H)
-        d_lstm = xtg(t["h_in"].view(M * rows64, 72), gl)                   # rows: 64 hidden, 7 inputs, 1 padding; packed gate columns
-        net.lstm_kernel.grad = d_lstm.reshape(-1).index_select(0, self._lstm_flat).view(H + net.OTHER, 4 * H)
-        net.lstm_bias.grad = db[:256].index_select(0, self._k_of_c)
+        loss = self._pass(x, y_r, a_idx, n)["loss"].sum()
         if self._base.distributed:
             self._base._allreduce_grads()
         self.opt.step()
@@ -288,28 +301,25 @@ class FusedA3CTrainer(object):
         pol.refresh(with_backward=True)                    # actors and the next training pass see the new weights
         return loss
 
-    def _train_ws(self, x, y_r, a_idx, n, rows64, t, cbuf) -> torch.Tensor:
-        """The weight-sharing network's step: cavoid_policy_train_ws, then the weight-gradient GEMMs it leaves the operands of."""
+    def train_regression(self, x: torch.Tensor, y_r: torch.Tensor, a: torch.Tensor, opt=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One step of the supervised start (``train_regression_op`` on ``cost_regression``, NetworkVPCore.py:90-100,123) on the fused
+        kernels: softmax cross-entropy of the logits with the teacher's action ``a`` (indices [n], or one-hot [n, A]) + cost_v
+        against ``y_r``.  Steps ``opt`` (default: the trainer's own Adam) and re-packs the weights.  Returns (cost_p, cost_v), sums
+        over the rows, as 0-d device tensors: nothing here waits for the GPU.  The regression phase is per rank by design
+        (``regression.pretrain``): no all-reduce, and ``training_step`` / ``frame_counter`` count RL steps only."""
         net, pol = self.net, self.policy
-        ptr = lambda v: C.c_void_p(v.data_ptr())
-        _lib.check(pol._lib.cavoid_policy_train_ws(pol._h, ptr(x), n, x.stride(0), ptr(y_r), ptr(a_idx), float(net.beta),
-                                                   float(net.log_epsilon), C.byref(cbuf), pol._stream()), "cavoid_policy_train_ws")
-        A, M = net.num_actions, net.max_others
-        xtg = self._xtg
-        d_head = xtg(t["z3"], t["gh"])
-        net.p_kernel.grad, net.v_kernel.grad = d_head[:, :A].contiguous(), d_head[:, A:A + 1].contiguous()
-        db = t["db"]                                       # packed bias order: other_bias 64 (of 256) | layer1 | layer2 | fc1 | heads 16
-        loss = t["loss"].sum()
-        net.p_bias.grad, net.v_bias.grad = db[1024:1024 + A], db[1024 + A:1025 + A]
-        net.fc1_kernel.grad, net.fc1_bias.grad = xtg(t["z2"], t["g3"]), db[768:1024]
-        net.layer2_kernel.grad, net.layer2_bias.grad = xtg(t["z1"], t["g2"]), db[512:768]
-        net.layer1_kernel.grad, net.layer1_bias.grad = xtg(t["l1_in"], t["g1"]), db[256:512]     # rows: host 4, then slot-major
-        net.other_kernel.grad = xtg(t["f_in"].view(M * rows64, 8), t["gf"].view(M * rows64, 64))  # one GEMM over every slot's rows
-        net.other_bias.grad = db[:64]
-        if self._base.distributed:
-            self._base._allreduce_grads()
-        self.opt.step()
-        self._base.training_step += 1
-        self._base.frame_counter += n
+        n = int(x.shape[0])
+        if n == 0:
+            zero = torch.zeros((), dtype=torch.float32, device=self.device)
+            return zero, zero.clone()
+        if x.dim() != 2 or x.shape[1] != net.input_size or x.device != self.device:
+            raise ValueError("x must be [n, %d] on %s" % (net.input_size, self.device))
+        x = x.to(torch.float32)
+        if x.stride(1) != 1 or x.stride(0) < net.input_size:                   # (a column slice of wider rows goes in as it is)
+            x = x.reshape(n, -1).clone()
+        y_r = y_r.to(torch.float32).contiguous()
+        a_idx = (a.argmax(dim=1) if a.dim() == 2 else a).to(torch.int32).contiguous()
+        loss = self._pass(x, y_r, a_idx, n, regression=True)["loss"].clone()       # (the scratch is the next pass's)
+        (opt if opt is not None else self.opt).step()
         pol.refresh(with_backward=True)
-        return loss
+        return loss[0], loss[1]

@@ -46,15 +46,21 @@ def regression_loss(net: NetworkVP_rnn, x: torch.Tensor, y_r: torch.Tensor, a_in
 
 
 def pretrain(net: NetworkVP_rnn, env, steps: int = 300, learning_rate: float = 1e-3, discount: float = 0.97,
-             rows_per_step: int = 32768, log_every: int = 0) -> dict:
+             rows_per_step: int = 32768, log_every: int = 0, trainer=None) -> dict:
     """Drive ``env`` with the teacher, regress the network onto (observation -> teacher action, n-step return).
-    Returns the last losses per row and the teacher's mean episode reward."""
+    Returns the last losses per row and the teacher's mean episode reward.  ``trainer``: a ``FusedA3CTrainer`` of ``net`` -- every
+    step then runs on the fused trainer kernels (``train_regression``) with this function's own Adam, and the losses stay on the
+    device until a log line or the end needs them; None: PyTorch autograd."""
     possible = torch.as_tensor(np.asarray(env.actions if hasattr(env, "actions") else _action_table()), dtype=torch.float32,
                                device=env.device)
     roll = BatchedRollout(env, policy=None, discount=discount, reflush_done=False)
     roll.reset()
     opt = torch.optim.Adam(net.parameters(), lr=learning_rate, eps=1e-8)
     zeros = torch.zeros((env.num_worlds, env.max_agents), dtype=torch.float32, device=env.device)
+    if trainer is not None:
+        if trainer.net is not net:
+            raise ValueError("trainer must be the FusedA3CTrainer of the network being regressed")
+        return _pretrain_fused(trainer, roll, opt, possible, zeros, steps, rows_per_step, log_every)
     done_steps, ep_reward, last = 0, [], (0.0, 0.0)
     while done_steps < steps:
         for _ in range(4):
@@ -78,6 +84,32 @@ def pretrain(net: NetworkVP_rnn, env, steps: int = 300, learning_rate: float = 1
                 break
     roll.close()
     return {"p_loss_per_row": last[0], "v_loss_per_row": last[1],
+            "teacher_episode_reward": float(np.mean(ep_reward[-50:])) if ep_reward else float("nan"), "steps": done_steps}
+
+
+def _pretrain_fused(trainer, roll, opt, possible, zeros, steps, rows_per_step, log_every) -> dict:
+    """``pretrain``'s loop with ``FusedA3CTrainer.train_regression`` as the step: no host wait per step."""
+    done_steps, ep_reward, last, rows = 0, [], None, 1
+    while done_steps < steps:
+        for _ in range(4):
+            roll.step(teacher_actions(roll.obs, possible), zeros)
+        b = roll.drain(provenance=False)
+        e = roll.drain_episodes()
+        if e.shape[0]:
+            ep_reward.append(float(e[:, 1].mean()))
+        for lo in range(0, len(b), rows_per_step):
+            x, y, a = b.x[lo:lo + rows_per_step], b.r[lo:lo + rows_per_step], b.a_index[lo:lo + rows_per_step]
+            last, rows = trainer.train_regression(x, y, a, opt=opt), len(y)
+            done_steps += 1
+            if log_every and done_steps % log_every == 0:
+                print("[Regression] step %d  p-loss/row %.4f  v-loss/row %.5f  teacher episode reward %.3f"
+                      % (done_steps, float(last[0]) / rows, float(last[1]) / rows, np.mean(ep_reward[-20:]) if ep_reward else float("nan")),
+                      flush=True)
+            if done_steps >= steps:
+                break
+    roll.close()
+    p_loss, v_loss = (float(last[0]) / rows, float(last[1]) / rows) if last is not None else (0.0, 0.0)
+    return {"p_loss_per_row": p_loss, "v_loss_per_row": v_loss,
             "teacher_episode_reward": float(np.mean(ep_reward[-50:])) if ep_reward else float("nan"), "steps": done_steps}
 
 
