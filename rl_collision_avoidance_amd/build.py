@@ -22,17 +22,17 @@ HEADERS = {
     "cavoid_relay.hip": ["cavoid_kernels.hpp", "cavoid_relay.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
     "cavoid_quad.hip": ["cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
     "cavoid_rollout_capi.hip": ["cavoid_rollout.hpp", "cavoid_rollout_host.hpp", "cavoid_host.hpp"],
-    "cavoid_policy_capi.hip": ["cavoid_policy.hpp", "cavoid_policy_forward_body.hpp", "cavoid_policy_split.hpp", "cavoid_policy_split8.hpp", "cavoid_policy_crowd.hpp", "cavoid_policy_host.hpp",
+    "cavoid_policy_capi.hip": ["cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_split8.hpp", "cavoid_policy_crowd.hpp", "cavoid_policy_host.hpp",
                                "cavoid_host.hpp"],
-    "cavoid_actor.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_forward_body.hpp",
+    "cavoid_actor.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
                          "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp", "cavoid_rollout_host.hpp", "cavoid_host.hpp"],
-    "cavoid_actor_rvo.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_forward_body.hpp",
+    "cavoid_actor_rvo.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
                              "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_actor_frozen.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_forward_body.hpp",
+    "cavoid_actor_frozen.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
                                 "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
     "cavoid_comm_capi.hip": ["cavoid_host.hpp"],
     "cavoid_crowd.hip": ["cavoid_kernels.hpp", "cavoid_crowd.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
-    "cavoid_policy_ws.hip": ["cavoid_policy.hpp", "cavoid_policy_forward_body.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_ws_forward_body.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
+    "cavoid_policy_ws.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
 }
 # per-file extra flags.  The multi-step env kernels run their step loop inside the launch; MachineLICM would hoist every
 # constant materialisation of the body (float64 polynomial coefficients, config scalars) out of that loop into

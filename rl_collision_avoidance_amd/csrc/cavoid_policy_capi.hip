@@ -2,8 +2,6 @@
 // inference kernel of cavoid_policy.hpp.
 #include <hip/hip_runtime.h>
 
-#include <new>
-
 #include "cavoid.h"
 #include "cavoid_host.hpp"
 #define CAVOID_POLICY_KERNELS 1
@@ -23,25 +21,8 @@ extern "C" int cavoid_policy_create(int32_t max_other, int32_t num_actions, int 
     *out = nullptr;
     // M <= kPolMaxOthers: every kernel; up to kPolMaxOthersInference: a CROWD handle -- inference only, on policy_crowd_forward_kernel
     if (max_other < 1 || max_other > kPolMaxOthersInference || num_actions < 1 || num_actions > 15) return CAVOID_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return CAVOID_ENODEVICE;
-    HIP_TRY(hipSetDevice(device));
-    cavoid_policy *h = new (std::nothrow) cavoid_policy();
-    if (!h) return CAVOID_ENOMEM;
-    h->device = device; h->max_other = max_other; h->num_actions = num_actions;
-    h->in_size = 1 + kPolHost + kPolOther * max_other;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_frag = carve((size_t)kPackFragsTrain * sizeof(f32x4)), o_bias = carve(kBiasFloats * sizeof(float));
-    const size_t o_sfrag = carve((size_t)kSpPackFrags8 * sizeof(uint4)), o_sbias = carve(kBiasFloats8 * sizeof(float));
-    const size_t o_avg = carve(h->in_size * sizeof(float)), o_std = carve(h->in_size * sizeof(float));
-    const size_t o_step = carve(sizeof(int32_t)), o_done = carve(sizeof(uint32_t)), o_tick = carve(kPolCuSlots * sizeof(uint32_t));
-    const size_t o_clamp = carve(sizeof(uint32_t));
-    if (hipMalloc(&h->slab, off) != hipSuccess) { delete h; return CAVOID_ENOMEM; }
-    if (hipMemset(h->slab, 0, off) != hipSuccess) { g_last_hip_error = (int)hipGetLastError(); (void)hipFree(h->slab); delete h; return CAVOID_EHIP; }
-    unsigned char *b = static_cast<unsigned char *>(h->slab);
-    h->frags = reinterpret_cast<f32x4 *>(b + o_frag); h->bias = reinterpret_cast<float *>(b + o_bias);
-    h->sfrags = reinterpret_cast<uint4 *>(b + o_sfrag); h->sbias = reinterpret_cast<float *>(b + o_sbias);
+    cavoid_policy *h = nullptr;
+    if (const int rc = policy_new_handle(max_other, num_actions, device, kPackFragsTrain, true, &h)) return rc;
     if (const char *ov = std::getenv("CAVOID_POLICY_F32")) h->use_split = std::atoi(ov) == 0;
     // 16 (default): two float16 pieces per operand, three products -- float32-grade; 3 / 4 / 5: bf16 pieces, that many products (A/B runs)
     if (const char *ov = std::getenv("CAVOID_POLICY_PRODUCTS")) { const int v = std::atoi(ov); if ((v >= 3 && v <= 5) || v == kSpF16) h->split_products = v; }
@@ -54,40 +35,22 @@ extern "C" int cavoid_policy_create(int32_t max_other, int32_t num_actions, int 
     if (h->crowd && (!h->use_split || (h->split_products != kSpF16 && h->split_products != 3))) {   // (the crowd kernel's two product forms)
         (void)hipFree(h->slab); delete h; return CAVOID_EUNSUPPORTED;
     }
-    if (hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->num_cus <= 0) h->num_cus = 256;
-    h->avg = reinterpret_cast<float *>(b + o_avg); h->std = reinterpret_cast<float *>(b + o_std);
-    h->step_counter = reinterpret_cast<int32_t *>(b + o_step); h->blocks_done = reinterpret_cast<uint32_t *>(b + o_done);
-    h->cu_tickets = reinterpret_cast<uint32_t *>(b + o_tick);
-    h->clamped_weights = reinterpret_cast<uint32_t *>(b + o_clamp);
-    // 70 KB of LDS per 64-row workgroup: above the 64 KB static limit, so it is dynamic and opted into here
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_lds_bytes(4)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_lds_bytes(4)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_regression_forward_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_lds_bytes(4)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_backward_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_lds_bytes(4)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split_kernel<kSpF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split_kernel<kSpF16, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_forward_split_duo_kernel<kSpF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_duo_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_crowd_forward_kernel<kSpF16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_lds_bytes()) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(policy_crowd_forward_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)policy_split_lds_bytes()) != hipSuccess) {
-        g_last_hip_error = (int)hipGetLastError(); (void)hipFree(h->slab); delete h; return CAVOID_EHIP;
-    }
+    const PolicyLdsOptIn kernels[] = {
+        {reinterpret_cast<const void *>(policy_forward_kernel<4, false>), policy_lds_bytes(4)},
+        {reinterpret_cast<const void *>(policy_forward_kernel<4, true>), policy_lds_bytes(4)},
+        {reinterpret_cast<const void *>(policy_regression_forward_kernel<4>), policy_lds_bytes(4)},
+        {reinterpret_cast<const void *>(policy_backward_kernel<4>), policy_lds_bytes(4)},
+        {reinterpret_cast<const void *>(policy_forward_split_kernel<3>), policy_split_lds_bytes()},
+        {reinterpret_cast<const void *>(policy_forward_split_kernel<4>), policy_split_lds_bytes()},
+        {reinterpret_cast<const void *>(policy_forward_split_kernel<5>), policy_split_lds_bytes()},
+        {reinterpret_cast<const void *>(policy_forward_split_kernel<kSpF16>), policy_split_lds_bytes()},
+        {reinterpret_cast<const void *>(policy_forward_split_kernel<kSpF16, true>), policy_split_lds_bytes()},
+        {reinterpret_cast<const void *>(policy_forward_split8_kernel), policy_split_lds_bytes()},
+        {reinterpret_cast<const void *>(policy_forward_split_duo_kernel<kSpF16>), policy_split_duo_lds_bytes()},
+        {reinterpret_cast<const void *>(policy_crowd_forward_kernel<kSpF16>), policy_split_lds_bytes()},
+        {reinterpret_cast<const void *>(policy_crowd_forward_kernel<3>), policy_split_lds_bytes()},
+    };
+    if (const int rc = policy_opt_in_lds(h, kernels)) return rc;
     *out = h;
     return CAVOID_OK;
 }
@@ -115,7 +78,6 @@ extern "C" int cavoid_policy_load(cavoid_policy *h, const cavoid_policy_weights 
     const int with_backward = w->with_backward ? 1 : 0;
     const unsigned blocks = (unsigned)(((with_backward ? kPackFragsTrain : kPackFrags) + 255) / 256);
     hipLaunchKernelGGL(policy_pack_kernel, dim3(blocks), dim3(256), 0, s, k, h->frags, h->bias, with_backward);
-    h->backward_loaded = with_backward != 0;
     HIP_TRY(hipGetLastError());
     {   // the inference kernel's copy, fragment order: every weight split into two float16 pieces (22 bits; the default form) or
         // three bf16 pieces (exact; CAVOID_POLICY_PRODUCTS = 3 / 4 / 5)
@@ -129,14 +91,7 @@ extern "C" int cavoid_policy_load(cavoid_policy *h, const cavoid_policy_weights 
             HIP_TRY(hipGetLastError());
         }
     }
-    h->normalize = w->avg != nullptr;
-    if (h->normalize) {
-        HIP_TRY(hipMemcpyAsync(h->avg, w->avg, h->in_size * sizeof(float), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(h->std, w->std, h->in_size * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    h->min_policy = w->min_policy;
-    h->loaded = true;
-    return CAVOID_OK;
+    return policy_finish_load(h, w, s);
 }
 
 extern "C" int cavoid_policy_info(cavoid_policy *h, void *stream, int32_t *use_split, int32_t *split_products, int32_t *clamped_weights) {
@@ -167,13 +122,10 @@ static int policy_forward(cavoid_policy *h, const float *x, int64_t rows, int64_
     if (!h || !x || !p_out || !v_out || rows < 0 || row_stride < h->in_size || row_stride > (h->crowd ? kPolCrowdMaxStride : 256)) return CAVOID_EINVAL;
     if (!h->loaded) return CAVOID_EINVAL;
     if (rows == 0) return CAVOID_OK;
-    PolicyArgs a{};
-    a.x = x; a.rows = rows; a.stride = row_stride; a.max_other = h->max_other; a.num_actions = h->num_actions; a.in_size = h->in_size;
-    a.avg = h->normalize ? h->avg : nullptr; a.std = h->normalize ? h->std : nullptr;
-    a.frags = h->frags; a.bias = h->bias; a.min_policy = h->min_policy; a.p_out = p_out; a.v_out = v_out;
-    a.actions_out = actions_out; a.greedy = greedy ? 1 : 0;
+    PolicyArgs a = policy_common_args(h, x, rows, row_stride);
+    a.p_out = p_out; a.v_out = v_out; a.actions_out = actions_out; a.greedy = greedy ? 1 : 0;
     a.seed_lo = (uint32_t)h->seed; a.seed_hi = (uint32_t)(h->seed >> 32);
-    a.step_counter = h->step_counter; a.blocks_done = h->blocks_done; a.cu_tickets = h->cu_tickets;
+    a.step_counter = h->step_counter; a.blocks_done = h->blocks_done;
     a.row_index = row_index; a.row_count = row_count;
     const int tile = 16 * h->row_tiles;
     const int64_t blocks = (rows + tile - 1) / tile;
@@ -223,29 +175,18 @@ static int policy_train(cavoid_policy *h, const float *x, int64_t rows, int64_t 
     if (h->ws) return CAVOID_EINVAL;                       // (a weight-sharing handle trains with cavoid_policy_train_ws)
     if (h->crowd) return CAVOID_EUNSUPPORTED;              // (the trainer pass parks the whole row: kPolMaxOthers)
     if (!h->loaded || !h->backward_loaded || rows < 0 || row_stride < h->in_size) return CAVOID_EINVAL;
-    const int64_t rows64 = (rows + 63) / 64 * 64;
-    if (b->capacity_rows < rows64 || b->capacity_rows % 64 != 0 || !b->z1 || !b->z2 || !b->z3 || !b->l1_in || !b->h_in || !b->save || !b->gh || !b->loss ||
-        !b->g1 || !b->g2 || !b->g3 || !b->gl || !b->db)
-        return CAVOID_EINVAL;
+    if (!b->h_in || !b->save || !b->gl) return CAVOID_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(b->loss, 0, 2 * sizeof(float), s));
-    HIP_TRY(hipMemsetAsync(b->db, 0, kBiasFloats * sizeof(float), s));
-    if (rows == 0) return CAVOID_OK;
-    const int64_t cap = b->capacity_rows;                  // leading dimension (in rows) of the per-step buffers
-    PolicyArgs a{};
-    a.x = x; a.rows = rows; a.stride = row_stride; a.max_other = h->max_other; a.num_actions = h->num_actions; a.in_size = h->in_size;
-    a.avg = h->normalize ? h->avg : nullptr; a.std = h->normalize ? h->std : nullptr;
-    a.frags = h->frags; a.bias = h->bias; a.min_policy = h->min_policy; a.cu_tickets = h->cu_tickets;
-    a.y_r = y_r; a.a_idx = a_idx; a.beta = beta; a.log_eps = log_epsilon; a.rows64 = cap;
-    a.z1 = b->z1; a.z2 = b->z2; a.z3 = b->z3; a.l1_in = b->l1_in; a.h_in = b->h_in; a.save = b->save; a.gh = b->gh; a.loss = b->loss; a.db = b->db;
-    // every tile of the buffers is processed (tiles past `rows` carry zero gradients), so that the caller can run its
-    // weight-gradient GEMMs over a convenient row count without ever reading stale rows
-    const unsigned blocks = (unsigned)(cap / 64);
+    PolicyArgs a;
+    unsigned blocks = 0;
+    if (const int rc = policy_train_begin(h, x, rows, row_stride, y_r, a_idx, beta, log_epsilon, b, s, &a, &blocks)) return rc;
+    if (blocks == 0) return CAVOID_OK;
+    a.h_in = b->h_in; a.save = b->save;
     if (loss_kind == kLossRegression) hipLaunchKernelGGL(policy_regression_forward_kernel<4>, dim3(blocks), dim3(256), policy_lds_bytes(4), s, a);
     else hipLaunchKernelGGL((policy_forward_kernel<4, true>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, a);
     HIP_TRY(hipGetLastError());
     PolicyBackArgs k{};
-    k.x = x; k.rows = rows; k.stride = row_stride; k.rows64 = cap; k.max_other = h->max_other; k.frags = h->frags;
+    k.x = x; k.rows = rows; k.stride = row_stride; k.rows64 = a.rows64; k.max_other = h->max_other; k.frags = h->frags;
     k.z1 = b->z1; k.z2 = b->z2; k.z3 = b->z3; k.save = b->save; k.gh = b->gh; k.g1 = b->g1; k.g2 = b->g2; k.g3 = b->g3; k.gl = b->gl; k.db = b->db; k.h_in = b->h_in;
     hipLaunchKernelGGL((policy_backward_kernel<4>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, k);
     HIP_TRY(hipGetLastError());

@@ -97,16 +97,13 @@ class FusedPolicy(object):
         self._keep = []                  # tensors that had to be made contiguous stay alive until the next refresh
         if n.normalize:
             w.avg, w.std = ptr(n.avg), ptr(n.std)
-        if self.ws:                      # (the lstm fields stay NULL: cavoid_policy_load_ws ignores them)
-            for name in ("layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel", "fc1_bias", "p_kernel", "p_bias",
-                         "v_kernel", "v_bias"):
-                setattr(w, name, ptr(getattr(n, name)))
+        names = ("layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel", "fc1_bias", "p_kernel", "p_bias", "v_kernel", "v_bias")
+        for name in names if self.ws else ("lstm_kernel", "lstm_bias") + names:      # (weight_sharing: the lstm fields stay NULL)
+            setattr(w, name, ptr(getattr(n, name)))
+        if self.ws:
             _lib.check(self._lib.cavoid_policy_load_ws(self._h, C.byref(w), ptr(n.other_kernel), ptr(n.other_bias), self._stream()),
                        "cavoid_policy_load_ws")
             return
-        for name in ("lstm_kernel", "lstm_bias", "layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias",
-                     "fc1_kernel", "fc1_bias", "p_kernel", "p_bias", "v_kernel", "v_bias"):
-            setattr(w, name, ptr(getattr(n, name)))
         _lib.check(self._lib.cavoid_policy_load(self._h, C.byref(w), self._stream()), "cavoid_policy_load")
         if check_range and self.inference_form == ("split", 16):
             bad = self.clamped_weights()
@@ -203,28 +200,19 @@ class FusedA3CTrainer(object):
     frame_counter = property(lambda self: self._base.frame_counter)
 
     def _scratch(self, rows64: int):
+        """The pass's buffers for rows64 buffer rows: (tensors by name, the C struct that points at them)."""
         b = self._buffers.get(rows64)
-        if b is None and self.ws:
-            M, dev = self.net.max_others, self.device
-            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            t = {"z1": f(rows64, 256), "z2": f(rows64, 256), "z3": f(rows64, 256), "l1_in": f(rows64, 4 + 64 * M), "f_in": f(M, rows64, 8),
-                 "gh": f(rows64, 16), "loss": f(2), "g1": f(rows64, 256), "g2": f(rows64, 256), "g3": f(rows64, 256),
-                 "gf": f(M, rows64, 64), "db": f(1040)}
-            c = _lib.CavoidPolicyTrainWsBuffers()
-            c.struct_size, c.capacity_rows = C.sizeof(_lib.CavoidPolicyTrainWsBuffers), rows64
-            for k, v in t.items():
-                setattr(c, k, C.c_void_p(v.data_ptr()))
-            b = self._buffers[rows64] = (t, c)
-            if len(self._buffers) > 4:
-                self._buffers.pop(next(iter(self._buffers)))
         if b is None:
-            M, dev = self.net.max_others, self.device
-            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            t = {"z1": f(rows64, 256), "z2": f(rows64, 256), "z3": f(rows64, 256), "l1_in": f(rows64, 72), "h_in": f(M, rows64, 72),
-                 "save": f(rows64 // 64, M, 16, 256, 8), "gh": f(rows64, 16), "loss": f(2), "g1": f(rows64, 256), "g2": f(rows64, 256),
-                 "g3": f(rows64, 256), "gl": f(M, rows64, 256), "db": f(1040)}
-            c = _lib.CavoidPolicyTrainBuffers()
-            c.struct_size, c.capacity_rows = C.sizeof(_lib.CavoidPolicyTrainBuffers), rows64
+            M, R = self.net.max_others, rows64
+            shapes = {"z1": (R, 256), "z2": (R, 256), "z3": (R, 256), "gh": (R, 16), "loss": (2,), "g1": (R, 256), "g2": (R, 256),
+                      "g3": (R, 256), "db": (1040,)}
+            if self.ws:
+                shapes.update(l1_in=(R, 4 + 64 * M), f_in=(M, R, 8), gf=(M, R, 64))
+            else:
+                shapes.update(l1_in=(R, 72), h_in=(M, R, 72), save=(R // 64, M, 16, 256, 8), gl=(M, R, 256))
+            t = {k: torch.empty(shape, dtype=torch.float32, device=self.device) for k, shape in shapes.items()}
+            c = (_lib.CavoidPolicyTrainWsBuffers if self.ws else _lib.CavoidPolicyTrainBuffers)()
+            c.struct_size, c.capacity_rows = C.sizeof(c), rows64
             for k, v in t.items():
                 setattr(c, k, C.c_void_p(v.data_ptr()))
             b = self._buffers[rows64] = (t, c)

@@ -158,7 +158,7 @@ def _cases():
 
 
 TRAINER_CASES = _cases()
-# the weight-sharing trainer's own copy of the epilogue with MIN_POLICY > 0 (the LSTM trainer's test has such a case) ...
+# the weight-sharing trainer's instantiation of the epilogue (policy_heads) with MIN_POLICY > 0 (the LSTM trainer's test has such a case) ...
 WS_MIN_POLICY_CASES = [_case("beta", "weight_sharing", M, 1000, 1e-4, min_policy=1e-3) for M in (3, 7)]
 # ... and one trainer, two calls, beta = 0 then beta = 1
 BETA_SWITCH_CASES = [_case("beta", arch, M, 1000, 0.0) for arch, M in ARCH_M]

@@ -1,6 +1,6 @@
 """The epilogue that follows the heads -- softmax + MIN_POLICY, the A3C loss and its gradient at the logits, the action draw -- where the
-entropy term and the log clamp matter.  Every fused path carries its own copy of it (cavoid_policy.hpp, policy_ws_heads in
-cavoid_policy_ws.hpp, the softmax blocks of the split / oct forms, split_select_action inlined into the split, oct, pipe, crowd and fused
+entropy term and the log clamp matter.  It exists in several copies (policy_heads of cavoid_policy.hpp, which the LSTM and the
+weight-sharing float32-MFMA kernels share, the softmax blocks of the split / oct forms, split_select_action inlined into the split, oct, pipe, crowd and fused
 actor kernels), and the other test files hold all of them to the PyTorch network in ONE regime: fresh Glorot weights, whose softmax is
 nearly uniform (no p within four orders of magnitude of LOG_EPSILON, beta = 1e-4: an entropy gradient below the tolerances).  Here:
   * both FusedA3CTrainer paths against float64 autograd of NetworkVP_rnn.loss under test_fused_trainer_gradients_match_autograd's own
