@@ -402,7 +402,8 @@ int cavoid_step_push(cavoid_env *env, cavoid_rollout *rollout, const cavoid_roll
  * the step blocks [step_lo, step_hi) to one batch -- out_x float [capacity, D], out_r float [capacity] (n-step returns),
  * out_a int32 [capacity], out_src int32 [capacity, 4] (world, agent, recorded-at, emitted-at; may be NULL),
  * out_count int32 [2] = (rows appended, rows dropped for lack of capacity), zeroed by the call.  Row order is unspecified.
- * mark_taken != 0 stamps the rows emit_t = -2 (they are not handed out again). */
+ * mark_taken != 0 stamps the rows emit_t = -2 (they are not handed out again).  Rows of every width the env makes are carried
+ * (D up to 453 = 5 + 7 * 64); CAVOID_EUNSUPPORTED only from D = 4096 up, where the copy loop's multiply-shift e / D is no longer exact. */
 int cavoid_rollout_compact(cavoid_rollout *r, int32_t step_lo, int32_t step_hi, int32_t mark_taken, const float *x, const float *ret,
                            const uint8_t *act, int32_t *emit_t, float *out_x, float *out_r, int32_t *out_a, int32_t *out_src,
                            int32_t *out_count, int64_t capacity, void *stream);
@@ -433,12 +434,14 @@ int cavoid_rollout_active_rows(cavoid_rollout *r, const float *obs, const uint8_
  *                          (seed, row, launch counter); the counter lives on the device (hipGraph replays).
  * Observed agents: cavoid_policy_create takes max_other 1..64 (the env's own limit); 65 and up is CAVOID_EINVAL.
  *   max_other <= 19: every kernel below -- the inference forms (CAVOID_POLICY_F32 / _PRODUCTS / _FORM), the trainer pass, the fused actor.
- *   20..64, a CROWD handle: inference only, on one kernel that streams the observed agents through a ring of input slots; a row of
+ *   20..64, a CROWD handle: inference on one kernel that streams the observed agents through a ring of input slots; a row of
  *     <= 19 observed agents gets bit for bit what a handle of max_other <= 19 gives it.  Two product forms: the default (float16 pieces) and
  *     CAVOID_POLICY_PRODUCTS=3 (bf16 pieces, float32's range); CAVOID_POLICY_F32=1 or _PRODUCTS=4 / 5 make cavoid_policy_create return
  *     CAVOID_EUNSUPPORTED, CAVOID_POLICY_FORM is ignored.  cavoid_policy_forward / _rows take a row_stride up to 455 floats (1 + 6 + 7 * 64:
- *     the widest env observation row; 256 for max_other <= 19).  cavoid_policy_train and cavoid_actor_run / _run_mix return
- *     CAVOID_EUNSUPPORTED: the trainer pass and the actor kernel park the whole input row and stop at 19. */
+ *     the widest env observation row; 256 for max_other <= 19).  cavoid_policy_train / _train_regression run their forward launch on
+ *     ring kernels of the same kind (float32 MFMA, whatever the inference form) and the unchanged backward launch behind it: same
+ *     buffers and contract, bit for bit a max_other <= 19 handle's results on rows of <= 19 observed agents.  cavoid_actor_run /
+ *     _run_mix return CAVOID_EUNSUPPORTED: the actor kernel parks the whole input row and stops at 19. */
 typedef struct cavoid_policy_weights {
     int32_t struct_size;             /* sizeof(cavoid_policy_weights) */
     float min_policy;                /* Config.MIN_POLICY */
@@ -483,7 +486,9 @@ int cavoid_policy_forward_rows(cavoid_policy *p, const float *x, int64_t rows, i
  *   d [logits_p | logits_v] = z3^T gh,  d lstm (rows: 64 hidden then 7 inputs; gate columns in packed order
  *   64w + 16 gate + u for unit 16w + u) = sum_t h_in[t]^T gl[t];   bias gradients (column sums of g3, g2, g1, gh, gl) come back in `db`.
  * All per-row buffers have `capacity_rows` rows (a multiple of 64, >= rows rounded up to 64); every one of them is
- * written by each call, rows past `rows` with zero gradients -- the GEMMs may run over all capacity_rows.  loss[0] = cost_p, loss[1] = cost_v (sums over rows, NetworkVPCore.py:71-100). */
+ * written by each call, rows past `rows` with zero gradients -- the GEMMs may run over all capacity_rows.  loss[0] = cost_p, loss[1] = cost_v (sums over rows, NetworkVPCore.py:71-100).
+ * max_other 1..64: a crowd handle (20..64) takes the same call and buffers.  Mind their size there: 6 496 + 3 360 max_other bytes per
+ * buffer row, 218 KB at max_other = 63. */
 typedef struct cavoid_policy_train_buffers {
     int32_t struct_size;             /* sizeof(cavoid_policy_train_buffers) */
     int32_t reserved;
@@ -540,7 +545,7 @@ int cavoid_policy_train_ws(cavoid_policy *p, const float *x, int64_t rows, int64
 /* ---- the supervised start's trainer pass (train_regression_op on cost_regression, ga3c/GA3C/NetworkVPCore.py:90-100,123; the
  * phase Regression.py runs for TRAIN_ONLY_REGRESSION and LOAD_REGRESSION_THEN_TRAIN_RL) ------------------------------------------
  * cavoid_policy_train / cavoid_policy_train_ws with the other loss head, everything else the same: the same two launches, buffer
- * structs, preconditions (with_backward = 1, max_other <= 19, capacity_rows), caller's GEMMs, db layout and error codes -- the LSTM
+ * structs, preconditions (with_backward = 1, max_other <= 64 / <= 19 for _ws, capacity_rows), caller's GEMMs, db layout and error codes -- the LSTM
  * call on a weight-sharing handle and the _ws call on an LSTM handle are CAVOID_EINVAL.  Per row, with z the A policy logits, v the
  * value logit, a_idx the TEACHER's action and y_r the value target:
  *   cost_p_regression = log sum_k exp(z_k) - z_a   (softmax cross-entropy on the logits, evaluated as log-sum-exp: finite and exact

@@ -19,7 +19,8 @@ using namespace cavoid;
 extern "C" int cavoid_policy_create(int32_t max_other, int32_t num_actions, int device, cavoid_policy **out) {
     if (!out) return CAVOID_EINVAL;
     *out = nullptr;
-    // M <= kPolMaxOthers: every kernel; up to kPolMaxOthersInference: a CROWD handle -- inference only, on policy_crowd_forward_kernel
+    // M <= kPolMaxOthers: every kernel; up to kPolMaxOthersInference: a CROWD handle -- inference on policy_crowd_forward_kernel, the trainer
+    // pass on the ring kernels of cavoid_policy_train_ring.hpp
     if (max_other < 1 || max_other > kPolMaxOthersInference || num_actions < 1 || num_actions > 15) return CAVOID_EINVAL;
     cavoid_policy *h = nullptr;
     if (const int rc = policy_new_handle(max_other, num_actions, device, kPackFragsTrain, true, &h)) return rc;
@@ -51,6 +52,8 @@ extern "C" int cavoid_policy_create(int32_t max_other, int32_t num_actions, int 
         {reinterpret_cast<const void *>(policy_crowd_forward_kernel<3>), policy_split_lds_bytes()},
     };
     if (const int rc = policy_opt_in_lds(h, kernels)) return rc;
+    if (h->crowd)
+        if (const int rc = cavoid_policy_train_ring_opt_in(h)) return rc;
     *out = h;
     return CAVOID_OK;
 }
@@ -173,7 +176,6 @@ static int policy_train(cavoid_policy *h, const float *x, int64_t rows, int64_t 
                         float beta, float log_epsilon, const cavoid_policy_train_buffers *b, void *stream, int loss_kind) {
     if (!h || !x || !y_r || !a_idx || !b || b->struct_size != (int32_t)sizeof(cavoid_policy_train_buffers)) return CAVOID_EINVAL;
     if (h->ws) return CAVOID_EINVAL;                       // (a weight-sharing handle trains with cavoid_policy_train_ws)
-    if (h->crowd) return CAVOID_EUNSUPPORTED;              // (the trainer pass parks the whole row: kPolMaxOthers)
     if (!h->loaded || !h->backward_loaded || rows < 0 || row_stride < h->in_size) return CAVOID_EINVAL;
     if (!b->h_in || !b->save || !b->gl) return CAVOID_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -182,7 +184,9 @@ static int policy_train(cavoid_policy *h, const float *x, int64_t rows, int64_t 
     if (const int rc = policy_train_begin(h, x, rows, row_stride, y_r, a_idx, beta, log_epsilon, b, s, &a, &blocks)) return rc;
     if (blocks == 0) return CAVOID_OK;
     a.h_in = b->h_in; a.save = b->save;
-    if (loss_kind == kLossRegression) hipLaunchKernelGGL(policy_regression_forward_kernel<4>, dim3(blocks), dim3(256), policy_lds_bytes(4), s, a);
+    if (h->crowd) {                                        // (the forward parks R agents of the row at a time: cavoid_policy_train_ring.hpp)
+        if (const int rc = cavoid_policy_train_ring_launch(h, a, blocks, loss_kind, s)) return rc;
+    } else if (loss_kind == kLossRegression) hipLaunchKernelGGL(policy_regression_forward_kernel<4>, dim3(blocks), dim3(256), policy_lds_bytes(4), s, a);
     else hipLaunchKernelGGL((policy_forward_kernel<4, true>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, a);
     HIP_TRY(hipGetLastError());
     PolicyBackArgs k{};

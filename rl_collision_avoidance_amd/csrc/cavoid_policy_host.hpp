@@ -40,6 +40,10 @@ struct cavoid_policy {
 
 // the inference launch of a weight-sharing handle (cavoid_policy_ws.hip): cavoid_policy_forward / _rows route there
 int cavoid_policy_ws_launch(cavoid_policy *h, const cavoid::PolicyArgs &a, int64_t blocks, hipStream_t stream);
+// the trainer's forward pass of a crowd handle (cavoid_policy_train_ring.hip): cavoid_policy_train / _train_regression route there, then launch
+// policy_backward_kernel themselves.  _opt_in: the two ring kernels' dynamic LDS, at creation (on failure the handle is gone)
+int cavoid_policy_train_ring_opt_in(cavoid_policy *h);
+int cavoid_policy_train_ring_launch(cavoid_policy *h, const cavoid::PolicyArgs &a, unsigned blocks, int loss_kind, hipStream_t stream);
 
 // ---- creation -------------------------------------------------------------------------------------------------------------------
 // The handle of cavoid_policy_create / _create_ws, once the caller has checked the argument ranges: the device check, then one zeroed

@@ -387,7 +387,7 @@ __global__ void __launch_bounds__(256) rollout_compact_kernel(const RolloutCfg c
     for (int g = 0; g < kCompactSpan; ++g)
         if (emitted[g] >= 0) slot_of_rank[wave][rank[g]] = 64 * g + lane;
     __builtin_amdgcn_wave_barrier();                       // wave-private table: LDS operations of a wavefront are in order
-    const uint32_t inv_d = (uint32_t)((1ull << 32) / (uint32_t)D) + 1u;      // e / D by multiply-shift (e < 2^16)
+    const uint32_t inv_d = (uint32_t)((1ull << 32) / (uint32_t)D) + 1u;      // e / D by multiply-shift (exact while e D < 2^32: cavoid_rollout_compact)
     const float *__restrict__ src = a.x + (block_row0 + span0) * D;
     float *__restrict__ dstx = a.out_x + base * D;
     const int total = fit * D;

@@ -92,7 +92,15 @@ extern "C" int cavoid_rollout_compact(cavoid_rollout *r, int32_t step_lo, int32_
     CompactArgs a{};
     a.step_lo = step_lo; a.step_hi = step_hi; a.mark_taken = mark_taken ? 1 : 0; a.x = x; a.ret = ret; a.act = act; a.emit_t = emit_t;
     a.out_x = out_x; a.out_r = out_r; a.out_a = out_a; a.out_src = out_src; a.out_count = out_count; a.capacity = capacity;
-    if ((int64_t)(r->c.obs_width - 1) * 64 * kCompactSpan > 65535) return CAVOID_EUNSUPPORTED;   // (the copy loop's e / D trick)
+    // The copy loop takes e / D (D = obs_width - 1 floats per row) as (e * inv_d) >> 32 with inv_d = floor(2^32 / D) + 1 = (2^32 + k) / D,
+    // 1 <= k <= D.  For e = q D + s (0 <= s < D): e inv_d / 2^32 = q + s / D + e k / (D 2^32), whose floor is q exactly when
+    // e k < (D - s) 2^32 -- and e k <= e D, D - s >= 1: exact while e D < 2^32.  A wavefront copies at most 64 kCompactSpan rows and its
+    // last trip of 8 x 64 elements runs at most 511 past them (those lanes are masked, their quotient still indexes the rank table's
+    // neighbourhood): e < 64 kCompactSpan D + 512.  The widest row the env makes is D = 453 (5 + 7 x 64): 453 x 116 480 = 5.3e7.
+    {
+        const uint64_t D = (uint64_t)(r->c.obs_width - 1);
+        if ((64 * kCompactSpan * D + 512) * D >= (1ull << 32)) return CAVOID_EUNSUPPORTED;
+    }
     const int per_block = 256 * kCompactSpan;
     const dim3 grid((unsigned)((r->c.num_slots + per_block - 1) / per_block), (unsigned)(step_hi - step_lo));
     hipLaunchKernelGGL(rollout_compact_kernel, grid, dim3(256), 0, s, r->c, a);

@@ -22,6 +22,9 @@ MAX_OTHERS = 19
 # ... and fused inference (FusedPolicy: predict_p_and_v + select_action), on the crowd kernel above MAX_OTHERS (kPolMaxOthersInference,
 # cavoid_policy_crowd.hpp)
 MAX_OTHERS_INFERENCE = 64
+# the most observed neighbours the fused trainer carries when asked to (FusedA3CTrainer(crowd=True)): rows above MAX_OTHERS run the ring trainer
+# kernels (kPolMaxOthersTrain, cavoid_policy_train_ring.hpp -- tests/test_policy_train_ring_host.py holds the two equal)
+MAX_OTHERS_TRAIN = 64
 # the most observed neighbours the weight-sharing kernels carry, inference and trainer alike (kWsMaxOthers, cavoid_policy_ws.hpp --
 # tests/test_policy_ws_host.py holds the two equal): wider weight-sharing rows act and train through PyTorch
 MAX_OTHERS_WS = 19
@@ -45,7 +48,7 @@ class FusedPolicy(object):
                              "observes %d" % (MAX_OTHERS_WS, self.max_others))
         if self.max_others > MAX_OTHERS_INFERENCE:
             raise ValueError("FusedPolicy carries up to %d observed neighbours, the network observes %d" % (MAX_OTHERS_INFERENCE, self.max_others))
-        self.crowd = self.max_others > MAX_OTHERS      # the crowd handle: inference only, float16 or bf16 pieces (include/cavoid.h)
+        self.crowd = self.max_others > MAX_OTHERS      # the crowd handle: inference in float16 or bf16 pieces, the trainer pass on the ring kernels (include/cavoid.h)
         self._lib = _lib.lib()
         h = C.c_void_p()
         create = self._lib.cavoid_policy_create_ws if self.ws else self._lib.cavoid_policy_create
@@ -166,13 +169,20 @@ class FusedA3CTrainer(object):
     (``cavoid_policy_train``); the weight gradients are the library GEMMs ``X^T G`` over all rows (split-K batched), the
     optimiser is the same fused Adam as ``A3CTrainer``.  Gradients equal PyTorch autograd's on ``NetworkVP_rnn.loss`` to
     float32 rounding (tests/test_gpu_policy.py).  ``train_regression`` is the supervised start's step on the same pair with the
-    regression loss head (``cavoid_policy_train_regression``; tests/test_gpu_policy_regression.py)."""
+    regression loss head (``cavoid_policy_train_regression``; tests/test_gpu_policy_regression.py).
+    ``crowd=True`` (opt-in; the step's time against autograd: profiles/policy_crowd_train_timing.txt) accepts an 'rnn' network of MAX_OTHERS + 1 .. MAX_OTHERS_TRAIN observed
+    neighbours: the same two calls on a crowd handle, whose forward launch is the ring kernel of cavoid_policy_train_ring.hpp
+    (tests/test_gpu_policy_train_ring.py).  Mind ``scratch_bytes``: the pass keeps 3 360 bytes per buffer row and observed neighbour."""
 
     def __init__(self, net: NetworkVP_rnn, policy: Optional[FusedPolicy] = None, learning_rate: float = 2e-5, group=None,
-                 distributed: Optional[bool] = None):
+                 distributed: Optional[bool] = None, crowd: bool = False):
         from .network import A3CTrainer
         self.ws = net.arch == "weight_sharing"          # cavoid_policy_train_ws (limit: FusedPolicy's MAX_OTHERS_WS)
-        if not self.ws and net.max_others > MAX_OTHERS:
+        self.crowd = bool(crowd) and not self.ws and net.max_others > MAX_OTHERS
+        if self.crowd and net.max_others > MAX_OTHERS_TRAIN:
+            raise ValueError("the fused ring trainer carries up to %d observed neighbours (kPolMaxOthersTrain), the network observes %d: "
+                             "train with A3CTrainer (autograd)" % (MAX_OTHERS_TRAIN, net.max_others))
+        if not self.ws and not self.crowd and net.max_others > MAX_OTHERS:
             raise ValueError("the fused trainer carries up to %d observed neighbours (kPolMaxOthers), the network observes %d: "
                              "train with A3CTrainer (autograd)" % (MAX_OTHERS, net.max_others))
         self.net = net
@@ -199,6 +209,21 @@ class FusedA3CTrainer(object):
                              lambda self, v: setattr(self._base, "training_step", v))
     frame_counter = property(lambda self: self._base.frame_counter)
 
+    @staticmethod
+    def buffer_rows(n: int) -> int:
+        """Buffer rows of a pass over n rows: a multiple of 2048 (the split-K slice of the weight-gradient GEMMs) once the batch is that
+        large, else of the kernels' 64-row tile."""
+        return (n + 2047) // 2048 * 2048 if n >= 2048 else (n + 63) // 64 * 64
+
+    @staticmethod
+    def scratch_bytes(max_others: int, rows: int, arch: str = "rnn") -> int:
+        """Bytes of device memory ``_scratch`` holds for ``rows`` buffer rows (see ``buffer_rows``), without the 4 168 bytes of loss and
+        bias gradients.  'rnn': 6 496 + 3 360 M per row -- z1..z3, g1..g3 (6 x 1 024), gh (64), l1_in (288); per observed neighbour h_in (288),
+        save (2 048), gl (1 024): 218 KB per row at M = 63.  'weight_sharing': 6 224 + 544 M."""
+        if arch == "weight_sharing":
+            return rows * (6 * 1024 + 64 + 4 * 4 + (4 * 64 + 32 + 256) * max_others)
+        return rows * (6496 + 3360 * max_others)
+
     def _scratch(self, rows64: int):
         """The pass's buffers for rows64 buffer rows: (tensors by name, the C struct that points at them)."""
         b = self._buffers.get(rows64)
@@ -216,7 +241,7 @@ class FusedA3CTrainer(object):
             for k, v in t.items():
                 setattr(c, k, C.c_void_p(v.data_ptr()))
             b = self._buffers[rows64] = (t, c)
-            if len(self._buffers) > 4:                     # keep the cache small: minibatch size + a remainder or two
+            if len(self._buffers) > (2 if self.crowd else 4):  # keep the cache small: minibatch size + a remainder or two (crowd rows: GBs each)
                 self._buffers.pop(next(iter(self._buffers)))
         return b
 
@@ -236,7 +261,7 @@ class FusedA3CTrainer(object):
         net, pol = self.net, self.policy
         # buffer rows: a multiple of 2048 (the split-K slice of the weight-gradient GEMMs) once the batch is that large;
         # the kernels write every buffer row, rows past n with zero gradients
-        rows64 = (n + 2047) // 2048 * 2048 if n >= 2048 else (n + 63) // 64 * 64
+        rows64 = self.buffer_rows(n)
         t, cbuf = self._scratch(rows64)
         ptr = lambda v: C.c_void_p(v.data_ptr())
         name = "cavoid_policy_train" + ("_regression" if regression else "") + ("_ws" if self.ws else "")
