@@ -512,8 +512,16 @@ int cavoid_policy_train(cavoid_policy *p, const float *x, int64_t rows, int64_t 
  *   f_i = relu([xn_i (7) | is_on_i] . other_kernel[8, 64] + other_bias[64]),  is_on_i = (x[:,0] >= i + 1) on the RAW count,
  *   layer1 = relu([host(4) | f_0 .. f_{max_other-1}] . layer1_kernel[4 + 64 max_other, 256] + layer1_bias), then layer2,
  *   fullyconnected1 and the heads as for the LSTM network.  Float32 MFMA (no split form; the products are exact float32).
- *   cavoid_policy_create_ws: max_other 1..19 (the kernel parks the whole input row); 20..64 is CAVOID_EUNSUPPORTED, outside 1..64
+ *   cavoid_policy_create_ws: max_other 1..19 (the kernel parks the whole input row); 20..64 is CAVOID_EUNSUPPORTED (_create_ws_crowd
+ *       takes those), outside 1..64
  *       CAVOID_EINVAL (the range is checked before the device).
+ *   cavoid_policy_create_ws_crowd: max_other 20..64, the handle for the rows the crowd step form's worlds observe.  1..19 is
+ *       CAVOID_EUNSUPPORTED (use cavoid_policy_create_ws), outside 1..64 CAVOID_EINVAL (the range is checked before the device).  Every
+ *       call below takes such a handle as it takes a cavoid_policy_create_ws one -- same arguments, buffers, contract and error codes;
+ *       cavoid_policy_forward / _rows then take a row_stride up to 455 floats, and the forward launches (inference, _train_ws,
+ *       _train_regression_ws) run on kernels that park 19 slots of the row at a time and stream the rest through them as a ring; the
+ *       backward launch is the same kernel.  On rows whose slots past 19 carry zero layer1 weights they give bit for bit what a
+ *       max_other = 19 handle gives.  Mind the trainer buffers' size: 6 224 + 544 max_other bytes per buffer row.
  *   cavoid_policy_load_ws  : w as for cavoid_policy_load, except that w->layer1_kernel is [4 + 64 max_other, 256] (rows: host, then
  *       slot-major) and the lstm fields and forget_bias are ignored; other_kernel [8, 64], other_bias [64].
  *   cavoid_policy_forward / _forward_rows / _seed / _info / _destroy take either kind of handle (same arguments, same action draw;
@@ -538,6 +546,7 @@ typedef struct cavoid_policy_train_ws_buffers {
     float *db;                       /* [1040] */
 } cavoid_policy_train_ws_buffers;
 int cavoid_policy_create_ws(int32_t max_other, int32_t num_actions, int device, cavoid_policy **out);
+int cavoid_policy_create_ws_crowd(int32_t max_other, int32_t num_actions, int device, cavoid_policy **out);
 int cavoid_policy_load_ws(cavoid_policy *p, const cavoid_policy_weights *w, const float *other_kernel, const float *other_bias, void *stream);
 int cavoid_policy_train_ws(cavoid_policy *p, const float *x, int64_t rows, int64_t row_stride, const float *y_r, const int32_t *a_idx,
                            float beta, float log_epsilon, const cavoid_policy_train_ws_buffers *buffers, void *stream);
@@ -545,7 +554,7 @@ int cavoid_policy_train_ws(cavoid_policy *p, const float *x, int64_t rows, int64
 /* ---- the supervised start's trainer pass (train_regression_op on cost_regression, ga3c/GA3C/NetworkVPCore.py:90-100,123; the
  * phase Regression.py runs for TRAIN_ONLY_REGRESSION and LOAD_REGRESSION_THEN_TRAIN_RL) ------------------------------------------
  * cavoid_policy_train / cavoid_policy_train_ws with the other loss head, everything else the same: the same two launches, buffer
- * structs, preconditions (with_backward = 1, max_other <= 64 / <= 19 for _ws, capacity_rows), caller's GEMMs, db layout and error codes -- the LSTM
+ * structs, preconditions (with_backward = 1, max_other <= 64 / for _ws <= 19, or <= 64 on a cavoid_policy_create_ws_crowd handle; capacity_rows), caller's GEMMs, db layout and error codes -- the LSTM
  * call on a weight-sharing handle and the _ws call on an LSTM handle are CAVOID_EINVAL.  Per row, with z the A policy logits, v the
  * value logit, a_idx the TEACHER's action and y_r the value target:
  *   cost_p_regression = log sum_k exp(z_k) - z_a   (softmax cross-entropy on the logits, evaluated as log-sum-exp: finite and exact

@@ -152,6 +152,7 @@ SYMBOLS = [
     ("cavoid_policy_forward", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int32, _P]),
     ("cavoid_policy_train", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_float, C.POINTER(CavoidPolicyTrainBuffers), _P]),
     ("cavoid_policy_create_ws", C.c_int, [C.c_int32, C.c_int32, C.c_int, C.POINTER(_P)]),
+    ("cavoid_policy_create_ws_crowd", C.c_int, [C.c_int32, C.c_int32, C.c_int, C.POINTER(_P)]),
     ("cavoid_policy_load_ws", C.c_int, [_P, C.POINTER(CavoidPolicyWeights), _P, _P, _P]),
     ("cavoid_policy_train_ws", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_float, C.POINTER(CavoidPolicyTrainWsBuffers), _P]),
     ("cavoid_policy_train_regression", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(CavoidPolicyTrainBuffers), _P]),

@@ -14,7 +14,8 @@ SOURCES = [os.path.join(CSRC, "cavoid_capi.hip"), os.path.join(CSRC, "cavoid_mul
            os.path.join(CSRC, "cavoid_relay.hip"), os.path.join(CSRC, "cavoid_quad.hip"), os.path.join(CSRC, "cavoid_rollout_capi.hip"),
            os.path.join(CSRC, "cavoid_policy_capi.hip"), os.path.join(CSRC, "cavoid_comm_capi.hip"), os.path.join(CSRC, "cavoid_actor.hip"),
            os.path.join(CSRC, "cavoid_actor_rvo.hip"), os.path.join(CSRC, "cavoid_actor_frozen.hip"), os.path.join(CSRC, "cavoid_crowd.hip"),
-           os.path.join(CSRC, "cavoid_policy_ws.hip"), os.path.join(CSRC, "cavoid_policy_train_ring.hip")]
+           os.path.join(CSRC, "cavoid_policy_ws.hip"), os.path.join(CSRC, "cavoid_policy_train_ring.hip"),
+           os.path.join(CSRC, "cavoid_policy_wsring.hip")]
 HEADERS = {
     "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp"],
     "cavoid_multistep.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
@@ -33,6 +34,8 @@ HEADERS = {
                                 "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
     "cavoid_comm_capi.hip": ["cavoid_host.hpp"],
     "cavoid_crowd.hip": ["cavoid_kernels.hpp", "cavoid_crowd.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
+    "cavoid_policy_wsring.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp",
+                                 "cavoid_host.hpp"],
     "cavoid_policy_ws.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
 }
 # per-file extra flags.  The multi-step env kernels run their step loop inside the launch; MachineLICM would hoist every

@@ -27,7 +27,7 @@ struct cavoid_policy {
     int form = -1;                   // CAVOID_POLICY_FORM = quad (0) / oct (1) / duo (2) / unset (-1: duo from two tiles per CU on, else quad): the stand-alone inference
                                      // launch's tile-to-wavefront mapping (same results in every form)
     int num_cus = 256;
-    bool crowd = false;              // max_other > kPolMaxOthers: inference on policy_crowd_forward_kernel only (cavoid_policy_crowd.hpp)
+    bool crowd = false;              // max_other > kPolMaxOthers: inference on policy_crowd_forward_kernel only (cavoid_policy_crowd.hpp); with ws: the ring kernels of cavoid_policy_wsring.hpp
     bool ws = false;                 // MULTI_AGENT_ARCH 'weight_sharing' (cavoid_policy_create_ws): frags / bias hold the pack of cavoid_policy_ws.hpp
     bool use_split = true;           // CAVOID_POLICY_F32=1: run inference on the float32-MFMA kernel instead (A/B runs)
     float *bias = nullptr, *avg = nullptr, *std = nullptr;
@@ -44,6 +44,13 @@ int cavoid_policy_ws_launch(cavoid_policy *h, const cavoid::PolicyArgs &a, int64
 // policy_backward_kernel themselves.  _opt_in: the two ring kernels' dynamic LDS, at creation (on failure the handle is gone)
 int cavoid_policy_train_ring_opt_in(cavoid_policy *h);
 int cavoid_policy_train_ring_launch(cavoid_policy *h, const cavoid::PolicyArgs &a, unsigned blocks, int loss_kind, hipStream_t stream);
+
+// a cavoid_policy_create_ws_crowd handle (ws and crowd both set; cavoid_policy_wsring.hip): cavoid_policy_ws_launch and the trainer pass of
+// cavoid_policy_ws.hip route their forward launch there, then launch policy_ws_backward_kernel themselves.  _backward_opt_in
+// (cavoid_policy_ws.hip): that kernel's dynamic LDS, at creation (on failure the handle is gone)
+int cavoid_policy_wsring_launch(cavoid_policy *h, const cavoid::PolicyArgs &a, int64_t blocks, hipStream_t stream);
+int cavoid_policy_wsring_train_launch(cavoid_policy *h, const cavoid::PolicyArgs &a, float *f_in, unsigned blocks, int loss_kind, hipStream_t stream);
+int cavoid_policy_ws_backward_opt_in(cavoid_policy *h);
 
 // ---- creation -------------------------------------------------------------------------------------------------------------------
 // The handle of cavoid_policy_create / _create_ws, once the caller has checked the argument ranges: the device check, then one zeroed

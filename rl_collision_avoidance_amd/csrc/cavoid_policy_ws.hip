@@ -51,7 +51,13 @@ extern "C" int cavoid_policy_load_ws(cavoid_policy *h, const cavoid_policy_weigh
     return policy_finish_load(h, w, s);
 }
 
+int cavoid_policy_ws_backward_opt_in(cavoid_policy *h) {
+    const PolicyLdsOptIn kernels[] = {{reinterpret_cast<const void *>(policy_ws_backward_kernel), policy_lds_bytes(4)}};
+    return policy_opt_in_lds(h, kernels);
+}
+
 int cavoid_policy_ws_launch(cavoid_policy *h, const PolicyArgs &a, int64_t blocks, hipStream_t stream) {
+    if (h->crowd) return cavoid_policy_wsring_launch(h, a, blocks, stream);    // (20..64 slots: the input slots as a ring)
     const PolicyWsArgs wa{a, nullptr};
     hipLaunchKernelGGL((policy_ws_forward_kernel<false>), dim3((unsigned)blocks), dim3(256), policy_lds_bytes(4), stream, wa);
     HIP_TRY(hipGetLastError());
@@ -70,7 +76,9 @@ static int policy_train_ws(cavoid_policy *h, const float *x, int64_t rows, int64
     if (const int rc = policy_train_begin(h, x, rows, row_stride, y_r, a_idx, beta, log_epsilon, b, s, &wa.a, &blocks)) return rc;
     if (blocks == 0) return CAVOID_OK;
     wa.f_in = b->f_in;
-    if (loss_kind == kLossRegression) hipLaunchKernelGGL(policy_regression_ws_forward_kernel, dim3(blocks), dim3(256), policy_lds_bytes(4), s, wa);
+    if (h->crowd) {                                        // (the forward parks R slots of the row at a time: cavoid_policy_wsring.hpp)
+        if (const int rc = cavoid_policy_wsring_train_launch(h, wa.a, wa.f_in, blocks, loss_kind, s)) return rc;
+    } else if (loss_kind == kLossRegression) hipLaunchKernelGGL(policy_regression_ws_forward_kernel, dim3(blocks), dim3(256), policy_lds_bytes(4), s, wa);
     else hipLaunchKernelGGL((policy_ws_forward_kernel<true>), dim3(blocks), dim3(256), policy_lds_bytes(4), s, wa);
     HIP_TRY(hipGetLastError());
     PolicyWsBackArgs k{};

@@ -126,6 +126,7 @@ struct PolicyWsArgs {
     float *f_in;                       // [M, rows64, 8] filter inputs [xn_i | is_on_i] (TRAIN only)
 };
 
+#ifndef CAVOID_POLICY_WS_LAYOUT_ONLY  /* cavoid_policy_wsring.hip takes the layout and the argument struct above, and none of the kernels below */
 // The forward pass of one 64-row tile: policy_ws_forward_kernel<TRAIN> (LOSS = kLossA3C) and policy_regression_ws_forward_kernel
 // (TRAIN with LOSS = kLossRegression) are thin kernels over it.
 template <bool TRAIN, int LOSS>
@@ -351,5 +352,7 @@ __global__ void __launch_bounds__(256, 1) policy_ws_backward_kernel(const Policy
         if (lane < 16) atomicAdd(p.db + kBiasOther + col, bsum);
     }
 }
+
+#endif  /* CAVOID_POLICY_WS_LAYOUT_ONLY */
 
 }  // namespace cavoid

@@ -28,11 +28,17 @@ MAX_OTHERS_TRAIN = 64
 # the most observed neighbours the weight-sharing kernels carry, inference and trainer alike (kWsMaxOthers, cavoid_policy_ws.hpp --
 # tests/test_policy_ws_host.py holds the two equal): wider weight-sharing rows act and train through PyTorch
 MAX_OTHERS_WS = 19
+# ... and when asked to (FusedPolicy(ws_crowd=True), FusedA3CTrainer(ws_crowd=True)): rows above MAX_OTHERS_WS run the weight-sharing ring
+# kernels on a cavoid_policy_create_ws_crowd handle (kWsMaxOthersCrowd, cavoid_policy_wsring.hpp -- tests/test_policy_wsring_host.py holds the
+# two equal)
+MAX_OTHERS_WS_CROWD = 64
 
 class FusedPolicy(object):
     accepts_strided_obs = True          # BatchedRollout hands over the env's obs tensor itself, no slice copy
 
-    def __init__(self, net: NetworkVP_rnn, seed: int = 0, forget_bias: float = 1.0):
+    def __init__(self, net: NetworkVP_rnn, seed: int = 0, forget_bias: float = 1.0, ws_crowd: bool = False):
+        """``ws_crowd=True`` (opt-in) carries a 'weight_sharing' network of MAX_OTHERS_WS + 1 .. MAX_OTHERS_WS_CROWD observed neighbours on the
+        ring kernels of cavoid_policy_wsring.hpp; it changes nothing for a narrower one and is ignored for 'rnn'."""
         if net.arch not in ("rnn", "weight_sharing"):
             raise ValueError("FusedPolicy implements MULTI_AGENT_ARCH 'rnn' and 'weight_sharing', not %r" % (net.arch,))
         self.arch = net.arch
@@ -43,7 +49,8 @@ class FusedPolicy(object):
         self.num_actions, self.max_others, self.input_size = net.num_actions, net.max_others, net.input_size
         self.forget_bias = float(forget_bias)
         self.ws = self.arch == "weight_sharing"      # the weight-sharing kernels (cavoid_policy_create_ws): float32 MFMA, no split form
-        if self.ws and self.max_others > MAX_OTHERS_WS:
+        ws_crowd = bool(ws_crowd) and self.ws and MAX_OTHERS_WS < self.max_others <= MAX_OTHERS_WS_CROWD
+        if self.ws and self.max_others > MAX_OTHERS_WS and not ws_crowd:
             raise ValueError("FusedPolicy carries the weight_sharing network up to %d observed neighbours (kWsMaxOthers), the network "
                              "observes %d" % (MAX_OTHERS_WS, self.max_others))
         if self.max_others > MAX_OTHERS_INFERENCE:
@@ -51,8 +58,8 @@ class FusedPolicy(object):
         self.crowd = self.max_others > MAX_OTHERS      # the crowd handle: inference in float16 or bf16 pieces, the trainer pass on the ring kernels (include/cavoid.h)
         self._lib = _lib.lib()
         h = C.c_void_p()
-        create = self._lib.cavoid_policy_create_ws if self.ws else self._lib.cavoid_policy_create
-        _lib.check(create(self.max_others, self.num_actions, dev.index or 0, C.byref(h)), "cavoid_policy_create" + ("_ws" if self.ws else ""))
+        name = "cavoid_policy_create" + ("_ws_crowd" if ws_crowd else "_ws" if self.ws else "")
+        _lib.check(getattr(self._lib, name)(self.max_others, self.num_actions, dev.index or 0, C.byref(h)), name)
         self._h = h
         # the inference form is fixed at creation (CAVOID_POLICY_F32 / CAVOID_POLICY_PRODUCTS are read by cavoid_policy_create only)
         use_split, products = C.c_int32(), C.c_int32()
@@ -172,13 +179,24 @@ class FusedA3CTrainer(object):
     regression loss head (``cavoid_policy_train_regression``; tests/test_gpu_policy_regression.py).
     ``crowd=True`` (opt-in; the step's time against autograd: profiles/policy_crowd_train_timing.txt) accepts an 'rnn' network of MAX_OTHERS + 1 .. MAX_OTHERS_TRAIN observed
     neighbours: the same two calls on a crowd handle, whose forward launch is the ring kernel of cavoid_policy_train_ring.hpp
-    (tests/test_gpu_policy_train_ring.py).  Mind ``scratch_bytes``: the pass keeps 3 360 bytes per buffer row and observed neighbour."""
+    (tests/test_gpu_policy_train_ring.py).  Mind ``scratch_bytes``: the pass keeps 3 360 bytes per buffer row and observed neighbour.
+    ``ws_crowd=True`` (opt-in; profiles/policy_wsring_timing.txt) does the same for a 'weight_sharing' network of MAX_OTHERS_WS + 1 ..
+    MAX_OTHERS_WS_CROWD neighbours: ``cavoid_policy_train_ws`` on a ``FusedPolicy(net, ws_crowd=True)``, whose forward launch is the ring kernel
+    of cavoid_policy_wsring.hpp (tests/test_gpu_policy_wsring.py); a ``policy`` that is already such a one has the same effect.  544 bytes per
+    buffer row and neighbour."""
 
     def __init__(self, net: NetworkVP_rnn, policy: Optional[FusedPolicy] = None, learning_rate: float = 2e-5, group=None,
-                 distributed: Optional[bool] = None, crowd: bool = False):
+                 distributed: Optional[bool] = None, crowd: bool = False, ws_crowd: bool = False):
         from .network import A3CTrainer
-        self.ws = net.arch == "weight_sharing"          # cavoid_policy_train_ws (limit: FusedPolicy's MAX_OTHERS_WS)
+        self.ws = net.arch == "weight_sharing"          # cavoid_policy_train_ws (limit: FusedPolicy's MAX_OTHERS_WS, or _WS_CROWD)
         self.crowd = bool(crowd) and not self.ws and net.max_others > MAX_OTHERS
+        # a weight-sharing network above MAX_OTHERS_WS: when asked to, or when the policy handed over already runs the ring kernels
+        self.ws_crowd = (self.ws and MAX_OTHERS_WS < net.max_others <= MAX_OTHERS_WS_CROWD and
+                         (bool(ws_crowd) or (policy is not None and policy.ws and policy.crowd)))
+        if self.ws and net.max_others > MAX_OTHERS_WS and not self.ws_crowd:
+            raise ValueError("the fused trainer carries the weight_sharing network up to %d observed neighbours (kWsMaxOthers), and up to %d "
+                             "with ws_crowd=True; the network observes %d: train with A3CTrainer (autograd)"
+                             % (MAX_OTHERS_WS, MAX_OTHERS_WS_CROWD, net.max_others))
         if self.crowd and net.max_others > MAX_OTHERS_TRAIN:
             raise ValueError("the fused ring trainer carries up to %d observed neighbours (kPolMaxOthersTrain), the network observes %d: "
                              "train with A3CTrainer (autograd)" % (MAX_OTHERS_TRAIN, net.max_others))
@@ -186,7 +204,7 @@ class FusedA3CTrainer(object):
             raise ValueError("the fused trainer carries up to %d observed neighbours (kPolMaxOthers), the network observes %d: "
                              "train with A3CTrainer (autograd)" % (MAX_OTHERS, net.max_others))
         self.net = net
-        self.policy = policy if policy is not None else FusedPolicy(net)
+        self.policy = policy if policy is not None else FusedPolicy(net, ws_crowd=self.ws_crowd)
         self._base = A3CTrainer(net, learning_rate=learning_rate, group=group, distributed=distributed)
         self.opt = self._base.opt
         self.device = self.policy.device
@@ -241,7 +259,7 @@ class FusedA3CTrainer(object):
             for k, v in t.items():
                 setattr(c, k, C.c_void_p(v.data_ptr()))
             b = self._buffers[rows64] = (t, c)
-            if len(self._buffers) > (2 if self.crowd else 4):  # keep the cache small: minibatch size + a remainder or two (crowd rows: GBs each)
+            if len(self._buffers) > (2 if self.crowd or self.ws_crowd else 4):  # keep the cache small: minibatch size + a remainder or two (crowd rows: GBs each)
                 self._buffers.pop(next(iter(self._buffers)))
         return b
 

@@ -1,0 +1,101 @@
+"""CPU tests of the weight-sharing ring kernels' host side (cavoid_policy_wsring.hpp / cavoid_policy_wsring.hip): the new C call is
+declared in plain C and exported, cavoid_policy_create_ws_crowd tells the range it carries from the ranges it refuses before it looks for
+a device, the Python limit mirrors the kernel's, the built library holds the three ring kernels without scratch, the training CLI knows its
+flag, and the scratch figure it prints is the buffers' own."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+from tests.test_crowd_host import LLVM, ROOT, _kernel_notes, _no_gpu
+
+HEADER = os.path.join(ROOT, "include", "cavoid.h")
+CSRC = os.path.join(ROOT, "rl_collision_avoidance_amd", "csrc")
+
+
+def test_create_ws_crowd_is_declared_in_plain_c_and_exported():
+    text = open(HEADER).read()
+    assert re.search(r"\bint\s+cavoid_policy_create_ws_crowd\s*\(", text)
+    assert re.search(r"#define\s+CAVOID_ABI_VERSION\s+3\b", text)                 # additive: the version stays
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if cc:                                        # the header still compiles as C (no C++ crept in)
+        work = tempfile.mkdtemp(prefix="cavoid_hdr_")
+        try:
+            src = os.path.join(work, "t.c")
+            with open(src, "w") as f:
+                f.write('#include "cavoid.h"\nint main(void) { cavoid_policy_train_ws_buffers b; (void)b; '
+                        'return (int)sizeof(&cavoid_policy_create_ws_crowd); }\n')
+            subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-I" + os.path.dirname(HEADER), "-c", src, "-o",
+                            os.path.join(work, "t.o")], check=True)
+        finally:
+            shutil.rmtree(work, ignore_errors=True)
+    from rl_collision_avoidance_amd import _lib
+    assert hasattr(_lib.lib(), "cavoid_policy_create_ws_crowd")
+    assert any(name == "cavoid_policy_create_ws_crowd" for name, _, _ in _lib.SYMBOLS)
+
+
+@pytest.mark.parametrize("m,actions,code", [(20, 11, -5), (38, 11, -5), (64, 11, -5), (1, 11, -4), (19, 11, -4), (0, 11, -1), (65, 11, -1),
+                                            (31, 16, -1), (31, 0, -1)])
+def test_create_ws_crowd_range_is_checked_before_the_device(m, actions, code):
+    _no_gpu()
+    from rl_collision_avoidance_amd import _lib
+    h = C.c_void_p()
+    assert _lib.lib().cavoid_policy_create_ws_crowd(m, actions, 0, C.byref(h)) == code      # -5 ENODEVICE, -4 EUNSUPPORTED, -1 EINVAL
+    assert not h.value
+
+
+def test_ws_crowd_neighbour_limit_mirrors_the_kernel():
+    from rl_collision_avoidance_amd.ga3c.policy_kernel import MAX_OTHERS_INFERENCE, MAX_OTHERS_WS, MAX_OTHERS_WS_CROWD
+    src = open(os.path.join(CSRC, "cavoid_policy_wsring.hpp")).read()
+    m = re.search(r"constexpr\s+int\s+kWsMaxOthersCrowd\s*=\s*(\d+)\s*;", src)
+    assert m and int(m.group(1)) == MAX_OTHERS_WS_CROWD == 64
+    assert re.search(r"constexpr\s+int\s+kWsRing\s*=\s*kWsMaxOthers\s*;", src)
+    assert MAX_OTHERS_WS == 19 and MAX_OTHERS_WS_CROWD <= MAX_OTHERS_INFERENCE
+
+
+@pytest.mark.skipif(not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))),
+                    reason="llvm-objdump / llvm-readelf of the ROCm toolchain not present")
+def test_wsring_kernels_exist_and_use_no_scratch():
+    text = _kernel_notes()
+    found = dict(re.findall(r"\.name:\s+(\S*policy_wsring_\S*kernel\S*)\s*\n\s*\.private_segment_fixed_size:\s+(\d+)", text))
+    assert len(found) == 3, found            # inference forward, trainer forward, the supervised start's forward
+    assert sum("policy_wsring_forward_kernel" in k for k in found) == 2 and sum("policy_wsring_regression_kernel" in k for k in found) == 1
+    assert all(int(size) == 0 for size in found.values()), found
+    # the names stay clear of the substrings other tests count kernels by
+    for k in found:
+        assert not re.search(r"policy_ws_\S*kernel|policy_regression_\S*kernel|policy_train_ring_\w+_kernel|policy_crowd_forward_kernel|crowd_kernel", k), k
+
+
+def test_train_cli_knows_the_flag(monkeypatch):
+    """the parser accepts --fused-crowd-ws (off by default); parsing stops before anything touches a device"""
+    import argparse
+    from rl_collision_avoidance_amd.ga3c import train
+    seen = {}
+
+    class Stop(Exception):
+        pass
+
+    def parse(self, argv=None):
+        seen["args"] = argparse.ArgumentParser.parse_known_args(self, argv)[0]
+        raise Stop()
+    monkeypatch.setattr(argparse.ArgumentParser, "parse_args", parse)
+    for argv, want in ((["--fused-crowd-ws"], True), ([], False)):
+        with pytest.raises(Stop):
+            train.main(argv)
+        assert seen["args"].fused_crowd_ws is want and seen["args"].fused_crowd_trainer is False
+    monkeypatch.undo()
+    with pytest.raises(SystemExit):                          # (an unknown flag is still an error)
+        train.main(["--fused-crowd-ws-typo"])
+
+
+def test_ws_scratch_bytes():
+    from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedA3CTrainer
+    # per buffer row z1..z3 g1..g3 gh l1_in (host columns), per row and neighbour l1_in's 64 filter outputs, f_in, gf (float32)
+    per_row = lambda M: 4 * (6 * 256 + 16 + 4) + 4 * M * (64 + 8 + 64)
+    assert FusedA3CTrainer.scratch_bytes(63, 2048, arch="weight_sharing") == 2048 * per_row(63) == 2048 * (6224 + 544 * 63)
+    assert FusedA3CTrainer.scratch_bytes(23, 2048, arch="weight_sharing") == 2048 * per_row(23)
+    assert FusedA3CTrainer.scratch_bytes(64, 16384, arch="weight_sharing") == 16384 * per_row(64)

@@ -1,6 +1,7 @@
 """Time the fused policy kernel against the PyTorch-ROCm graph of the same network (development aid).
 usage: python tools/polbench.py [rows] [max_other] [--arch rnn|weight_sharing]
-  (max_other 1..64: above 19 the rnn handle runs the crowd kernel, cavoid_policy_crowd.hpp; weight_sharing: 1..19, cavoid_policy_ws.hpp)
+  (max_other 1..64: above 19 the rnn handle runs the crowd kernel, cavoid_policy_crowd.hpp; weight_sharing: 1..19 on cavoid_policy_ws.hpp,
+   20..64 on the ring kernel of cavoid_policy_wsring.hpp, FusedPolicy(ws_crowd=True))
 Every row observes max_other agents.  fused_us: predict + sampled select_action (act); forward_us: predict only; torch_us: predict_p_and_v."""
 import argparse
 import os
@@ -11,7 +12,7 @@ import torch
 
 from rl_collision_avoidance_amd.config import EnvConfig
 from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
-from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
+from rl_collision_avoidance_amd.ga3c.policy_kernel import MAX_OTHERS_WS, FusedPolicy
 
 
 def main():
@@ -27,7 +28,7 @@ def main():
             self.MAX_NUM_AGENTS_IN_ENVIRONMENT = M + 1
             EnvConfig.__init__(self)
     net = NetworkVP_rnn(Cfg(), arch=args.arch).cuda()
-    pol = FusedPolicy(net)
+    pol = FusedPolicy(net, ws_crowd=M > MAX_OTHERS_WS)
     g = torch.Generator().manual_seed(0)
     x = (torch.randn((B, net.input_size), generator=g) * net.std.cpu() + net.avg.cpu())
     x[:, 0] = float(M)
@@ -54,7 +55,7 @@ def main():
         useful = B * 2 * ((7 + 64 * (M - 1) + 7 * (M - 1)) * 256 + 68 * 256 + 2 * 256 * 256 + 256 * 12)
     else:
         useful = B * 2 * (M * 8 * 64 + (4 + 64 * M) * 256 + 2 * 256 * 256 + 256 * 12)
-    form = "ws" if pol.ws else ("crowd" if pol.crowd else os.environ.get("CAVOID_POLICY_FORM", "quad"))
+    form = ("wsring" if pol.crowd else "ws") if pol.ws else ("crowd" if pol.crowd else os.environ.get("CAVOID_POLICY_FORM", "quad"))
     print({"form": form, "products": pol.inference_form[1], "rows": B, "max_other": M, "fused_us": round(t_fused, 1), "forward_us": round(t_forward, 1),
            "torch_us": round(t_torch, 1), "speedup_act": round(t_torch / t_fused, 2), "pack_us": round(t_load, 1),
            "issued_TFLOPs": round(flop / t_fused * 1e-6, 1), "useful_TFLOPs": round(useful / t_fused * 1e-6, 1),

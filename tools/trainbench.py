@@ -1,12 +1,14 @@
 """Time one trainer step of the fused trainer against the autograd trainer on the same rows, up to crowd rows (development aid).
-usage: python tools/trainbench.py [rows] [max_other ...] [--reps 10] [--rounds 3]
+usage: python tools/trainbench.py [rows] [max_other ...] [--reps 10] [--rounds 3] [--arch rnn|weight_sharing]
 For each max_other (default 19 31 63) at `rows` rows (default 16384): per round, the median of --reps HIP-event-timed steps after 5
 warm-up steps, alternating
   fused:    FusedA3CTrainer.train (launch pair -- above 19 observed neighbours the ring forward kernel, crowd=True -- weight-gradient GEMMs,
             Adam step, weight re-pack)
   autograd: A3CTrainer.train (NetworkVP_rnn.loss + backward + Adam step)
 (learning rate 0 on both sides: the weights stay put).  Row lengths are drawn uniformly from 0 .. max_other.  The fused trainer's scratch is
-printed with each line (FusedA3CTrainer.scratch_bytes).  Figures go to profiles/policy_crowd_train_timing.txt."""
+printed with each line (FusedA3CTrainer.scratch_bytes).  Figures go to profiles/policy_crowd_train_timing.txt.
+--arch weight_sharing: the same for the weight-sharing network -- above 19 observed neighbours the ring forward kernel of
+cavoid_policy_wsring.hpp, ws_crowd=True; figures go to profiles/policy_wsring_timing.txt."""
 import argparse
 import os
 import statistics
@@ -17,7 +19,7 @@ import torch
 
 from rl_collision_avoidance_amd.config import EnvConfig
 from rl_collision_avoidance_amd.ga3c.network import A3CTrainer, NetworkVP_rnn
-from rl_collision_avoidance_amd.ga3c.policy_kernel import MAX_OTHERS, FusedA3CTrainer
+from rl_collision_avoidance_amd.ga3c.policy_kernel import MAX_OTHERS, MAX_OTHERS_WS, FusedA3CTrainer
 
 
 def median_us(fn, reps):
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("max_other", type=int, nargs="*", default=[19, 31, 63])
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--arch", default="rnn", choices=["rnn", "weight_sharing"])
     args = ap.parse_args()
     B = args.rows
     print("M   rows    scratch (GB)  fused step (us)                autograd step (us)             autograd / fused")
@@ -49,20 +52,23 @@ def main():
             def __init__(self):
                 self.MAX_NUM_AGENTS_IN_ENVIRONMENT = M + 1
                 EnvConfig.__init__(self)
-        net_f = NetworkVP_rnn(Cfg()).cuda()
-        net_a = NetworkVP_rnn(Cfg()).cuda()
+        net_f = NetworkVP_rnn(Cfg(), arch=args.arch).cuda()
+        net_a = NetworkVP_rnn(Cfg(), arch=args.arch).cuda()
         g = torch.Generator().manual_seed(0)
         x = torch.randn((B, net_f.input_size), generator=g) * net_f.std.cpu() + net_f.avg.cpu()
         x[:, 0] = torch.randint(0, M + 1, (B,), generator=g).float()
         x, y, a = x.cuda(), torch.randn(B, generator=g).cuda(), torch.randint(0, net_f.num_actions, (B,), generator=g).cuda()
         onehot = torch.nn.functional.one_hot(a, net_f.num_actions).float()
-        tf = FusedA3CTrainer(net_f, learning_rate=0.0, crowd=M > MAX_OTHERS)
+        if args.arch == "weight_sharing":
+            tf = FusedA3CTrainer(net_f, learning_rate=0.0, ws_crowd=M > MAX_OTHERS_WS)
+        else:
+            tf = FusedA3CTrainer(net_f, learning_rate=0.0, crowd=M > MAX_OTHERS)
         ta = A3CTrainer(net_a, learning_rate=0.0)
         t_f, t_a = [], []
         for _ in range(args.rounds):
             t_f.append(median_us(lambda: tf.train(x, y, a), args.reps))
             t_a.append(median_us(lambda: ta.train(x, y, onehot), args.reps))
-        print("%-3d %-7d %-13.2f %-30s %-30s %.2fx" % (M, B, FusedA3CTrainer.scratch_bytes(M, FusedA3CTrainer.buffer_rows(B)) / 1e9,
+        print("%-3d %-7d %-13.2f %-30s %-30s %.2fx" % (M, B, FusedA3CTrainer.scratch_bytes(M, FusedA3CTrainer.buffer_rows(B), arch=args.arch) / 1e9,
                                                        " ".join("%.0f" % t for t in t_f), " ".join("%.0f" % t for t in t_a),
                                                        statistics.median(t_a) / statistics.median(t_f)), flush=True)
         del tf, ta, net_f, net_a
