@@ -56,7 +56,7 @@ extern "C" {
  * CAVOID_FORM_CROWD (the lanes of a world are its agents; a wavefront owns floor(64/N) whole worlds: three of 17..21 agents,
  * two of 22..32, one of 33..64).
  * What stops at 16 agents (CAVOID_EUNSUPPORTED for max_agents > 16): rvo_enabled and gen_lookahead > 0 (checked by
- * cavoid_create), cavoid_actor_run, cavoid_actor_run_mix and cavoid_step_push (use the env step + cavoid_rollout_push). */
+ * cavoid_create), cavoid_actor_run and cavoid_actor_run_mix (use cavoid_step_push, or the env step + cavoid_rollout_push). */
 #define CAVOID_MAX_AGENTS 64
 
 /* agent flag bits */
@@ -218,7 +218,8 @@ int cavoid_step_autoreset_n(cavoid_env *env, const int32_t *actions, int64_t act
  * C oracle indexes the table without a clamp. */
 
 /* which kernel form the last stepping launch of this handle ran (cavoid_step, _packed, _continuous and every
- * cavoid_step*_autoreset* entry point; reset and observe leave it alone, cavoid_step_push and the actor do not report here).
+ * cavoid_step*_autoreset* entry point; reset and observe leave it alone, the actor does not report here and cavoid_step_push only
+ * on an env of more than 16 agents per world: CAVOID_FORM_CROWD).
  * Several forms carry the same call and a form that does not carry a configuration hands it to the next one; all of them are
  * bit-identical to CAVOID_FORM_STEP.  relay_consumers (may be NULL) receives the
  * observation wavefronts per tile the relay launch really used (the launcher lowers CAVOID_RELAY_CONSUMERS until the LDS fits),
@@ -394,6 +395,8 @@ int cavoid_actor_run_mix(cavoid_env *env, cavoid_policy *policy, cavoid_policy *
  * a caller-supplied policy).  obs_cur [W,N,1+D]: the observation `actions` / `values` (V(s_t)) were computed on; the step writes the
  * next one into obs_next (a different buffer) and rewards / done / game_over; buffers: the experience store of cavoid_rollout_push;
  * step as there (< 0: the handle's device-side counter, advanced by the call).  Bit-identical to the two calls it replaces.
+ * Worlds of 17..64 agents run the crowd form's kernel of the same kind (one workgroup of two wavefronts per tile: the env step and the
+ * bookkeeping on one, the copy of the step's state rows on the other) and report CAVOID_FORM_CROWD to cavoid_last_step_form.
  * CAVOID_EUNSUPPORTED: holonomic dynamics. */
 int cavoid_step_push(cavoid_env *env, cavoid_rollout *rollout, const cavoid_rollout_buffers *buffers, const float *obs_cur, float *obs_next,
                      const int32_t *actions, const float *values, float *rewards, uint8_t *done, uint8_t *game_over, int32_t step, void *stream);

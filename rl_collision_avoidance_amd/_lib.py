@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("CAVOID_LIB", _DEFAULT_LIB_PATH)
 
 MAX_ACTIONS = 32
 MAX_AGENTS = 64
-TILE_MAX_AGENTS = 16      # more agents per world: the crowd form (CAVOID_FORM_CROWD); no fused actor / step_push, no ORCA, no look-ahead
+TILE_MAX_AGENTS = 16      # more agents per world: the crowd form (CAVOID_FORM_CROWD); no fused actor, no ORCA, no look-ahead (step_push: its own kernel, crowd_push_kernel)
 ABI_VERSION = 3
 
 F_AT_GOAL, F_RAN_OUT, F_IN_COLL, F_WAS_AT_GOAL, F_WAS_IN_COLL, F_PRESENT, F_LEARNING = 1, 2, 4, 8, 16, 32, 64

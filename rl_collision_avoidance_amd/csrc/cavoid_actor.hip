@@ -109,7 +109,6 @@ extern "C" int cavoid_step_push(cavoid_env *e, cavoid_rollout *r, const cavoid_r
         return CAVOID_EINVAL;
     if (r->device != e->device || r->c.num_slots != e->A || r->c.max_agents != e->cfg.max_agents || r->c.obs_width != e->k.width) return CAVOID_EINVAL;
     if (e->cfg.dynamics == CAVOID_DYN_HOLONOMIC) return CAVOID_EUNSUPPORTED;       // (velocity actions: cavoid_step_continuous + cavoid_rollout_push)
-    if (e->cfg.max_agents > kTileMaxAgents) return CAVOID_EUNSUPPORTED;   // (the crowd form: cavoid_step_autoreset + cavoid_rollout_push)
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc_a = cavoid_ahead_prepare(e, 1, s)) return rc_a;
@@ -124,7 +123,13 @@ extern "C" int cavoid_step_push(cavoid_env *e, cavoid_rollout *r, const cavoid_r
     io.obs[0] = const_cast<float *>(obs_cur); io.obs[1] = obs_next; io.rewards = rewards; io.done = done; io.game_over = game_over;
     io.actions = const_cast<int32_t *>(actions); io.values = const_cast<float *>(values); io.rollout_step = r->s.step_counter; io.n_steps = 1;
     const bool rvo_form = e->cfg.rvo_enabled || (e->cfg.gen_mode == 1 && e->pool_size <= 0);
-    const int rc_launch = rvo_form ? cavoid_launch_step_push_rvo(e, rc, r->s, rio, io, step, s) : launch_step_push_any<false>(e, rc, r->s, rio, io, step, s);
+    int rc_launch;
+    if (e->cfg.max_agents > kTileMaxAgents) {                // more than kTileMaxAgents agents per world: the crowd form's kernel (cavoid_crowd_push.hpp)
+        e->last_form = CAVOID_FORM_NONE;
+        rc_launch = note_form(e, cavoid_launch_crowd_push(e, rc, r->s, rio, io, step, s), CAVOID_FORM_CROWD);
+    } else {
+        rc_launch = rvo_form ? cavoid_launch_step_push_rvo(e, rc, r->s, rio, io, step, s) : launch_step_push_any<false>(e, rc, r->s, rio, io, step, s);
+    }
     if (rc_launch != CAVOID_OK) return rc_launch;
     if (step < 0) {                                          // the device-side step counter moves on (hipGraph replays)
         hipLaunchKernelGGL(actor_finish_kernel, dim3(1), dim3(1), 0, s, r->s.step_counter, static_cast<int32_t *>(nullptr), 1);

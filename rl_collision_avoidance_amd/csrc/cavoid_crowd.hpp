@@ -144,10 +144,11 @@ __device__ __forceinline__ bool crowd_rank(const uint64_t *keys, uint8_t *pos, i
 }
 
 // env_tile for a world of n agents (17..64; any n >= 2 in the development build that routes every N here).  NB: the bucket
-// (32 or 64) -- the generator's round count and the ranking's register block.
+// (32 or 64) -- the generator's round count and the ranking's register block.  out (may be null): the step's results of this lane's
+// agent, handed over in registers where env_tile hands them over (crowd_push_kernel, cavoid_crowd_push.hpp).
 template <int NB, int MODE>
 __device__ __forceinline__ void crowd_tile(const KCfg &c, const KState &s, const PoolRec *pool, const KIO &io, const int n, double *lds_tab,
-                                           float *wbase, const int lane, const int64_t wave) {
+                                           float *wbase, const int lane, const int64_t wave, StepOut *out = nullptr) {
     constexpr bool kAuto = MODE == MODE_STEP_AUTORESET_N;
     constexpr bool kLoop = MODE == MODE_STEP_AUTORESET_N;
     constexpr bool kStepping = MODE == MODE_STEP || kAuto;
@@ -353,6 +354,7 @@ __device__ __forceinline__ void crowd_tile(const KCfg &c, const KState &s, const
         const bool game_over = (running & wmask) == 0ull;
         rew_f = (float)r;
         done_f = done ? 1.0f : 0.0f;
+        if (out) { out->reward = rew_f; out->done = done; out->game_over = game_over; }
         if (active) {
             if (!packed) {
                 io.rew[slot_w * n + a_idx] = rew_f;
@@ -386,6 +388,7 @@ __device__ __forceinline__ void crowd_tile(const KCfg &c, const KState &s, const
         }
     }
 
+    if (out) out->learning_next = active && (a.flags & CAVOID_F_PRESENT) != 0u && (a.flags & CAVOID_F_LEARNING) != 0u;
     if (kStepping && !kLoop) write_back();
     // ---- mirrors env_tile's E9 (assemble_obs): ranks, then the rows in passes of c.tile_rows ----------------------------------------
     if (io.obs) {

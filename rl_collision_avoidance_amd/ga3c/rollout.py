@@ -25,6 +25,17 @@ from .policy_kernel import MAX_OTHERS as POLICY_MAX_OTHERS
 Policy = Callable[[torch.Tensor], Tuple[torch.Tensor, torch.Tensor]]   # x[B, D] -> (p[B, A], v[B])
 
 
+def step_path(agents_per_world: int, dynamics: int, fuse_env_push: bool) -> str:
+    """Which launches ``BatchedRollout.step`` takes for env.step + Experience bookkeeping: ``"step_push"`` (ONE launch,
+    ``cavoid_step_push``: ``step_push_kernel`` up to 16 agents per world, ``crowd_push_kernel`` for 17..64) or
+    ``"env, push, episode log"`` (three).  The one launch carries table actions only (holonomic dynamics take velocities) and
+    ``CAVOID_FUSE_ENV_PUSH=0`` keeps the three.  The one launch is the default for crowd worlds as for tile worlds: it takes 0.56 to
+    0.64 of the three launches' time at 32 768 rows (tools/crowdpushbench.py, profiles/crowd_step_push_timing.txt)."""
+    if not 1 <= int(agents_per_world) <= _lib.MAX_AGENTS:
+        raise ValueError("agents per world must be 1..%d" % _lib.MAX_AGENTS)
+    return "step_push" if fuse_env_push and int(dynamics) != 2 else "env, push, episode log"
+
+
 class TrainingBatch(object):
     """Rows that became final since the last drain: ``x`` f32 [n, D], ``r`` f32 [n] (n-step returns),
     ``a_index`` int32 [n], ``src`` int32 [n, 4] (world, agent, recorded-at step, emitted-at step)."""
@@ -181,7 +192,7 @@ class BatchedRollout(object):
         values = env._want(values, (env.num_worlds, env.max_agents), torch.float32, "values")
         nxt = self._obs_buffers[1 - self._cur]
         p = BatchedCollisionAvoidanceEnv._ptr
-        if self.fuse_env_push and env.cfg.dynamics != 2 and env.max_agents <= _lib.TILE_MAX_AGENTS:   # (cavoid_step_push stops at 16 agents)
+        if self.step_path == "step_push":
             # env.step + Experience bookkeeping as ONE launch (cavoid_step_push: the fused actor's env phase as a kernel of its own)
             _lib.check(self._lib.cavoid_step_push(self._h_env(), self._h, C.byref(self._actor_buffers()), p(obs), p(nxt), p(actions), p(values),
                                                   p(env.rewards), p(env.done), p(env.game_over), -1, env._stream()), "cavoid_step_push")
@@ -197,6 +208,11 @@ class BatchedRollout(object):
         self._cur = 1 - self._cur
         self.step_index += 1
         return rew, done, game_over
+
+    @property
+    def step_path(self) -> str:
+        """The launches ``step()`` takes for env.step + Experience bookkeeping (see the module's ``step_path``)."""
+        return step_path(self.env.max_agents, self.env.cfg.dynamics, self.fuse_env_push)
 
     # -- the fused actor: K closed-loop steps in ONE launch -------------------------------------------------------
     @property
