@@ -55,8 +55,11 @@ extern "C" {
 /* Agents per world: 1..64.  Worlds of up to 16 agents run the tile forms below; 17..64 agents run ONE form,
  * CAVOID_FORM_CROWD (the lanes of a world are its agents; a wavefront owns floor(64/N) whole worlds: three of 17..21 agents,
  * two of 22..32, one of 33..64).
- * What stops at 16 agents (CAVOID_EUNSUPPORTED for max_agents > 16): rvo_enabled and gen_lookahead > 0 (checked by
- * cavoid_create), cavoid_actor_run and cavoid_actor_run_mix (use cavoid_step_push, or the env step + cavoid_rollout_push). */
+ * What stops at 16 agents (CAVOID_EUNSUPPORTED for max_agents > 16): gen_lookahead > 0 and rvo_enabled = 1 (checked by
+ * cavoid_create), cavoid_actor_run and cavoid_actor_run_mix (use cavoid_step_push, or the env step + cavoid_rollout_push).
+ * ORCA agents in worlds of 17..64 agents: rvo_enabled = CAVOID_RVO_WAVE (the wavefront solves one agent's programme at a time, one
+ * lane per constraint line; stepping launches then report CAVOID_FORM_CROWD_RVO).  ORCA at EXACTLY 16 agents is not available in
+ * either form (the tile forms' line scratch ends at 15, the crowd form starts at 17): take max_agents = 17, gen_max_agents = 16. */
 #define CAVOID_MAX_AGENTS 64
 
 /* agent flag bits */
@@ -146,8 +149,10 @@ typedef struct cavoid_cfg {
     int32_t gen_mode;
     int32_t gen_box_large_from;   /* 5 */
     uint32_t gen_pool_epoch;      /* the pool holds generator worlds 0..P-1 of THIS episode index (cavoid_pool_refresh) */
-    int32_t rvo_enabled;          /* agents with policy 3 may exist: the step kernels reserve the ORCA scratch (4 KiB of LDS per
-                                     wavefront and neighbour; max_agents <= 15, else CAVOID_EUNSUPPORTED) */
+    int32_t rvo_enabled;          /* agents with policy 3 may exist.  Up to 15 agents per world any non-zero value selects the tile forms'
+                                     ORCA (a lane solves its own agent; 4 KiB of LDS per wavefront and neighbour for the lines, which is
+                                     why it ends at 15).  17..64 agents: CAVOID_RVO_WAVE only (the crowd form's wave-cooperative solve; no
+                                     LDS beyond the crowd form's own); 1 is refused there, and both at exactly 16: CAVOID_EUNSUPPORTED */
     double gen_rvo_fraction;      /* of the scripted agents: P(static) = gen_static_fraction, P(RVO) = this, P(frozen network) =
                                      gen_frozen_fraction, the rest non-cooperative */
     double gen_frozen_fraction;   /* policy 4 agents (their actions come from the caller: cavoid_policy_rows lists them) */
@@ -159,6 +164,9 @@ typedef struct cavoid_cfg {
     double rvo_radius_scale;      /* 1.05: the policy inflates every radius by 5 % */
     double rvo_max_delta_heading; /* pi/6: larger turns are clipped and taken standing still */
 } cavoid_cfg;
+
+/* values of cavoid_cfg.rvo_enabled */
+enum { CAVOID_RVO_OFF = 0, CAVOID_RVO_LANE = 1, CAVOID_RVO_WAVE = 2 };
 
 typedef struct cavoid_env cavoid_env;
 typedef struct cavoid_rollout cavoid_rollout;   /* (section 'rollout' below) */
@@ -219,7 +227,7 @@ int cavoid_step_autoreset_n(cavoid_env *env, const int32_t *actions, int64_t act
 
 /* which kernel form the last stepping launch of this handle ran (cavoid_step, _packed, _continuous and every
  * cavoid_step*_autoreset* entry point; reset and observe leave it alone, the actor does not report here and cavoid_step_push only
- * on an env of more than 16 agents per world: CAVOID_FORM_CROWD).
+ * on an env of more than 16 agents per world: CAVOID_FORM_CROWD, or CAVOID_FORM_CROWD_RVO where ORCA agents may exist).
  * Several forms carry the same call and a form that does not carry a configuration hands it to the next one; all of them are
  * bit-identical to CAVOID_FORM_STEP.  relay_consumers (may be NULL) receives the
  * observation wavefronts per tile the relay launch really used (the launcher lowers CAVOID_RELAY_CONSUMERS until the LDS fits),
@@ -233,7 +241,8 @@ enum {
     CAVOID_FORM_LOOP = 5,      /* env_kernel's in-launch step loop, restarts gathered on demand (MODE_STEP_AUTORESET_N) */
     CAVOID_FORM_PIPE = 6,      /* env_pipe_kernel: the step loop on two wavefronts per tile */
     CAVOID_FORM_RELAY = 7,     /* env_relay_kernel: the step loop cut into roles on 3 + relay_consumers wavefronts per tile */
-    CAVOID_FORM_CROWD = 8      /* crowd_kernel: every stepping mode of a world of 17..64 agents (one lane per agent, keys and ranks in LDS) */
+    CAVOID_FORM_CROWD = 8,     /* crowd_kernel: every stepping mode of a world of 17..64 agents (one lane per agent, keys and ranks in LDS) */
+    CAVOID_FORM_CROWD_RVO = 9  /* crowd_rvo_kernel: the same with ORCA agents solved by the whole wavefront (rvo_enabled = CAVOID_RVO_WAVE) */
 };
 int32_t cavoid_last_step_form(const cavoid_env *env, int32_t *relay_consumers);
 
@@ -396,7 +405,8 @@ int cavoid_actor_run_mix(cavoid_env *env, cavoid_policy *policy, cavoid_policy *
  * next one into obs_next (a different buffer) and rewards / done / game_over; buffers: the experience store of cavoid_rollout_push;
  * step as there (< 0: the handle's device-side counter, advanced by the call).  Bit-identical to the two calls it replaces.
  * Worlds of 17..64 agents run the crowd form's kernel of the same kind (one workgroup of two wavefronts per tile: the env step and the
- * bookkeeping on one, the copy of the step's state rows on the other) and report CAVOID_FORM_CROWD to cavoid_last_step_form.
+ * bookkeeping on one, the copy of the step's state rows on the other) and report CAVOID_FORM_CROWD to cavoid_last_step_form
+ * (CAVOID_FORM_CROWD_RVO with rvo_enabled = CAVOID_RVO_WAVE: the same launch over the ORCA-carrying env step).
  * CAVOID_EUNSUPPORTED: holonomic dynamics. */
 int cavoid_step_push(cavoid_env *env, cavoid_rollout *rollout, const cavoid_rollout_buffers *buffers, const float *obs_cur, float *obs_next,
                      const int32_t *actions, const float *values, float *rewards, uint8_t *done, uint8_t *game_over, int32_t step, void *stream);

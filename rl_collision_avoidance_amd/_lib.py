@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("CAVOID_LIB", _DEFAULT_LIB_PATH)
 
 MAX_ACTIONS = 32
 MAX_AGENTS = 64
-TILE_MAX_AGENTS = 16      # more agents per world: the crowd form (CAVOID_FORM_CROWD); no fused actor, no ORCA, no look-ahead (step_push: its own kernel, crowd_push_kernel)
+TILE_MAX_AGENTS = 16      # more agents per world: the crowd form (CAVOID_FORM_CROWD); no fused actor, no look-ahead (step_push: its own kernel, crowd_push_kernel)
+RVO_WAVE = 2              # cavoid_cfg.rvo_enabled above TILE_MAX_AGENTS agents per world: ORCA solved by the whole wavefront (CAVOID_FORM_CROWD_RVO)
 ABI_VERSION = 3
 
 F_AT_GOAL, F_RAN_OUT, F_IN_COLL, F_WAS_AT_GOAL, F_WAS_IN_COLL, F_PRESENT, F_LEARNING = 1, 2, 4, 8, 16, 32, 64
@@ -25,7 +26,7 @@ POLICY_EXTERNAL, POLICY_STATIC, POLICY_NONCOOP, POLICY_RVO, POLICY_FROZEN_NET = 
 F_DONE_MASK = 7
 COMM_FORCE_RCCL = 1
 # CAVOID_FORM_* (cavoid_last_step_form): the kernel form a stepping launch ran, by enum value
-STEP_FORMS = ("NONE", "STEP", "QUAD", "RVO", "LOOP_PF", "LOOP", "PIPE", "RELAY", "CROWD")
+STEP_FORMS = ("NONE", "STEP", "QUAD", "RVO", "LOOP_PF", "LOOP", "PIPE", "RELAY", "CROWD", "CROWD_RVO")
 
 
 class CavoidCfg(C.Structure):

@@ -54,7 +54,9 @@ def make_cfg(config: Optional[EnvConfig] = None, **overrides) -> _lib.CavoidCfg:
     cfg.gen_static_fraction = float(getattr(config, "SCRIPTED_STATIC_FRACTION", 0.5))
     cfg.gen_rvo_fraction = float(getattr(config, "SCRIPTED_RVO_FRACTION", 0.0))
     cfg.gen_frozen_fraction = float(getattr(config, "SCRIPTED_FROZEN_NET_FRACTION", 0.0))
-    cfg.rvo_enabled = 1 if cfg.gen_rvo_fraction > 0.0 and cfg.gen_nonlearning_fraction > 0.0 else 0
+    # ORCA agents: a lane solves its own agent in the tile forms (1); above 16 agents per world the crowd form's wavefront solves
+    # one agent at a time (2 = CAVOID_RVO_WAVE; cavoid_create refuses 1 there)
+    cfg.rvo_enabled = (_lib.RVO_WAVE if N > _lib.TILE_MAX_AGENTS else 1) if cfg.gen_rvo_fraction > 0.0 and cfg.gen_nonlearning_fraction > 0.0 else 0
     cfg.rvo_time_horizon = float(getattr(config, "RVO_TIME_HORIZON", 5.0))
     cfg.rvo_collab_coeff = float(getattr(config, "RVO_COLLAB_COEFF", 0.5))
     for key, val in overrides.items():

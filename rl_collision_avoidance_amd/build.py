@@ -15,9 +15,9 @@ SOURCES = [os.path.join(CSRC, "cavoid_capi.hip"), os.path.join(CSRC, "cavoid_mul
            os.path.join(CSRC, "cavoid_policy_capi.hip"), os.path.join(CSRC, "cavoid_comm_capi.hip"), os.path.join(CSRC, "cavoid_actor.hip"),
            os.path.join(CSRC, "cavoid_actor_rvo.hip"), os.path.join(CSRC, "cavoid_actor_frozen.hip"), os.path.join(CSRC, "cavoid_crowd.hip"),
            os.path.join(CSRC, "cavoid_policy_ws.hip"), os.path.join(CSRC, "cavoid_policy_train_ring.hip"),
-           os.path.join(CSRC, "cavoid_policy_wsring.hip"), os.path.join(CSRC, "cavoid_crowd_push.hip")]
+           os.path.join(CSRC, "cavoid_policy_wsring.hip"), os.path.join(CSRC, "cavoid_crowd_push.hip"), os.path.join(CSRC, "cavoid_crowd_rvo.hip")]
 HEADERS = {
-    "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp"],
+    "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp"],
     "cavoid_multistep.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
     "cavoid_rvo.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
     "cavoid_relay.hip": ["cavoid_kernels.hpp", "cavoid_relay.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
@@ -33,9 +33,11 @@ HEADERS = {
     "cavoid_actor_frozen.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
                                 "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
     "cavoid_comm_capi.hip": ["cavoid_host.hpp"],
-    "cavoid_crowd.hip": ["cavoid_kernels.hpp", "cavoid_crowd.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_push.hip": ["cavoid_crowd_push.hpp", "cavoid_crowd.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp",
-                              "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
+    "cavoid_crowd.hip": ["cavoid_kernels.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
+    "cavoid_crowd_push.hip": ["cavoid_crowd_push.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp",
+                              "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
+    "cavoid_crowd_rvo.hip": ["cavoid_crowd_push.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp",
+                             "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
     "cavoid_policy_wsring.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp",
                                  "cavoid_host.hpp"],
     "cavoid_policy_ws.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
@@ -52,7 +54,9 @@ EXTRA_FLAGS = {"cavoid_multistep.hip": ["-mllvm", "-disable-machine-licm"], "cav
                # the crowd form's step loop (cavoid_crowd.hpp): same reason
                "cavoid_crowd.hip": ["-mllvm", "-disable-machine-licm"],
                # crowd_push_kernel (cavoid_crowd_push.hpp) carries the same step loop
-               "cavoid_crowd_push.hip": ["-mllvm", "-disable-machine-licm"]}
+               "cavoid_crowd_push.hip": ["-mllvm", "-disable-machine-licm"],
+               # crowd_rvo_kernel / crowd_rvo_push_kernel (cavoid_crowd_rvo.hpp): the same step loop with the ORCA solve inside
+               "cavoid_crowd_rvo.hip": ["-mllvm", "-disable-machine-licm"]}
 STAMP_PATH = os.path.join(PKG_DIR, "libcavoid_hip.so.stamp")
 DEPS = SOURCES + [os.path.join(CSRC, h) for hs in HEADERS.values() for h in hs] + [os.path.join(ROOT, "include", "cavoid.h")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")
@@ -193,7 +197,8 @@ def build_ulp_fault(kind: int, verbose: bool = False) -> str:
 def build_crowd_dev(verbose: bool = False) -> str:
     """Development variant that routes EVERY agent count >= 2 to the crowd form (-DCAVOID_DEV_CROWD_FROM_N=2, dev-only N = 4, 10 for
     the tile forms): tests/test_gpu_crowd.py holds its outputs bitwise to the product's tile forms at N = 4 and 10 -- the guard on the
-    crowd kernel's copies of env_tile's statements.  Built like the ulp-fault variants; never loaded by the product."""
+    crowd kernel's copies of env_tile's statements -- and tests/test_gpu_crowd_rvo.py its wave-cooperative ORCA (rvo_enabled = 2 runs it
+    at every N >= 2 here) to the tile forms' lane-serial ORCA at N = 4, 10 and 15.  Built like the ulp-fault variants; never loaded by the product."""
     import glob
     from concurrent.futures import ThreadPoolExecutor
     out = variant_path("crowd2")
@@ -202,7 +207,7 @@ def build_crowd_dev(verbose: bool = False) -> str:
     build()
     objs = _compile_objects([], "", False, verbose)
     jobs, swap = [], {}
-    for name in ("cavoid_capi.hip", "cavoid_multistep.hip", "cavoid_crowd.hip"):     # (the units that route by agent count)
+    for name in ("cavoid_capi.hip", "cavoid_multistep.hip", "cavoid_crowd.hip", "cavoid_crowd_rvo.hip"):     # (the units that route by agent count)
         src = os.path.join(CSRC, name)
         obj = os.path.join(OBJ_DIR, name.replace(".hip", ".crowd2.o"))
         jobs.append([hipcc()] + FLAGS + EXTRA_FLAGS.get(name, []) + ["-DCAVOID_DEV_CROWD_FROM_N=2", "-DCAVOID_DEV_ONLY_N", "-c", src, "-o", obj])

@@ -126,7 +126,7 @@ extern "C" int cavoid_step_push(cavoid_env *e, cavoid_rollout *r, const cavoid_r
     int rc_launch;
     if (e->cfg.max_agents > kTileMaxAgents) {                // more than kTileMaxAgents agents per world: the crowd form's kernel (cavoid_crowd_push.hpp)
         e->last_form = CAVOID_FORM_NONE;
-        rc_launch = note_form(e, cavoid_launch_crowd_push(e, rc, r->s, rio, io, step, s), CAVOID_FORM_CROWD);
+        rc_launch = note_form(e, cavoid_launch_crowd_push(e, rc, r->s, rio, io, step, s), crowd_step_form(e));
     } else {
         rc_launch = rvo_form ? cavoid_launch_step_push_rvo(e, rc, r->s, rio, io, step, s) : launch_step_push_any<false>(e, rc, r->s, rio, io, step, s);
     }

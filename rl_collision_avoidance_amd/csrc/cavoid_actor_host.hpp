@@ -66,5 +66,7 @@ int cavoid_launch_actor_frozen(cavoid_env *e, const cavoid::SplitArgs &sa, const
                                const cavoid::RolloutState &rs, const cavoid::RolloutIO &rio, const cavoid::ActorIO &io, hipStream_t s);
 // cavoid_crowd_push.hip: crowd_push_kernel<NB> -- cavoid_step_push on an env of more than kTileMaxAgents agents per world (the crowd step form);
 // CAVOID_EUNSUPPORTED for a configuration the crowd form does not carry or whose LDS does not fit 64 KiB
+int cavoid_launch_crowd_rvo_push(cavoid_env *e, const cavoid::RolloutCfg &rc, const cavoid::RolloutState &rs, const cavoid::RolloutIO &rio,
+                                 const cavoid::ActorIO &io, int32_t step, hipStream_t s);   // (cavoid_crowd_rvo.hip: an env with rvo_enabled; cavoid_launch_crowd_push routes there)
 int cavoid_launch_crowd_push(cavoid_env *e, const cavoid::RolloutCfg &rc, const cavoid::RolloutState &rs, const cavoid::RolloutIO &rio,
                              const cavoid::ActorIO &io, int32_t step, hipStream_t s);

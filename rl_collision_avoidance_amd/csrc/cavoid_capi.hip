@@ -125,7 +125,10 @@ static int validate(const cavoid_cfg *c) {
     if (c->gen_frozen_fraction < 0.0 || c->gen_frozen_fraction > 1.0) return CAVOID_EINVAL;
     if (c->gen_rvo_fraction > 0.0 && !c->rvo_enabled) return CAVOID_EINVAL;    /* the generator would create agents the step cannot drive */
     if (c->rvo_enabled && !(c->rvo_time_horizon > 0.0 && c->rvo_radius_scale > 0.0)) return CAVOID_EINVAL;
-    if (crowd_form(c->max_agents) && (c->rvo_enabled || c->gen_lookahead > 0)) return CAVOID_EUNSUPPORTED;   /* (stop at kTileMaxAgents) */
+    /* what stops at kTileMaxAgents: the look-ahead, and ORCA solved lane by lane (the crowd form solves it wave-cooperatively: CAVOID_RVO_WAVE) */
+    if (crowd_form(c->max_agents) && ((c->rvo_enabled && c->rvo_enabled != CAVOID_RVO_WAVE) || c->gen_lookahead > 0)) return CAVOID_EUNSUPPORTED;
+    /* exactly kTileMaxAgents: the tile forms' line scratch does not fit a workgroup's LDS and the crowd form starts one above */
+    if (!crowd_form(c->max_agents) && c->max_agents >= kTileMaxAgents && c->rvo_enabled == CAVOID_RVO_WAVE) return CAVOID_EUNSUPPORTED;
     return CAVOID_OK;
 }
 
@@ -358,7 +361,7 @@ static int launch(cavoid_env *e, const KIO &io, hipStream_t s, hipEvent_t ev_sta
     if (stepping) e->last_form = CAVOID_FORM_NONE;
     if (crowd_form(e->cfg.max_agents)) {                  // more than kTileMaxAgents agents per world: the crowd form carries every mode
         const int rc = cavoid_launch_crowd(e, MODE, e->k, e->st, e->W, io, s, ev_start, ev_stop);
-        return stepping ? note_form(e, rc, CAVOID_FORM_CROWD) : rc;
+        return stepping ? note_form(e, rc, crowd_step_form(e)) : rc;
     }
     // the 'everything' instantiations (cavoid_rvo.hip): ORCA agents; box scenarios generated inside the auto-reset step
     if ((stepping && e->k.rvo_enabled) || (MODE == MODE_STEP_AUTORESET && e->k.gen_mode == 1 && e->k.pool_size <= 0))

@@ -31,7 +31,9 @@ static int launch_crowd_nb(const cavoid_env *e, int mode, const KCfg &k, const K
 int cavoid_launch_crowd(cavoid_env *e, int mode, const KCfg &k, const KState &st, int64_t worlds, const KIO &io, hipStream_t s,
                         hipEvent_t ev_start, hipEvent_t ev_stop) {
     const int n = e->cfg.max_agents;
-    if (n < 2 || n > CAVOID_MAX_AGENTS || k.rvo_enabled || k.ahead > 0) return CAVOID_EUNSUPPORTED;
+    // ORCA agents may exist: the stepping launches take the kernels that carry the wave-cooperative solve (cavoid_crowd_rvo.hip)
+    if (k.rvo_enabled && mode != MODE_OBSERVE && mode != MODE_RESET) return cavoid_launch_crowd_rvo(e, mode, k, st, worlds, io, s, ev_start, ev_stop);
+    if (n < 2 || n > CAVOID_MAX_AGENTS || k.ahead > 0) return CAVOID_EUNSUPPORTED;
     const int64_t waves = (worlds + k.wpw - 1) / k.wpw;
     if (waves < 1 || waves > 0x7fffffffLL) return CAVOID_EINVAL;
     const int ostride = io.obs ? io.obs_stride : k.width;

@@ -15,6 +15,7 @@
 // exact path.  Ranking counts, for every neighbour, the keys below its own (see crowd_rank).
 #pragma once
 #include "cavoid_kernels.hpp"
+#include "cavoid_crowd_rvo.hpp"
 
 namespace cavoid {
 
@@ -146,7 +147,10 @@ __device__ __forceinline__ bool crowd_rank(const uint64_t *keys, uint8_t *pos, i
 // env_tile for a world of n agents (17..64; any n >= 2 in the development build that routes every N here).  NB: the bucket
 // (32 or 64) -- the generator's round count and the ranking's register block.  out (may be null): the step's results of this lane's
 // agent, handed over in registers where env_tile hands them over (crowd_push_kernel, cavoid_crowd_push.hpp).
-template <int NB, int MODE>
+// RVO: the instantiation can drive policy-3 (ORCA) agents -- the wavefront solves one agent's programme at a time
+// (cavoid_crowd_rvo.hpp).  Instantiations of their own (crowd_rvo_kernel, cavoid_crowd_rvo.hip), as for env_tile: the programmes
+// inlined into the step cost every other configuration registers for code it never runs.
+template <int NB, int MODE, bool RVO = false>
 __device__ __forceinline__ void crowd_tile(const KCfg &c, const KState &s, const PoolRec *pool, const KIO &io, const int n, double *lds_tab,
                                            float *wbase, const int lane, const int64_t wave, StepOut *out = nullptr) {
     constexpr bool kAuto = MODE == MODE_STEP_AUTORESET_N;
@@ -199,7 +203,7 @@ __device__ __forceinline__ void crowd_tile(const KCfg &c, const KState &s, const
         }
         if (!fresh) {
             load_agent(s, a_idx, a);
-            if (!kStepping) a.speed = s.speed[a_idx];
+            if (!kStepping || RVO) a.speed = s.speed[a_idx];   // (ORCA agents read the others' last velocities)
         }
         if (kStepping) {
             if (io.cont) { act_next = __float_as_int(io.cont[2 * a_idx]); c1_next = io.cont[2 * a_idx + 1]; }
@@ -274,6 +278,20 @@ __device__ __forceinline__ void crowd_tile(const KCfg &c, const KState &s, const
                 a0 = (double)a.pref;
                 a1 = -e0.heading_ego;
             }
+        }
+        const bool orca = present_in && !done_in && pol == 3u;
+        if (RVO && CAVOID_RARE(__ballot(orca) != 0ull)) {        // ORCA agents in this tile
+            // ---- mirrors env_tile: the PRE-move state of every agent, in the box generator's scratch (idle here) ---------------
+            double sn, cs;
+            sincos_bounded(a.heading, &sn, &cs);
+            lds_px[lane] = a.px; lds_py[lane] = a.py;
+            lds_gx[lane] = present_in ? (double)a.speed * cs : 0.0;
+            lds_gy[lane] = present_in ? (double)a.speed * sn : 0.0;
+            lds_r[lane] = present_in ? a.radius : -1.0f;
+            wave_lds_sync();
+            // the lines of the agent being solved lie in the keys region: idle until the pair pass
+            crowd_rvo_actions<NB>(c, a, orca, n, lane, lds_px, lds_py, lds_gx, lds_gy, lds_r, reinterpret_cast<double *>(keys), a0, a1);
+            wave_lds_sync();
         }
         if (c.actions_fp32) { a0 = (double)(float)a0; a1 = (double)(float)a1; }
         // ---- mirrors env_tile: E5 dynamics -------------------------------------------------------------------------------------
@@ -500,6 +518,14 @@ __global__ void __launch_bounds__(64) crowd_kernel(const KCfg c, const KState s,
     double *lds_tab = reinterpret_cast<double *>(smem);
     float *wbase = reinterpret_cast<float *>(smem) + lds_floats_block();
     crowd_tile<NB, MODE>(c, s, pool, io, n, lds_tab, wbase, (int)threadIdx.x, (int64_t)blockIdx.x);
+}
+// ... and the stepping modes of an env whose worlds may hold ORCA agents (cavoid_crowd_rvo.hip)
+template <int NB, int MODE>
+__global__ void __launch_bounds__(64) crowd_rvo_kernel(const KCfg c, const KState s, const PoolRec *pool, const KIO io, const int n) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *lds_tab = reinterpret_cast<double *>(smem);
+    float *wbase = reinterpret_cast<float *>(smem) + lds_floats_block();
+    crowd_tile<NB, MODE, true>(c, s, pool, io, n, lds_tab, wbase, (int)threadIdx.x, (int64_t)blockIdx.x);
 }
 
 }  // namespace cavoid

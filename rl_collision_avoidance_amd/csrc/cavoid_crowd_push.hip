@@ -10,7 +10,8 @@ int cavoid_launch_crowd_push(cavoid_env *e, const RolloutCfg &rc, const RolloutS
                              hipStream_t s) {
     const KCfg &k = e->k;
     const int n = e->cfg.max_agents;
-    if (n < 2 || n > CAVOID_MAX_AGENTS || k.rvo_enabled || k.ahead > 0) return CAVOID_EUNSUPPORTED;     // (cavoid_launch_crowd's refusals)
+    if (k.rvo_enabled) return cavoid_launch_crowd_rvo_push(e, rc, rs, rio, io, step, s);                // (cavoid_crowd_rvo.hip)
+    if (n < 2 || n > CAVOID_MAX_AGENTS || k.ahead > 0) return CAVOID_EUNSUPPORTED;                      // (cavoid_launch_crowd's refusals)
     const int64_t tiles = (e->W + k.wpw - 1) / k.wpw;
     if (tiles < 1 || tiles > 0x7fffffffLL) return CAVOID_EINVAL;
     // one LDS allocation per workgroup, crowd_kernel's: only the env wavefront uses it

@@ -20,53 +20,62 @@
 
 namespace cavoid {
 
-template <int NB>
-__global__ void __launch_bounds__(128) crowd_push_kernel(const KCfg c, const KState s, const PoolRec *pool, const RolloutCfg rc, const RolloutState rs,
-                                                         const RolloutIO rio_arg, const ActorIO io, const int n, const int32_t step_arg) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
-    const int64_t tile = blockIdx.x;
-    const int32_t step = step_arg >= 0 ? step_arg : *io.rollout_step;
-    const int blk = step % rc.ring_len;
-    const int wpw = c.wpw, ow = c.width;
-    const int64_t w0 = tile * wpw;
-    const float *obs_t = io.obs[0];
-    if (wave_in_block == 1) {
-        // the step's state rows -> the time-major experience store (the rows are obs_cur, complete before the launch: nothing here depends
-        // on the env step wavefront 0 runs).  rollout_copy_rows' multiply-shift index is exact: at most 64 x 452 values < 2^16.
-        int64_t worlds_here = c.num_worlds - w0;
-        worlds_here = worlds_here > wpw ? wpw : (worlds_here < 0 ? 0 : worlds_here);
-        rollout_copy_rows<CAVOID_COPY_U>(rc, obs_t, rio_arg.x, w0 * n, (int)worlds_here * n, blk, lane, 64);
-        return;
+// The kernel's text, once for both env steps: crowd_tile<NB, MODE_STEP_AUTORESET_N, RVO> inside.  A macro and not a body function over RVO: the
+// function, inlined, gives crowd_push_kernel another instruction stream (operand order, register numbers) than the kernel written out, and the
+// kernels that exist keep theirs.
+#define CAVOID_CROWD_PUSH_KERNEL(KERNEL, RVO)                                                                                                      \
+    template <int NB>                                                                                                                              \
+    __global__ void __launch_bounds__(128) KERNEL(const KCfg c, const KState s, const PoolRec *pool, const RolloutCfg rc, const RolloutState rs,   \
+                                                  const RolloutIO rio_arg, const ActorIO io, const int n, const int32_t step_arg) {                \
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];                                                                       \
+        const int wave_in_block = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;                             \
+        const int64_t tile = blockIdx.x;                                                                                                           \
+        const int32_t step = step_arg >= 0 ? step_arg : *io.rollout_step;                                                                          \
+        const int blk = step % rc.ring_len;                                                                                                        \
+        const int wpw = c.wpw, ow = c.width;                                                                                                       \
+        const int64_t w0 = tile * wpw;                                                                                                             \
+        const float *obs_t = io.obs[0];                                                                                                            \
+        if (wave_in_block == 1) {                                                                                                                  \
+            /* the step's state rows -> the time-major experience store (the rows are obs_cur, complete before the launch: nothing here depends */ \
+            /* on the env step wavefront 0 runs).  rollout_copy_rows' multiply-shift index is exact: at most 64 x 452 values < 2^16. */            \
+            int64_t worlds_here = c.num_worlds - w0;                                                                                               \
+            worlds_here = worlds_here > wpw ? wpw : (worlds_here < 0 ? 0 : worlds_here);                                                           \
+            rollout_copy_rows<CAVOID_COPY_U>(rc, obs_t, rio_arg.x, w0 * n, (int)worlds_here * n, blk, lane, 64);                                   \
+            return;                                                                                                                                \
+        }                                                                                                                                          \
+        double *lds_tab = reinterpret_cast<double *>(smem);                                                                                        \
+        float *wbase = reinterpret_cast<float *>(smem) + lds_floats_block();                                                                       \
+        KIO k{};                                                                                                                                   \
+        k.actions = io.actions; k.obs = io.obs[1]; k.rew = io.rewards; k.done = io.done; k.game_over = io.game_over;                               \
+        k.obs_stride = ow; k.n_steps = 1;                        /* (out_step_stride = 0: the one step's outputs in slot 0) */                     \
+        StepOut so{0.0f, true, false, false};                                                                                                      \
+        const int lw = lane / n, i = lane - lw * n;                                                                                                \
+        const int64_t w = w0 + lw, a = w * n + i;                                                                                                  \
+        const bool in_range = lane < wpw * n && w < c.num_worlds;                                                                                  \
+        /* the bookkeeping's first trip to memory, issued in front of the env step (see actor_env_push_tile) */                                    \
+        const RolloutSlot slot_in = rollout_slot_load(rs, a, in_range);                                                                            \
+        float learn_f = 0.0f, value = 0.0f;                      /* is_learning of the state acted on (ProcessAgent.py:130) */                     \
+        int action = 0;                                                                                                                            \
+        if (in_range) { learn_f = obs_t[a * ow]; value = io.values[a]; action = io.actions[a]; }                                                   \
+        crowd_tile<NB, MODE_STEP_AUTORESET_N, RVO>(c, s, pool, k, n, lds_tab, wbase, lane, tile, &so);                                             \
+        const bool learning = in_range && learn_f > 0.5f;                                                                                          \
+        const int base = lane < wpw * n ? lw * n : 0;                                                                                              \
+        const uint64_t wbits = n >= 64 ? ~0ull : ((1ull << n) - 1ull);       /* (crowd_tile's form: a shift by 64 is undefined) */                 \
+        const int n_learning = __popcll(__ballot(learning) & (wbits << base));                                                                     \
+        RolloutIO rio = rio_arg;                                                                                                                   \
+        rollout_push_slot(rc, rs, rio, a, in_range ? w : 0, i, in_range, learning, n_learning, so.done, so.game_over, so.reward, value, action,    \
+                          step, blk, slot_in);                                                                                                     \
+        /* episode_log_q.put: the totals above were accumulated with atomics by this wavefront's own lanes -- drain them; */                       \
+        /* rollout_close_episode reads the sums at the cache the atomics went to */                                                                \
+        if (__ballot(in_range && so.game_over) != 0ull) {                                                                                          \
+            __builtin_amdgcn_s_waitcnt(0);                       /* (vmcnt 0: the atomics have been performed at the L2) */                        \
+            if (in_range && i == 0 && so.game_over) rollout_close_episode(rc, rs, rio, w);                                                         \
+        }                                                                                                                                          \
     }
-    double *lds_tab = reinterpret_cast<double *>(smem);
-    float *wbase = reinterpret_cast<float *>(smem) + lds_floats_block();
-    KIO k{};
-    k.actions = io.actions; k.obs = io.obs[1]; k.rew = io.rewards; k.done = io.done; k.game_over = io.game_over;
-    k.obs_stride = ow; k.n_steps = 1;                        // (out_step_stride = 0: the one step's outputs in slot 0)
-    StepOut so{0.0f, true, false, false};
-    const int lw = lane / n, i = lane - lw * n;
-    const int64_t w = w0 + lw, a = w * n + i;
-    const bool in_range = lane < wpw * n && w < c.num_worlds;
-    // the bookkeeping's first trip to memory, issued in front of the env step (see actor_env_push_tile)
-    const RolloutSlot slot_in = rollout_slot_load(rs, a, in_range);
-    float learn_f = 0.0f, value = 0.0f;                      // is_learning of the state acted on (ProcessAgent.py:130)
-    int action = 0;
-    if (in_range) { learn_f = obs_t[a * ow]; value = io.values[a]; action = io.actions[a]; }
-    crowd_tile<NB, MODE_STEP_AUTORESET_N>(c, s, pool, k, n, lds_tab, wbase, lane, tile, &so);
-    const bool learning = in_range && learn_f > 0.5f;
-    const int base = lane < wpw * n ? lw * n : 0;
-    const uint64_t wbits = n >= 64 ? ~0ull : ((1ull << n) - 1ull);       // (crowd_tile's form: a shift by 64 is undefined)
-    const int n_learning = __popcll(__ballot(learning) & (wbits << base));
-    RolloutIO rio = rio_arg;
-    rollout_push_slot(rc, rs, rio, a, in_range ? w : 0, i, in_range, learning, n_learning, so.done, so.game_over, so.reward, value, action,
-                      step, blk, slot_in);
-    // episode_log_q.put: the totals above were accumulated with atomics by this wavefront's own lanes -- drain them;
-    // rollout_close_episode reads the sums at the cache the atomics went to
-    if (__ballot(in_range && so.game_over) != 0ull) {
-        __builtin_amdgcn_s_waitcnt(0);                       // (vmcnt 0: the atomics have been performed at the L2)
-        if (in_range && i == 0 && so.game_over) rollout_close_episode(rc, rs, rio, w);
-    }
-}
+
+CAVOID_CROWD_PUSH_KERNEL(crowd_push_kernel, false)
+// the same launch for an env whose worlds may hold ORCA agents (cfg.rvo_enabled = CAVOID_RVO_WAVE; instantiated in cavoid_crowd_rvo.hip)
+CAVOID_CROWD_PUSH_KERNEL(crowd_rvo_push_kernel, true)
+#undef CAVOID_CROWD_PUSH_KERNEL
 
 }  // namespace cavoid

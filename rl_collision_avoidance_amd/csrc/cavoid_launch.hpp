@@ -172,6 +172,12 @@ int cavoid_launch_rvo(cavoid_env *e, int mode, const cavoid::KIO &io, hipStream_
 // pool fill) in ceil(worlds / k.wpw) one-wavefront workgroups; CAVOID_EUNSUPPORTED for a configuration the form does not carry
 int cavoid_launch_crowd(cavoid_env *e, int mode, const cavoid::KCfg &k, const cavoid::KState &st, int64_t worlds, const cavoid::KIO &io,
                         hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
+// the stepping modes of such an env with rvo_enabled (cavoid_crowd_rvo.hip: the kernels that carry the wave-cooperative ORCA solve);
+// cavoid_launch_crowd routes there
+int cavoid_launch_crowd_rvo(cavoid_env *e, int mode, const cavoid::KCfg &k, const cavoid::KState &st, int64_t worlds, const cavoid::KIO &io,
+                            hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
+// what a stepping launch of a crowd env reports to cavoid_last_step_form
+static inline int crowd_step_form(const cavoid_env *e) { return e->k.rvo_enabled ? CAVOID_FORM_CROWD_RVO : CAVOID_FORM_CROWD; }
 #ifdef CAVOID_TRACE
 // development build only: cavoid::set_trace of the env units other than cavoid_capi.hip (cavoid_debug_trace calls them all)
 int cavoid_debug_trace_multistep(unsigned long long *dev_ptr);

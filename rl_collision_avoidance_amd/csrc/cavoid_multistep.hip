@@ -9,7 +9,7 @@ using namespace cavoid;
 
 int cavoid_launch_multistep(cavoid_env *e, const KIO &io, bool prefetch, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     if (crowd_form(e->cfg.max_agents))                                  // more than kTileMaxAgents agents per world: the crowd form's step loop
-        return note_form(e, cavoid_launch_crowd(e, MODE_STEP_AUTORESET_N, e->k, e->st, e->W, io, s, ev_start, ev_stop), CAVOID_FORM_CROWD);
+        return note_form(e, cavoid_launch_crowd(e, MODE_STEP_AUTORESET_N, e->k, e->st, e->W, io, s, ev_start, ev_stop), crowd_step_form(e));
     if (e->k.rvo_enabled || (e->k.gen_mode == 1 && e->k.pool_size <= 0))       // ORCA agents / in-step box generator: cavoid_rvo.hip
         return cavoid_launch_rvo(e, prefetch ? MODE_STEP_AUTORESET_PF : MODE_STEP_AUTORESET_N, io, s, ev_start, ev_stop);
     // (continuous actions: the role-split and pipelined forms decode table actions only -- the single-wavefront loops carry them)

@@ -1,0 +1,107 @@
+#!/usr/bin/env python
+"""Which generator seeds the oracle cases of tests/test_gpu_crowd_rvo.py::test_crowd_orca_parity_with_the_oracle can take, decided by
+code: for every case and seed the test's own trajectory is run (env.step against the float64 oracle, tests/test_gpu_parity.py's
+_compare_step); at the first step that misses the bar every world that left the oracle goes through
+tests/replay.py::classify_divergence -- with env.step and the oracle's step in place of the auto-reset step, since the test steps
+without restarts, the oracle's states and actions of the last 32 steps as history (the drift test), and --trials sign patterns of the
++-1e-13 m perturbation (default 2000: the classifier's 63 are sized for worlds of 4 to 10 agents).  A seed is usable when the run passes
+all 120 steps and its coverage asserts hold; a seed may be passed over when every world that left the oracle is a tie.
+
+    python tools/crowd_rvo_seeds.py [--trials 2000] [seed ...]          (default: seeds 23 .. 32)"""
+import argparse
+import collections
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+
+import replay
+from oracle import c_oracle as co
+from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
+from rl_collision_avoidance_amd.config import EnvConfig
+from tests.test_gpu_crowd_rvo import _infeasible_first_programmes
+from tests.test_gpu_parity import _compare_step, _goal_seeking_actions, _pull, _push
+
+# (N, gen_min, nonlearning, static, rvo, scenario mode, W, time-outs expected): the test's table
+CASES = [(17, 17, .6, .2, .6, 1, 96, True), (20, 10, .6, .2, .6, 1, 96, True), (24, 24, .7, 0., 1., 0, 64, False), (33, 30, .5, .2, .6, 1, 48, True),
+         (64, 50, .5, .1, .8, 1, 24, True)]
+
+
+def run_case(case, seed, trials):
+    N, gen_min, nonl, static, rvo, mode, W, timeouts = case
+    kw = dict(gen_min_agents=gen_min, gen_nonlearning_fraction=nonl, gen_static_fraction=static, gen_rvo_fraction=rvo, rvo_enabled=2, gen_mode=mode,
+              gen_pool_size=0)
+
+    def make_env(num_worlds, world_offset=0):
+        class Cfg(EnvConfig):
+            def __init__(self):
+                self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
+                self.MAX_NUM_OTHER_AGENTS_OBSERVED = N - 1
+                EnvConfig.__init__(self)
+        e = BatchedCollisionAvoidanceEnv(num_worlds, Cfg(), device="cuda:0", seed=seed, world_offset=world_offset, **kw)
+        e.step_autoreset = e.step                              # (the classifier's replay steps the way the test does: no restarts)
+        return e
+    ocfg = co.default_cfg(N, N - 1)
+    ogen = co.default_gen(gen_min, N, nonl, static, mode=mode, rvo_fraction=rvo)
+    env = make_env(W)
+    env.reset()
+    st, ep = co.State.empty(W, N), np.zeros(W, np.uint32)
+    co.generate(ocfg, ogen, seed, st, ep)
+    _push(env, st)
+    orca = int(((st.flags >> 8) & 7 == 3).sum())
+    rng = np.random.default_rng(seed)
+    infeasible, failed, verdicts = 0, None, []
+    history = collections.deque(maxlen=32)
+    for t in range(120):
+        if t % 10 == 0:
+            infeasible += _infeasible_first_programmes(st, N)
+        acts = _goal_seeking_actions(rng, W, N)
+        a64, a32, afl = _pull(env)
+        st0, ep0 = st.copy(), ep.copy()
+        out = env.step(torch.from_numpy(acts).cuda())
+        oout = co.step(ocfg, st, acts)
+        try:
+            _compare_step(("seeds", N, seed, t), out, oout, env, st)
+        except AssertionError:
+            failed = t
+            f64, f32, fl = _pull(env)
+            d = replay.obs_diff(out[0].cpu().numpy(), oout[0])
+            bad = ((fl != st.flags).reshape(W, N).any(1) | (f32 != st.f32).reshape(5, W, N).any(axis=(0, 2)) |
+                   (np.abs(f64 - st.f64).reshape(4, W, N).max(axis=(0, 2)) > 1e-9) | (d.max(axis=(1, 2)) > 1e-5) |
+                   (np.abs(out[1].cpu().numpy() - oout[1]).max(axis=1) > 1e-5))
+            for w in np.flatnonzero(bad):
+                sl = slice(w * N, (w + 1) * N)
+                verdict, _ = replay.classify_divergence(make_env, ocfg, ogen, seed, N, int(w), (a64[:, sl], a32[:, sl], afl[sl], 0), st0, ep0, acts[None, w],
+                                                        trials=trials, history=list(history))
+                verdicts.append(verdict)
+                print("  N=%d seed=%d step %d world %d: %s; max |d float64 state| %.3g, max |d float32 state| %.3g, flags equal %s" % (
+                    N, seed, t, w, verdict, np.abs(f64[:, sl] - st.f64[:, sl]).max(), np.abs(f32[:, sl].astype(np.float64) - st.f32[:, sl]).max(),
+                    np.array_equal(fl[sl], st.flags[sl])), flush=True)
+            break
+        history.append((st0, ep0, acts[None]))
+    env.close()
+    if failed is not None:
+        return "leaves the bar at step %d: %s" % (failed, "may be passed over (ties only)" if verdicts and all(v == "tie" for v in verdicts) else "NOT a tie"), orca, infeasible
+    cover = bool(orca > 20 and infeasible >= 1 and (st.flags & 1 != 0).any() and (st.flags & 4 != 0).any() and ((st.flags & 2 != 0).any() or not timeouts))
+    return "passes 120 steps, coverage asserts %s" % ("hold: usable" if cover else "FAIL"), orca, infeasible
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--trials", type=int, default=2000)
+    ap.add_argument("seeds", type=int, nargs="*", default=list(range(23, 33)))
+    args = ap.parse_args()
+    # the classifier replays through step_autoreset on both sides; the test steps without restarts
+    replay.co.step_autoreset = lambda ocfg, ogen, seed, s, e, a, world_offset=0: co.step(ocfg, s, a)
+    for case in CASES:
+        for seed in args.seeds:
+            what, orca, infeasible = run_case(case, seed, args.trials)
+            print("N=%d seed=%d: %s; %d ORCA agents, %d sampled first programmes without a solution" % (case[0], seed, what, orca, infeasible), flush=True)
+
+
+if __name__ == "__main__":
+    main()
