@@ -399,6 +399,23 @@ int cavoid_actor_run_mix(cavoid_env *env, cavoid_policy *policy, cavoid_policy *
                          const cavoid_rollout_buffers *buffers, float *obs_cur, float *obs_next, float *rewards, uint8_t *done, uint8_t *game_over,
                          int32_t *actions, float *values, int32_t n_steps, int32_t greedy, void *stream);
 
+/* cavoid_actor_run for CROWD worlds (17..64 agents per world; cavoid_actor_run and _run_mix refuse them): the same closed loop, K steps in one
+ * launch, over the crowd step form -- per tile of floor(64/N) worlds (at most 64 rows: one policy tile) a workgroup runs cavoid_policy_forward's
+ * arithmetic on the tile's rows with the input slots used as a ring (rows of up to 63 observed agents), draws the actions, steps the tile's worlds
+ * (cavoid_step_push's crowd launch: env step + Experience bookkeeping + episode log) and copies the step's state rows into the experience store.
+ * Arguments, buffers, counters and the rule for the rows that need an action exactly as cavoid_actor_run; results are bit-identical to the
+ * step-by-step entry points (cavoid_rollout_active_rows, cavoid_policy_forward[_rows], cavoid_step_push).  With rvo_enabled = CAVOID_RVO_WAVE
+ * the launch runs over the ORCA-carrying env step; afterwards cavoid_last_step_form reports CAVOID_FORM_CROWD / CAVOID_FORM_CROWD_RVO as after
+ * cavoid_step_push.  `policy`: an LSTM handle (cavoid_policy_create) of the default inference form whose max_other is the env's, 1..63.
+ * CAVOID_EINVAL: null or mismatching handles and buffers (cavoid_actor_run's checks).  CAVOID_EUNSUPPORTED (use the step-by-step entry
+ * points): an env of <= 16 agents per world (cavoid_actor_run carries those), a weight-sharing handle, holonomic dynamics,
+ * CAVOID_POLICY_F32 / a non-default CAVOID_POLICY_PRODUCTS (the bf16 product form included), and an env whose generator makes frozen-network
+ * agents (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0: there is no _mix form of this launch; the refusal looks at the generator's
+ * fractions only, as cavoid_actor_run's).  n_steps == 0: CAVOID_OK, nothing is launched. */
+int cavoid_crowd_actor_run(cavoid_env *env, cavoid_policy *policy, cavoid_rollout *rollout, const cavoid_rollout_buffers *buffers,
+                           float *obs_cur, float *obs_next, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values,
+                           int32_t n_steps, int32_t greedy, void *stream);
+
 /* cavoid_step_autoreset + cavoid_rollout_push as ONE launch: the env step of every world and the Experience bookkeeping of its slots
  * (ProcessAgent.py:149-211) -- the fused actor's env phase for actors whose policy is a launch of its own (frozen-network agents,
  * a caller-supplied policy).  obs_cur [W,N,1+D]: the observation `actions` / `values` (V(s_t)) were computed on; the step writes the

@@ -15,7 +15,8 @@ SOURCES = [os.path.join(CSRC, "cavoid_capi.hip"), os.path.join(CSRC, "cavoid_mul
            os.path.join(CSRC, "cavoid_policy_capi.hip"), os.path.join(CSRC, "cavoid_comm_capi.hip"), os.path.join(CSRC, "cavoid_actor.hip"),
            os.path.join(CSRC, "cavoid_actor_rvo.hip"), os.path.join(CSRC, "cavoid_actor_frozen.hip"), os.path.join(CSRC, "cavoid_crowd.hip"),
            os.path.join(CSRC, "cavoid_policy_ws.hip"), os.path.join(CSRC, "cavoid_policy_train_ring.hip"),
-           os.path.join(CSRC, "cavoid_policy_wsring.hip"), os.path.join(CSRC, "cavoid_crowd_push.hip"), os.path.join(CSRC, "cavoid_crowd_rvo.hip")]
+           os.path.join(CSRC, "cavoid_policy_wsring.hip"), os.path.join(CSRC, "cavoid_crowd_push.hip"), os.path.join(CSRC, "cavoid_crowd_rvo.hip"),
+           os.path.join(CSRC, "cavoid_crowd_actor.hip")]
 HEADERS = {
     "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp"],
     "cavoid_multistep.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
@@ -38,6 +39,9 @@ HEADERS = {
                               "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
     "cavoid_crowd_rvo.hip": ["cavoid_crowd_push.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp",
                              "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
+    "cavoid_crowd_actor.hip": ["cavoid_crowd_actor.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp",
+                               "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp",
+                               "cavoid_host.hpp"],
     "cavoid_policy_wsring.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp",
                                  "cavoid_host.hpp"],
     "cavoid_policy_ws.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
@@ -56,7 +60,9 @@ EXTRA_FLAGS = {"cavoid_multistep.hip": ["-mllvm", "-disable-machine-licm"], "cav
                # crowd_push_kernel (cavoid_crowd_push.hpp) carries the same step loop
                "cavoid_crowd_push.hip": ["-mllvm", "-disable-machine-licm"],
                # crowd_rvo_kernel / crowd_rvo_push_kernel (cavoid_crowd_rvo.hpp): the same step loop with the ORCA solve inside
-               "cavoid_crowd_rvo.hip": ["-mllvm", "-disable-machine-licm"]}
+               "cavoid_crowd_rvo.hip": ["-mllvm", "-disable-machine-licm"],
+               # crowd_actor_kernel (cavoid_crowd_actor.hpp): policy + crowd env step + bookkeeping inside one step loop, as cavoid_actor.hip
+               "cavoid_crowd_actor.hip": ["-mllvm", "-disable-machine-licm"]}
 STAMP_PATH = os.path.join(PKG_DIR, "libcavoid_hip.so.stamp")
 DEPS = SOURCES + [os.path.join(CSRC, h) for hs in HEADERS.values() for h in hs] + [os.path.join(ROOT, "include", "cavoid.h")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")

@@ -98,6 +98,59 @@ extern "C" int cavoid_actor_run_mix(cavoid_env *e, cavoid_policy *h, cavoid_poli
     return actor_run(e, h, frozen, r, b, obs_cur, obs_next, rewards, done, game_over, actions, values, n_steps, greedy, stream);
 }
 
+// cavoid_actor_run for crowd worlds (17..64 agents per world): crowd_actor_kernel<NB, RVO> (cavoid_crowd_actor.hpp, launched by
+// cavoid_crowd_actor.hip) -- the ring form of the policy pass, the crowd env step and its bookkeeping per tile, K steps in one launch
+extern "C" int cavoid_crowd_actor_run(cavoid_env *e, cavoid_policy *h, cavoid_rollout *r, const cavoid_rollout_buffers *b, float *obs_cur, float *obs_next,
+                                      float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps,
+                                      int32_t greedy, void *stream) {
+    if (!e || !h || !r || !b || b->struct_size != (int32_t)sizeof(cavoid_rollout_buffers) || !obs_cur || !obs_next || obs_cur == obs_next ||
+        !rewards || !done || !game_over || !actions || !values || n_steps < 0)
+        return CAVOID_EINVAL;
+    if (!b->x || !b->val || !b->ret || !b->act || !b->emit_t || !b->dup_x || !b->dup_r || !b->dup_a || !b->dup_src || !b->dup_count ||
+        !b->ep_out || !b->ep_count || b->dup_capacity < 1 || b->ep_capacity < 1)
+        return CAVOID_EINVAL;
+    if (h->ws) return CAVOID_EUNSUPPORTED;                   // (the kernel embeds the LSTM pass: a weight-sharing handle acts step by step)
+    if (n_steps == 0) return CAVOID_OK;
+    if (!h->loaded) return CAVOID_EINVAL;
+    // the three handles must describe the same batch
+    if (h->device != e->device || r->device != e->device || r->c.num_slots != e->A || r->c.max_agents != e->cfg.max_agents ||
+        r->c.obs_width != e->k.width || h->in_size != e->k.width - 1 || h->max_other != e->cfg.max_other)
+        return CAVOID_EINVAL;
+    // what the kernel does not carry (the step-by-step entry points do): velocity actions, the float32-MFMA inference kernel or the bf16
+    // product form (it carries the default form of cavoid_policy_forward, so that both stay bit-identical); tile worlds have cavoid_actor_run
+    if (e->cfg.dynamics == CAVOID_DYN_HOLONOMIC || !h->use_split || h->split_products != kSpDefaultProducts) return CAVOID_EUNSUPPORTED;
+    if (e->cfg.max_agents <= kTileMaxAgents) return CAVOID_EUNSUPPORTED;
+    // frozen-network agents act by THEIR network, and this launch carries one (no _mix form): an env whose generator makes them acts step by step
+    if (e->cfg.gen_frozen_fraction > 0.0 && e->cfg.gen_nonlearning_fraction > 0.0) return CAVOID_EUNSUPPORTED;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc_a = cavoid_ahead_prepare(e, n_steps, s)) return rc_a;      // (as cavoid_step_push; the crowd form has no scenario look-ahead)
+    cavoid_ahead_consumed(e, n_steps);
+
+    PolicyArgs a{};
+    a.rows = e->A; a.stride = e->k.width; a.max_other = h->max_other; a.num_actions = h->num_actions; a.in_size = h->in_size;
+    a.avg = h->normalize ? h->avg : nullptr; a.std = h->normalize ? h->std : nullptr;
+    a.frags = h->frags; a.bias = h->bias; a.min_policy = h->min_policy;
+    a.seed_lo = (uint32_t)h->seed; a.seed_hi = (uint32_t)(h->seed >> 32);
+    a.step_counter = h->step_counter; a.blocks_done = h->blocks_done; a.cu_tickets = h->cu_tickets;
+    const SplitArgs sa{a, h->sfrags, h->sbias};
+    RolloutCfg rc = r->c;
+    rc.dup_capacity = b->dup_capacity; rc.ep_capacity = b->ep_capacity;
+    RolloutIO rio{};
+    rio.step = -1; rio.x = b->x; rio.val = b->val; rio.ret = b->ret; rio.act = b->act; rio.emit_t = b->emit_t;
+    rio.dup_x = b->dup_x; rio.dup_r = b->dup_r; rio.dup_a = b->dup_a; rio.dup_src = b->dup_src; rio.dup_count = b->dup_count;
+    rio.ep_out = b->ep_out; rio.ep_count = b->ep_count;
+    ActorIO io{};
+    io.obs[0] = obs_cur; io.obs[1] = obs_next; io.rewards = rewards; io.done = done; io.game_over = game_over;
+    io.actions = actions; io.values = values; io.rollout_step = r->s.step_counter; io.n_steps = n_steps; io.greedy = greedy ? 1 : 0;
+    e->last_form = CAVOID_FORM_NONE;
+    const int rc_launch = note_form(e, cavoid_launch_crowd_actor(e, sa, rc, r->s, rio, io, s), crowd_step_form(e));   // (reported as after cavoid_step_push)
+    if (rc_launch != CAVOID_OK) return rc_launch;
+    hipLaunchKernelGGL(actor_finish_kernel, dim3(1), dim3(1), 0, s, r->s.step_counter, h->step_counter, n_steps);
+    HIP_TRY(hipGetLastError());
+    return CAVOID_OK;
+}
+
 extern "C" int cavoid_step_push(cavoid_env *e, cavoid_rollout *r, const cavoid_rollout_buffers *b, const float *obs_cur, float *obs_next,
                                 const int32_t *actions, const float *values, float *rewards, uint8_t *done, uint8_t *game_over, int32_t step,
                                 void *stream) {

@@ -70,3 +70,7 @@ int cavoid_launch_crowd_rvo_push(cavoid_env *e, const cavoid::RolloutCfg &rc, co
                                  const cavoid::ActorIO &io, int32_t step, hipStream_t s);   // (cavoid_crowd_rvo.hip: an env with rvo_enabled; cavoid_launch_crowd_push routes there)
 int cavoid_launch_crowd_push(cavoid_env *e, const cavoid::RolloutCfg &rc, const cavoid::RolloutState &rs, const cavoid::RolloutIO &rio,
                              const cavoid::ActorIO &io, int32_t step, hipStream_t s);
+// cavoid_crowd_actor.hip: crowd_actor_kernel<NB, RVO> -- cavoid_crowd_actor_run's launch (the closed loop of crowd worlds; routes an env with
+// rvo_enabled to the ORCA-carrying instantiation); CAVOID_EUNSUPPORTED as cavoid_launch_crowd_push
+int cavoid_launch_crowd_actor(cavoid_env *e, const cavoid::SplitArgs &sa, const cavoid::RolloutCfg &rc, const cavoid::RolloutState &rs,
+                              const cavoid::RolloutIO &rio, const cavoid::ActorIO &io, hipStream_t s);

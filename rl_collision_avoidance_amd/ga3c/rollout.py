@@ -36,6 +36,32 @@ def step_path(agents_per_world: int, dynamics: int, fuse_env_push: bool) -> str:
     return "step_push" if fuse_env_push and int(dynamics) != 2 else "env, push, episode log"
 
 
+def crowd_actor_unavailable_reason(agents_per_world: int, dynamics: int, arch: str, inference_form, policy_max_others: int,
+                                   env_max_other: int, frozen_agents: bool, fused_policy: bool = True) -> Optional[str]:
+    """Why ``BatchedRollout.run_fused_crowd`` (``cavoid_crowd_actor_run``: the closed actor loop of crowd worlds, K steps in one launch)
+    does not apply -- None when it does.  A pure function of host values, the refusals of the C entry point in its order of interest:
+    worlds of 17..64 agents (tile worlds have ``run_fused``), a ``FusedPolicy`` of the ``rnn`` network on the default (float16-split)
+    inference form whose neighbour count is the env's, table actions, and no frozen-network agents (the launch carries one network)."""
+    n = int(agents_per_world)
+    if not 1 <= n <= _lib.MAX_AGENTS:
+        raise ValueError("agents per world must be 1..%d" % _lib.MAX_AGENTS)
+    if n <= _lib.TILE_MAX_AGENTS:
+        return "%d agents per world: up to %d run the tile forms' fused actor kernel (run_fused / cavoid_actor_run)" % (n, _lib.TILE_MAX_AGENTS)
+    if not fused_policy:
+        return "the policy is not a FusedPolicy"
+    if arch != "rnn":
+        return "the policy is the %s network (the crowd actor kernel embeds the LSTM pass; its kernel acts step by step)" % (arch,)
+    if int(dynamics) == 2:
+        return "holonomic (velocity) actions"
+    if tuple(inference_form) != ("split", 16):
+        return "the policy runs a non-default inference form %r (CAVOID_POLICY_F32 / CAVOID_POLICY_PRODUCTS at its creation)" % (tuple(inference_form),)
+    if int(policy_max_others) != int(env_max_other):
+        return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy_max_others), int(env_max_other))
+    if frozen_agents:
+        return "frozen-network agents (the crowd actor kernel carries one network: no _mix form)"
+    return None
+
+
 class TrainingBatch(object):
     """Rows that became final since the last drain: ``x`` f32 [n, D], ``r`` f32 [n] (n-step returns),
     ``a_index`` int32 [n], ``src`` int32 [n, 4] (world, agent, recorded-at step, emitted-at step)."""
@@ -319,6 +345,56 @@ class BatchedRollout(object):
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             self.run_fused(steps_per_graph)
+        self.step_index -= steps_per_graph                # capture records, it does not execute
+        self._graph_steps = steps_per_graph
+
+    # -- the fused actor of crowd worlds (17..64 agents): opt-in, beside the step-by-step path ---------------------------------
+    @property
+    def crowd_fused_unavailable_reason(self) -> Optional[str]:
+        """Why ``run_fused_crowd`` does not apply to this rollout (None: it does) -- ``crowd_actor_unavailable_reason`` on its values."""
+        cfg, pol = self.env.cfg, self.policy
+        return crowd_actor_unavailable_reason(
+            self.env.max_agents, cfg.dynamics, getattr(pol, "arch", "rnn"), getattr(pol, "inference_form", ("split", 16)),
+            getattr(pol, "max_others", -1), cfg.max_other,
+            self.frozen_policy is not None or (cfg.gen_frozen_fraction > 0.0 and cfg.gen_nonlearning_fraction > 0.0),
+            fused_policy=bool(getattr(pol, "accepts_strided_obs", False)))
+
+    @property
+    def crowd_fused_available(self) -> bool:
+        """``run_fused_crowd`` applies (``fused_available`` stays False for crowd worlds: the default paths do not change)."""
+        return self.crowd_fused_unavailable_reason is None
+
+    def run_fused_crowd(self, n_steps: int) -> None:
+        """``run_fused`` for crowd worlds: ``n_steps`` closed-loop steps of every world in ONE launch (``cavoid_crowd_actor_run``) -- per
+        tile of floor(64/N) worlds a workgroup runs the policy on its own rows (the ring form: up to 63 observed neighbours), steps its
+        worlds and records the step.  Bit-identical to ``n_steps`` calls of ``step()``; capturable into a hipGraph."""
+        why = self.crowd_fused_unavailable_reason
+        if why is not None:
+            raise RuntimeError("run_fused_crowd does not apply: " + why)
+        env, pol = self.env, self.policy
+        b = self._actor_buffers()
+        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
+        p = BatchedCollisionAvoidanceEnv._ptr
+        _lib.check(self._lib.cavoid_crowd_actor_run(env._h, pol._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done),
+                                                    p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps), 1 if self.greedy else 0,
+                                                    env._stream()), "cavoid_crowd_actor_run")
+        self._cur = (self._cur + int(n_steps)) & 1
+        self.step_index += int(n_steps)
+
+    def capture_fused_crowd(self, steps_per_graph: int = 4) -> None:
+        """``run_fused_crowd(steps_per_graph)`` as a one-node hipGraph, as ``capture_fused``: an even step count (the two observation
+        buffers alternate), two warm-up steps outside the capture; ``replay`` serves it."""
+        if steps_per_graph < 2 or steps_per_graph % 2:
+            raise ValueError("steps_per_graph must be a positive even number")
+        side = torch.cuda.Stream(device=self.env.device)
+        side.wait_stream(torch.cuda.current_stream(self.env.device))
+        with torch.cuda.stream(side):
+            self.run_fused_crowd(2)
+        torch.cuda.current_stream(self.env.device).wait_stream(side)
+        torch.cuda.synchronize(self.env.device)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self.run_fused_crowd(steps_per_graph)
         self.step_index -= steps_per_graph                # capture records, it does not execute
         self._graph_steps = steps_per_graph
 
