@@ -14,8 +14,9 @@ R_TOL = 1e-6      # n-step returns: float64 on both sides, emitted as float32
 # cavoid_cfg field -> OracleGen field
 _GEN = {"gen_min_agents": "min_agents", "gen_nonlearning_fraction": "nonlearning_fraction", "gen_static_fraction": "static_fraction",
         "gen_rvo_fraction": "rvo_fraction", "gen_frozen_fraction": "frozen_fraction", "gen_mode": "mode", "gen_pool_size": "pool_size",
-        "gen_goal_jitter": "goal_jitter", "gen_angle_jitter": "angle_jitter", "gen_min_trip": "min_trip"}
-_SKIP = {"rvo_enabled"}          # env-side resource switches the oracle has no use for
+        "gen_goal_jitter": "goal_jitter", "gen_angle_jitter": "angle_jitter", "gen_min_trip": "min_trip", "gen_box_small": "box_small",
+        "gen_box_large": "box_large", "gen_box_large_from": "box_large_from"}
+_SKIP = {"rvo_enabled", "gen_lookahead"}          # env-side resource switches the oracle has no use for (it generates every restart afresh)
 
 
 def oracle_for(N, M=None, pool=65536, **over):

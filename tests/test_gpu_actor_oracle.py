@@ -17,6 +17,7 @@ torch = pytest.importorskip("torch")
 
 import replay as rp
 from oracle import c_oracle as co
+from tests import cfg_regimes as R
 
 pytestmark = pytest.mark.gpu
 
@@ -65,6 +66,9 @@ def _make(W, N, seed, reflush, greedy, ring_len, **over):
      dict(gen_min_agents=2, gen_nonlearning_fraction=0.6, gen_static_fraction=0.2, gen_frozen_fraction=0.6)),
     # PLAY_MODE (argmax), in-kernel ring generator, ragged last tile
     (3, 130, False, True, (5, 16, 16, 16, 16, 16, 11), dict(gen_pool_size=0, gen_min_agents=2)),
+    # every numeric field of the step and of the ring generator off its default, the max-turn dynamics on a table that reaches the clamp
+    # (tests/cfg_regimes.py: UNCLIPPED + RING; tests/test_cfg_regimes_host.py holds the configuration to its conditions over as many steps)
+    (4, 256, False, False, (4, 16, 16, 16, 16, 16, 8), R.BY_ID["actor-unclipped-ring-4x256"].over),
 ])
 def test_fused_actor_against_the_oracles(N, W, reflush, greedy, launches, over):
     _check_fused_actor(N, W, reflush, greedy, launches, over)

@@ -3,7 +3,10 @@ a FINITE `sensing_horizon` (SENSING_HORIZON, run-ws/config.yaml:249-251 records 
 it, so the neighbour count, the clipping and the slot order all change) and a non-zero `reward_time_step` (REWARD_TIME_STEP,
 :326-328 -- the reward every step starts from).  HIP vs the float64 oracle through EVERY form the env step is launched in:
 one step per launch, the in-launch step loop as relay / two-wavefront pipeline / single wavefront with register prefetch /
-plain loop, the N = 10 loop, and the packed-record outputs."""
+plain loop, the N = 10 loop, and the packed-record outputs.
+
+And EVERY numeric field off its default at once (tests/cfg_regimes.py: CLIPPED / UNCLIPPED beside the RING and BOX generator sets), through
+the same forms; tests/test_cfg_regimes_host.py proves on the CPU that each field decides something within each case's steps."""
 import numpy as np
 import pytest
 
@@ -11,14 +14,13 @@ torch = pytest.importorskip("torch")
 
 import replay as rp
 from oracle import c_oracle as co
+from tests import cfg_regimes as R
+from tests.cfg_regimes import WIDE          # turns beyond max_turn_rate * dt (0.6 rad), straight ahead at index 2: the max-turn clamp really acts
 
 pytestmark = pytest.mark.gpu
 
 OBS_TOL, STATE_TOL = 1e-5, 1e-9
 FIELDS = dict(sensing_horizon=3.0, reward_time_step=-0.01)
-# an action table with turns beyond max_turn_rate * dt (0.6 rad), straight ahead at index 2: the max-turn clamp really acts
-WIDE = [[1.0, 0.3], [1.0, -0.3], [1.0, 0.0], [1.0, 0.9], [1.0, -0.9], [0.5, 1.2], [0.5, -1.2], [0.0, 0.7], [0.0, -0.7], [1.0, 1.5], [1.0, -1.5]]
-
 
 def _env(W, N, M=None, seed=0, **over):
     from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
@@ -200,3 +202,51 @@ def test_sensing_horizon_known_answer():
     far.set_state(f64, f32, torch.full((3,), 0x20 | 0x40, dtype=torch.int32).cuda())
     assert far.observe()[0, :, 1].cpu().tolist() == [2.0, 2.0, 2.0]
     env.close(); far.close()
+
+
+# ---- every numeric field off its default (tests/cfg_regimes.py) ---------------------------------------------------------------------
+@pytest.mark.parametrize("cid", [c.cid for c in R.select("tile-")])
+def test_every_numeric_field_off_its_default_in_every_tile_form(cid, monkeypatch):
+    """CLIPPED / UNCLIPPED with RING on the pool and the look-ahead rings and BOX generated inside the step: one step per launch, the
+    K-step launch in slots and as packed records, every step against the oracle; the form of every launch against the case's table
+    entry (cfg_regimes.TILE_SHAPES) -- a silent fallback fails."""
+    case = R.BY_ID[cid]
+    if case.pipe is not None:
+        monkeypatch.setenv("CAVOID_PIPELINE", case.pipe)
+    env = _env(case.W, case.N, seed=case.seed, **case.over)
+    monkeypatch.delenv("CAVOID_PIPELINE", raising=False)
+    run = R.drive_gpu(case, env, *case.forms)
+    R.assert_events(case, run)
+    env.close()
+
+
+@pytest.mark.parametrize("pool", [0, 500, R.DEFAULT_POOL])
+@pytest.mark.parametrize("gen_set", ["RING", "BOX"])
+def test_reset_generator_parity_off_the_default_numbers(gen_set, pool):
+    """tests/test_gpu_parity.py::test_reset_generator_parity with every numeric field of the generator off its default: flags and float32
+    state exact, float64 state to 1e-12, the masked reset"""
+    W, N, seed = 1000, 6, 99
+    over = dict(R.GEN_SETS[gen_set], gen_pool_size=pool)
+    ocfg, ogen = rp.oracle_for(N, None, **over)
+    env = _env(W, N, seed=seed, **over)
+    obs = env.reset().cpu().numpy()
+    st = co.State.empty(W, N)
+    co.generate(ocfg, ogen, seed, st, np.zeros(W, np.uint32))
+
+    def same_state():
+        f64, f32, fl = [v.cpu().numpy() for v in env.get_state()]
+        assert np.array_equal(fl.view(np.uint32), st.flags) and np.array_equal(f32, st.f32)
+        np.testing.assert_allclose(f64, st.f64, rtol=0, atol=1e-12)
+    same_state()
+    np.testing.assert_allclose(obs, co.observe(ocfg, st), rtol=0, atol=OBS_TOL)
+    assert np.array_equal(env.episode.cpu().numpy(), np.zeros(W, np.int32))
+    n_world = ((st.flags.reshape(W, N) & 0x20) != 0).sum(axis=1)
+    assert set(n_world) == set(range(2, N + 1))                 # both box sizes (gen_box_large_from = 4) and every agent count
+    mask = (np.arange(W) % 3 == 0).astype(np.uint8)             # a masked reset advances only the masked worlds
+    obs2 = env.reset(torch.from_numpy(mask).cuda()).cpu().numpy()
+    ep = mask.astype(np.uint32)
+    co.generate(ocfg, ogen, seed, st, ep, mask)
+    same_state()
+    np.testing.assert_allclose(obs2, co.observe(ocfg, st), rtol=0, atol=OBS_TOL)
+    assert np.array_equal(env.episode.cpu().numpy().view(np.uint32), ep)
+    env.close()

@@ -24,6 +24,8 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests.cfg_regimes import TABLE5, TABLE32, WIDE          # (the tables live beside the other off-default cases)
+
 pytestmark = pytest.mark.gpu
 
 INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
@@ -32,12 +34,6 @@ ENV_VARS = ("CAVOID_QUAD", "CAVOID_PIPELINE", "CAVOID_RELAY_CONSUMERS", "CAVOID_
 # the form's switches; CAVOID_QUAD=0 everywhere: a one-step launch (K = 1) is env_kernel's plain step
 FORMS = {"relay": dict(CAVOID_PIPELINE="2"), "pipe": dict(CAVOID_PIPELINE="1"), "loop_pf": dict(CAVOID_PIPELINE="0"),
          "loop": dict(CAVOID_PREFETCH_POOL="0")}
-TABLE5 = [[1.0, 0.0], [1.0, np.pi / 6], [1.0, -np.pi / 6], [0.5, 0.0], [0.0, 0.0]]
-TABLE32 = [[(1.0, 0.5, 0.0, 0.75)[k % 4], (k - 16) * np.pi / 40] for k in range(32)]
-# turns beyond max_turn_rate * dt (3 rad/s * 0.2 s): the default table's widest turn (pi/6) never reaches the max-turn clamp
-WIDE = [[1.0, 0.3], [1.0, -0.3], [1.0, 0.0], [1.0, 0.9], [1.0, -0.9], [0.5, 1.2], [0.5, -1.2], [0.0, 0.7], [0.0, -0.7], [1.0, 1.5], [1.0, -1.5]]
-
-
 def _make_env(monkeypatch, W, N, M, seed, env_vars, over):
     from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
     from rl_collision_avoidance_amd.config import EnvConfig

@@ -10,6 +10,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from oracle import c_oracle as co
+from tests.cfg_regimes import _cont_actions, _goal_seeking_actions          # (shared with the off-default cases)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,14 +47,6 @@ def _push(env, st):
 def _pull(env):
     f64, f32, fl = env.get_state()
     return f64.cpu().numpy(), f32.cpu().numpy(), fl.cpu().numpy().view(np.uint32)
-
-
-def _goal_seeking_actions(rng, W, N, p_straight=0.8):
-    """uniform random actions, biased to 'full speed straight ahead' (index 2) so that agents also
-    REACH goals (pure noise mostly times out or collides)."""
-    acts = rng.integers(0, 11, size=(W, N))
-    acts[rng.random((W, N)) < p_straight] = 2
-    return acts.astype(np.int32)
 
 
 def _compare_step(tag, env_out, ora_out, env, st):
@@ -191,20 +184,6 @@ def test_continuous_actions_parity(dyn):
         out = env.step_continuous(torch.from_numpy(acts).cuda())
         _compare_step((dyn, t), out, co.step(ocfg, st, None, acts), env, st)
     env.close()
-
-
-def _cont_actions(rng, dyn, st, K, W, N):
-    """K slices of continuous actions [K,W,N,2]: holonomic = a velocity towards the goal (as seen from `st`) + noise, unicycle =
-    (speed, heading change) with the heading change biased towards the goal so that agents also arrive"""
-    g = np.stack([st.f32[0] - st.f64[0], st.f32[1] - st.f64[1]], -1).reshape(W, N, 2)
-    if dyn == "holonomic":
-        v = g / np.maximum(np.linalg.norm(g, axis=-1, keepdims=True), 1e-6) * st.f32[3].reshape(W, N, 1)
-        return (v[None] + rng.normal(0, 0.3, size=(K, W, N, 2))).astype(np.float32)
-    to_goal = np.arctan2(g[..., 1], g[..., 0]) - st.f64[2].reshape(W, N)
-    to_goal = (to_goal + np.pi) % (2 * np.pi) - np.pi
-    dh = np.clip(to_goal, -0.5, 0.5)[None] * (rng.random((K, W, N)) < 0.7) + rng.uniform(-0.4, 0.4, (K, W, N))
-    sp = st.f32[3].reshape(1, W, N) * rng.uniform(0.3, 1.0, (K, W, N))
-    return np.stack([sp, dh], -1).astype(np.float32)
 
 
 @pytest.mark.parametrize("source", ["pool", "lookahead", "instep"])
