@@ -246,6 +246,13 @@ enum {
 };
 int32_t cavoid_last_step_form(const cavoid_env *env, int32_t *relay_consumers);
 
+/* Scenario look-ahead bookkeeping (gen_lookahead > 0), host side only, no synchronisation: refill_launches (may be NULL) receives how many
+ * ahead_fill_kernel launches this handle has made so far (the first fill after create / seed / pool refresh, and every refill in front of
+ * a launch whose form does not regenerate the consumed ring slots itself); budget (may be NULL) the restarts per world the rings are still
+ * guaranteed to cover (0 before the first fill).  A relay launch (CAVOID_FORM_RELAY) of GEN v1 scenarios tops the rings up inside the
+ * launch and needs no refill launch as long as n_steps <= gen_lookahead / 2.  Without look-ahead both stay 0. */
+int cavoid_ahead_info(const cavoid_env *env, int64_t *refill_launches, int32_t *budget);
+
 /* The env-level CONTINUOUS action space (run-ws/config.yaml:3-5, ACTION_SPACE_TYPE = 0: "continuous" at the gym level; SURVEY App. A:
  * the discretisation lives in the policy) in the auto-reset and K-step launch forms: float actions [n_steps][W,N,2] -- (speed,
  * heading change) for the unicycle dynamics, a velocity (vx, vy) for CAVOID_DYN_HOLONOMIC (which ONLY these entry points and

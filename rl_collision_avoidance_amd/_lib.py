@@ -105,6 +105,7 @@ SYMBOLS = [
     ("cavoid_num_worlds", C.c_int64, [_P]),
     ("cavoid_obs_width", C.c_int32, [_P]),
     ("cavoid_last_step_form", C.c_int32, [_P, C.POINTER(C.c_int32)]),
+    ("cavoid_ahead_info", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("cavoid_seed", C.c_int, [_P, C.c_uint64, _P, _P]),
     ("cavoid_get_episode", C.c_int, [_P, _P, _P]),
     ("cavoid_pool_refresh", C.c_int, [_P, C.c_uint32, _P]),

@@ -262,6 +262,16 @@ class BatchedCollisionAvoidanceEnv(object):
         form = self._lib.cavoid_last_step_form(self._h, C.byref(nc))
         return _lib.STEP_FORMS[form], int(nc.value)
 
+    @property
+    def lookahead_info(self) -> Tuple[int, int]:
+        """(refill launches so far, guaranteed-cover budget) of the scenario look-ahead rings: how many ``ahead_fill_kernel``
+        launches the handle has made and how many restarts per world the rings still cover without one.  A relay launch of
+        GEN v1 scenarios tops its rings up inside the launch, so the count then grows only at the first fill and at calls of
+        other forms.  Host bookkeeping only: no synchronisation."""
+        refills, budget = C.c_int64(0), C.c_int32(0)
+        _lib.check(self._lib.cavoid_ahead_info(self._h, C.byref(refills), C.byref(budget)), "cavoid_ahead_info")
+        return int(refills.value), int(budget.value)
+
     # -- state -------------------------------------------------------------------------------------
     def set_state(self, state_f64: torch.Tensor, state_f32: torch.Tensor, flags: torch.Tensor) -> None:
         """Inject explicit world states (SoA): f64 [4,W*N] px,py,heading,t_remaining; f32 [5,W*N]

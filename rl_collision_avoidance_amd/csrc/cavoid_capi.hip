@@ -388,9 +388,19 @@ extern "C" int32_t cavoid_last_step_form(const cavoid_env *e, int32_t *relay_con
 // (Measured and dropped, profiles/r05_e_lookahead.txt: the refill on a side stream beside the previous launch -- the cross-stream event wait costs
 // what the refill launch costs; the refill inside env_relay_kernel, by its loader role in idle time -- +5 % on the kernel -- or by extra
 // workgroups of the same launch -- they displace tile workgroups, which must all be resident.)
-int cavoid_ahead_prepare(cavoid_env *e, int32_t n_steps, hipStream_t s, hipEvent_t *timed_start) {
+// relay_topup: the launch behind this call is env_relay_kernel with its TOP-UP wavefront (cavoid_relay.hpp; launch_autoreset decides the form
+// first, with the launcher's own refusals: cavoid_relay_takes_topup).  That launch regenerates, beside its step loop, the slots earlier
+// launches consumed -- up to (episode at entry) + R -- and reads no record beyond (episode at entry) + n_steps (its loader fetches one at entry
+// and one per restart event, and the last step posts none), so it needs a budget of n_steps, not n_steps + 1, and leaves one of R - n_steps
+// (cavoid_ahead_consumed): with n_steps <= R / 2 no refill launch in the steady state (profiles/lookahead_topup_timing.txt).  Every other form
+// keeps the rule above: the pipeline, the single-wavefront loops, the quad / one-step kernels, the actor kernels, resets, GEN v2 (its
+// wave-cooperative rejection sampling takes longer than a short launch and needs scratch LDS), N = 6 (no room for a seventh wavefront at two
+// workgroups per CU), and anything while a stream is capturing or once ahead_always is set.
+int cavoid_ahead_prepare(cavoid_env *e, int32_t n_steps, hipStream_t s, hipEvent_t *timed_start, bool relay_topup) {
     if (!e || e->ahead_R <= 0) return CAVOID_OK;
     if (n_steps + 1 > e->ahead_R) return CAVOID_EUNSUPPORTED;
+    // (relay_topup implies: not capturing, no graph so far -- cavoid_relay_takes_topup)
+    if (relay_topup && e->ahead_primed && e->ahead_budget >= n_steps) return CAVOID_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cap);
     const bool capturing = cap != hipStreamCaptureStatusNone;
@@ -414,14 +424,23 @@ int cavoid_ahead_prepare(cavoid_env *e, int32_t n_steps, hipStream_t s, hipEvent
     });
     if (rc != CAVOID_OK) return rc;
     HIP_TRY(hipGetLastError());
+    e->ahead_refills += 1;
     if (!in_place) e->ahead_cur ^= 1;
     if (!capturing) { e->ahead_primed = true; e->ahead_budget = e->ahead_R; }
     return CAVOID_OK;
 }
 // after a stepping launch of n_steps steps: what the rings are still guaranteed to cover (a world restarts at most once per step)
-void cavoid_ahead_consumed(cavoid_env *e, int32_t n_steps) {
+void cavoid_ahead_consumed(cavoid_env *e, int32_t n_steps, bool relay_topup) {
     if (!e || e->ahead_R <= 0) return;
-    e->ahead_budget = e->ahead_budget > n_steps ? e->ahead_budget - n_steps : 0;
+    if (relay_topup) e->ahead_budget = e->ahead_R - n_steps;          // topped up to (episode at entry) + R, at most n_steps of them consumed
+    else e->ahead_budget = e->ahead_budget > n_steps ? e->ahead_budget - n_steps : 0;
+}
+
+extern "C" int cavoid_ahead_info(const cavoid_env *e, int64_t *refill_launches, int32_t *budget) {
+    if (!e) return CAVOID_EINVAL;
+    if (refill_launches) *refill_launches = e->ahead_refills;
+    if (budget) *budget = e->ahead_R > 0 && e->ahead_primed ? e->ahead_budget : 0;
+    return CAVOID_OK;
 }
 
 // (re)fill the scenario pool for the current seed: the RESET kernel run over the pool buffer as
@@ -580,11 +599,15 @@ static int launch_autoreset(cavoid_env *e, KIO io, const int32_t *actions, int64
     io.action_stride = action_stride;
     io.n_steps = n_steps;
     e->last_form = CAVOID_FORM_NONE;                   // (the dispatcher that launches records its form)
-    if (int rc = cavoid_ahead_prepare(e, n_steps, s, &ev_start)) return rc;      // (a timed launch includes its look-ahead refill, when it needs one)
-    const int rc = (n_steps > 1 || e->prefetch_single)           // the in-launch step loop lives in cavoid_multistep.hip
-                       ? cavoid_launch_multistep(e, io, e->latency_mode != 0, s, ev_start, ev_stop)
-                       : launch<MODE_STEP_AUTORESET>(e, io, s, ev_start, ev_stop);
-    cavoid_ahead_consumed(e, n_steps);
+    const bool loop = n_steps > 1 || e->prefetch_single;         // the in-launch step loop lives in cavoid_multistep.hip
+    // the form is decided BEFORE the look-ahead rule: env_relay_kernel with its top-up wavefront regenerates the consumed ring slots itself
+    const bool topup = loop && e->ahead_R > 0 && relay_form_first(e, io, e->latency_mode != 0) && cavoid_relay_takes_topup(e, io, s);
+    if (int rc = cavoid_ahead_prepare(e, n_steps, s, &ev_start, topup)) return rc;      // (a timed launch includes its look-ahead refill, when it needs one)
+    if (topup) io.ahead_hi = e->ahead_hi[e->ahead_cur];
+    const int rc = loop ? cavoid_launch_multistep(e, io, e->latency_mode != 0, s, ev_start, ev_stop)
+                        : launch<MODE_STEP_AUTORESET>(e, io, s, ev_start, ev_stop);
+    if (topup && rc != CAVOID_OK) { e->ahead_primed = false; e->ahead_budget = 0; }      // (the launch did not happen: nothing is known about the rings)
+    else cavoid_ahead_consumed(e, n_steps, topup);
     return rc;
 }
 

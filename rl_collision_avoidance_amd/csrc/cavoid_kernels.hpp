@@ -138,6 +138,8 @@ struct KIO {
     int32_t n_steps;         // steps taken by ONE launch (MODE_STEP_AUTORESET; 1 elsewhere)
     int32_t obs_stride;      // floats per output row: width, or width + 2 in packed mode
     int32_t packed;          // != 0: reward and done (as 0.0f / 1.0f) are columns width, width+1 of the agent's row
+    uint32_t *ahead_hi;      // env_relay_kernel only: the look-ahead rings' bookkeeping [W], topped up IN PLACE by the launch's own top-up
+                             // wavefront (cavoid_relay.hpp); null: the launch has no such wavefront
 };
 
 // wrap to [-pi, pi) by repeated +-2*pi, exactly the oracle's `while` loops: one branch-free fold each way covers every
@@ -1051,20 +1053,13 @@ __device__ __forceinline__ void new_episode(const KCfg &c, const PoolRec *pool, 
 // wave-private LDS (GEN v2 only).  The missing episodes of a world are dealt over `ny` wavefronts (this one takes the y-th, y + ny-th, ...), so
 // that a world which consumed several episodes since the last refill does not serialise their generation: hi_in is read by all of them, the
 // y = 0 wavefront writes the new bookkeeping to hi_out (the host swaps the two arrays after every refill).
-template <int N>
-__device__ __forceinline__ void ahead_fill_wave(const KCfg &c, const uint32_t *episode, const uint32_t *hi_in, uint32_t *hi_out, PoolRec *ahead, const int need,
-                                                const int64_t wave, const int lane, const int y, const int ny, double *sc_d, float *sc_r) {
-    const int wpw = c.wpw, lanes_used = wpw * N;
-    const int lw = lane / N, i = lane - lw * N;
-    const int64_t w = wave * wpw + lw;
-    const bool active = lane < lanes_used && w < c.num_worlds;
-    const int base = lane < lanes_used ? lw * N : 0;
-    uint32_t ep = 0u, fh = 0u;
-    if (active) {
-        ep = episode[w];
-        fh = hi_in[w];
-        if (fh == 0xFFFFFFFFu || (int32_t)(fh - ep) < 0) fh = ep;      // nothing valid ahead of this world's current episode
-    }
+// the generation itself, from a lane's bookkeeping words already loaded (ep = episode[w], fh = hi_in[w]; both 0 on an idle lane): env_relay_kernel's
+// top-up role loads them at kernel entry and generates behind the workgroup barrier (V1_ONLY: GEN v1 alone is compiled in, no scratch LDS)
+template <int N, bool V1_ONLY = false>
+__device__ __forceinline__ void ahead_fill_range(const KCfg &c, const uint32_t ep, uint32_t fh, const bool active, const int64_t w, const int i, const int base,
+                                                 const int lane, uint32_t *hi_out, PoolRec *ahead, const int need, const int y, const int ny, double *sc_d,
+                                                 float *sc_r) {
+    if (active && (fh == 0xFFFFFFFFu || (int32_t)(fh - ep) < 0)) fh = ep;      // nothing valid ahead of this world's current episode
     const uint32_t target = ep + (uint32_t)need;
     int missing = active ? (int)(int32_t)(target - fh) : 0;
     missing = missing < 0 ? 0 : missing;
@@ -1077,7 +1072,7 @@ __device__ __forceinline__ void ahead_fill_wave(const KCfg &c, const uint32_t *e
         const bool fresh = active && k < missing;
         Agent a;
         absent_agent(a);
-        if (c.gen_mode == 1) generate_world_v2<N>(c, gw, e, i, base, lane, fresh, sc_d, sc_d + 64, sc_d + 128, sc_d + 192, sc_r, a);
+        if (!V1_ONLY && c.gen_mode == 1) generate_world_v2<N>(c, gw, e, i, base, lane, fresh, sc_d, sc_d + 64, sc_d + 128, sc_d + 192, sc_r, a);
         else if (fresh) generate_agent<N>(c, gw, e, i, a);
         if (fresh) {
             PoolRec r;
@@ -1088,6 +1083,21 @@ __device__ __forceinline__ void ahead_fill_wave(const KCfg &c, const uint32_t *e
         }
     }
     if (active && i == 0 && y == 0) hi_out[w] = missing > 0 ? target : fh;
+}
+template <int N>
+__device__ __forceinline__ void ahead_fill_wave(const KCfg &c, const uint32_t *episode, const uint32_t *hi_in, uint32_t *hi_out, PoolRec *ahead, const int need,
+                                                const int64_t wave, const int lane, const int y, const int ny, double *sc_d, float *sc_r) {
+    const int wpw = c.wpw, lanes_used = wpw * N;
+    const int lw = lane / N, i = lane - lw * N;
+    const int64_t w = wave * wpw + lw;
+    const bool active = lane < lanes_used && w < c.num_worlds;
+    const int base = lane < lanes_used ? lw * N : 0;
+    uint32_t ep = 0u, fh = 0u;
+    if (active) {
+        ep = episode[w];
+        fh = hi_in[w];
+    }
+    ahead_fill_range<N>(c, ep, fh, active, w, i, base, lane, hi_out, ahead, need, y, ny, sc_d, sc_r);
 }
 
 template <int N>

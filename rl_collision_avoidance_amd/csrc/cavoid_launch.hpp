@@ -27,6 +27,10 @@ struct cavoid_env {
     bool ahead_primed = false;          // the rings have been filled once for the current seed / episodes
     bool ahead_always = false;          // a hipGraph holding stepping launches of this env exists: replays consume episodes the host does not see,
                                         // so from then on every launch carries the refill (a no-op when nothing is missing)
+    int64_t ahead_refills = 0;          // ahead_fill_kernel launches so far (cavoid_ahead_info)
+    int relay_topup_nc = -1;            // env_relay_kernel's top-up wavefront: the shape (consumers, dynamic LDS) the occupancy calculator was last
+    size_t relay_topup_lds = 0;         // asked about, and whether two workgroups per CU are resident with it
+    bool relay_topup_fits = false;
     void *slab = nullptr;
     void *pool_slab = nullptr;
     double *d_actions = nullptr;
@@ -158,10 +162,20 @@ static inline int launch_pipe(cavoid_env *e, const KIO &io, hipStream_t s, hipEv
 // timed_start (may be null): a start event the caller wants recorded where the launch's work begins -- when a refill is launched it is recorded
 // in front of THAT kernel and *timed_start is set to null (the stepping kernel behind it then records only its stop event), so that a timed
 // launch includes its refill (cavoid_step_autoreset_n_timed)
-int cavoid_ahead_prepare(cavoid_env *e, int32_t n_steps, hipStream_t s, hipEvent_t *timed_start = nullptr);
-void cavoid_ahead_consumed(cavoid_env *e, int32_t n_steps);     // call after the stepping launch that cavoid_ahead_prepare(n_steps) preceded
+// relay_topup: the launch behind it is env_relay_kernel WITH its top-up wavefront (cavoid_relay_takes_topup said so): it needs the rings to
+// cover n_steps episodes only, regenerates what earlier launches consumed itself and leaves a budget of R - n_steps
+int cavoid_ahead_prepare(cavoid_env *e, int32_t n_steps, hipStream_t s, hipEvent_t *timed_start = nullptr, bool relay_topup = false);
+void cavoid_ahead_consumed(cavoid_env *e, int32_t n_steps, bool relay_topup = false);     // call after the stepping launch that cavoid_ahead_prepare(n_steps) preceded
 // env_relay_kernel (cavoid_relay.hip): CAVOID_EUNSUPPORTED when the batch is too large for it or its LDS does not fit
 int cavoid_launch_relay(cavoid_env *e, const cavoid::KIO &io, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
+// the multi-step launch of this call tries env_relay_kernel first (cavoid_launch_multistep's order, written once)
+static inline bool relay_form_first(const cavoid_env *e, const cavoid::KIO &io, bool prefetch) {
+    return !cavoid::crowd_form(e->cfg.max_agents) && !e->k.rvo_enabled && !(e->k.gen_mode == 1 && e->k.pool_size <= 0) && prefetch && e->pipeline >= 2 &&
+           !io.cont;
+}
+// ... and cavoid_launch_relay will carry it with the top-up wavefront, given io.ahead_hi: the refusals of cavoid_launch_relay, look-ahead
+// rings generated by GEN v1, no stream capture now or earlier, two workgroups per CU resident with the extra wavefront
+bool cavoid_relay_takes_topup(cavoid_env *e, const cavoid::KIO &io, hipStream_t s);
 // multi-step auto-reset launch (cavoid_multistep.hip): prefetch != 0 -> MODE_STEP_AUTORESET_PF, else MODE_STEP_AUTORESET_N
 // env_quad_kernel (cavoid_quad.hip): CAVOID_EUNSUPPORTED when the configuration or the launch is not one it carries
 int cavoid_launch_quad(cavoid_env *e, const cavoid::KIO &io, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);

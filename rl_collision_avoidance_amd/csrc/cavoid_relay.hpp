@@ -23,6 +23,9 @@
 //                      times per step.
 //   L  (loader)        everything that touches memory inside the loop and is not an output: the action block (a 64-step
 //                      byte ring in LDS, filled ahead of D) and the next scenario-pool record of every restarted lane.
+//   T  (top-up)        (look-ahead rings, GEN v1, when the host asks for it: KIO::ahead_hi) regenerates the ring slots the PREVIOUS launches
+//                      consumed, so that no ahead_fill_kernel launch has to sit in front of this one: it depends on nothing the launch
+//                      computes, hands nothing to any other role and is read by nobody inside the launch (see the role's comment below).
 //   D + P + L          (N >= 4) the observation of the LAST step, together: one neighbour slot in three each, the mapping of
 //                      cavoid_quad.hpp -- all three are idle once the last step is settled, and the launch's tail is one
 //                      observation latency behind that moment (relay_coop_last).
@@ -32,6 +35,9 @@
 // LDS, polled (s_sleep); an LDS write of a wavefront is visible to the workgroup in issue order, so "data, then counter" on
 // the writer and "counter, then data" on the reader is enough -- no workgroup barrier and no vmcnt drain inside the loop.
 #pragma once
+#include <cstddef>
+#include <type_traits>
+
 #include "cavoid_kernels.hpp"
 
 namespace cavoid {
@@ -48,6 +54,10 @@ constexpr size_t kRelayLdsLimit = 80 * 1024;      // per workgroup: two of them 
 constexpr int kRelayActRing = 64;        // action ring: steps
 constexpr int kRelayActAhead = 48;       // the loader runs at most this many steps ahead of D
 constexpr int kRelayEvq = 8;             // restart-event queue D -> L
+// The top-up wavefront makes 7 wavefronts per workgroup with three consumers: two workgroups per CU are then 4 wavefronts on two of its
+// SIMDs, i.e. at most 128 vector registers.  N <= 5 compile to 119 .. 130 left alone and are held to 128 (launch bounds below); N = 6
+// takes 144 and cannot carry the role (cavoid_launch_relay asks the runtime's occupancy calculator, not this constant).
+constexpr int kRelayTopupMaxN = 5;
 
 struct RelaySeq {                        // sequence counters (each written by exactly one wavefront)
     int spec;                            // D: the SPECULATIVE tentative state of steps < spec is in `tent` (nothing happened at the step before)
@@ -61,7 +71,7 @@ struct RelaySeq {                        // sequence counters (each written by e
     int cfin[kRelayMaxConsumers];        // C: all of the consumer's stores have completed
     int coop[2];                         // D, P, L (the last step's observation, made together): arrivals at its two hand-overs (LDS atomics)
     int kernarg[2];                      // ... and what they start from: the kernel-argument segment's address and the tile (written once, at entry)
-    int tile_id;
+    int tile_id;                         // ... the tile in the low 16 bits, the consumer count above them
 };
 static_assert(sizeof(RelaySeq) % 16 == 0, "the event queue behind it holds 64-bit masks; the tiles further on are read 16 bytes at a time");
 struct RelayTent { double px[64], py[64], vx[64], vy[64], heading[64]; float r[64], gx[64], gy[64], pref[64]; uint32_t flags[64]; };
@@ -74,7 +84,7 @@ struct RelayNxt { double px[64], py[64], heading[64], t_rem[64]; float gx[64], g
 // consumer on the even wavefronts -- each D beside the OTHER tile's P -- and the loader with two consumers on the odd ones (-2 % against
 // the plain order D P C0 C1 C2 L; P beside two consumers +12 %; D beside its own P +1 %; padding wavefronts that shift the pattern 0 %).
 #ifndef CAVOID_RELAY_ORDER
-#define CAVOID_RELAY_ORDER 0x432150      /* one nibble per wavefront, wavefront 0 lowest: D L P C0 C1 C2 */
+#define CAVOID_RELAY_ORDER 0x6432150     /* one nibble per wavefront, wavefront 0 lowest: D L P C0 C1 C2 T (T: only in a launch with the top-up) */
 #endif
 // Issue priority of the roles (s_setprio: a SIMD's arbiter takes the ready wavefront of the highest priority).  D and P carry the loop-carried
 // cycle and stay on top; the consumers ABOVE the loader (it only polls between its rare refills) is worth -1.4 % (K = 20) / -2.4 % (K = 64)
@@ -91,6 +101,9 @@ struct RelayNxt { double px[64], py[64], heading[64], t_rem[64]; float gx[64], g
 #endif
 #ifndef CAVOID_RELAY_PRIO_C
 #define CAVOID_RELAY_PRIO_C 1
+#endif
+#ifndef CAVOID_RELAY_PRIO_T
+#define CAVOID_RELAY_PRIO_T 0             /* the top-up: nobody in the launch waits for it */
 #endif
 // development: timing-only ablations of the roles (WRONG results; profiles/r06_w_relay_prio_ablation.txt): 1 the consumers make no observation
 // (they only free their ring slots), 2 P's distance loop left out, 4 D's advance without its sine / cosine, 8 D never waits for P's verdict and
@@ -362,6 +375,16 @@ __device__ __forceinline__ void relay_pair_part(const KCfg &c, const Agent &a, c
 // (written inline it cost D's and P's loops 23 and 16 v_readlane of spilled scalars per iteration; even the argument pointer kept live
 // put one of D's sine / cosine constants into a spill lane).
 struct RelayArgs { KCfg c; KState s; const PoolRec *pool; KIO io; };      // the kernel's argument segment
+// ... which the code-object ABI lays out like this struct as long as every argument is 8-byte aligned and a whole number of 8-byte words
+// (each by-value argument goes to the next offset of its own alignment): a field added to KCfg, KState or KIO must not silently shift what
+// relay_coop_last reads.  (That the kernel's parameter list IS these four is asserted behind the kernel.)
+static_assert(alignof(KCfg) == 8 && alignof(KState) == 8 && alignof(KIO) == 8 && alignof(RelayArgs) == 8, "kernel arguments: 8-byte aligned");
+static_assert(sizeof(KCfg) % 8 == 0 && sizeof(KState) % 8 == 0 && sizeof(KIO) % 8 == 0, "kernel arguments: whole 8-byte words, no tail padding to skip");
+static_assert(offsetof(RelayArgs, c) == 0 && offsetof(RelayArgs, s) == sizeof(KCfg) && offsetof(RelayArgs, pool) == sizeof(KCfg) + sizeof(KState) &&
+                  offsetof(RelayArgs, io) == sizeof(KCfg) + sizeof(KState) + sizeof(const PoolRec *) &&
+                  sizeof(RelayArgs) == sizeof(KCfg) + sizeof(KState) + sizeof(const PoolRec *) + sizeof(KIO),
+              "RelayArgs must be the kernel's argument segment, argument by argument");
+static_assert(sizeof(KIO) == 104 && offsetof(KIO, n_steps) == 80 && offsetof(KIO, ahead_hi) == 96, "KIO changed: check what relay_coop_last reads from it");
 template <class T>
 __device__ __forceinline__ void relay_load_args(T &dst, const __attribute__((address_space(4))) T *src) {      // word by word from the constant address space
     static_assert(sizeof(T) % 4 == 0, "whole words");
@@ -387,13 +410,14 @@ __device__ __forceinline__ void relay_coop_last(unsigned char *smem) {
     RelayCoop<N> *coopb = reinterpret_cast<RelayCoop<N> *>(sp); sp += relay_coop_bytes<N>();
     float *tiles = reinterpret_cast<float *>(sp);
     const int lane0 = threadIdx.x & 63;
-    const int NC = (blockDim.x >> 6) - 3;
+    const int tile_nc = relay_peek(&seq->tile_id);          // the tile and, above bit 16, the consumer count (a launch with the top-up has one
+    const int NC = tile_nc >> 16;                           // wavefront more than 3 + NC: not derived from the block size here)
     const int role = relay_role_of(threadIdx.x >> 6, NC);
     const int pw = role < 2 ? role : 2;                     // D 0, P 1, L 2
     const int ostride = io.obs_stride;
     const int tile_floats = (c.tile_rows * ostride + 3) & ~3;
     const int wpw = c.wpw, lanes_used = wpw * N;
-    const int64_t wave = relay_peek(&seq->tile_id);
+    const int64_t wave = tile_nc & 0xFFFF;
     const int64_t w0 = wave * wpw;
     const int lw = lane0 / N, i0 = lane0 - lw * N;
     const int64_t w = w0 + lw;
@@ -476,8 +500,39 @@ __device__ __forceinline__ void relay_coop_last(unsigned char *smem) {
     if (pw == 0) RELAY_MARK(29);                           // D: its share of the last step's rows flushed
 }
 
+// ---- T: the top-up of the look-ahead rings (the role's comment in env_relay_kernel) ------------------------------------------------------
 template <int N>
-__global__ void __launch_bounds__(64 * (3 + kRelayMaxConsumers), 1) env_relay_kernel(const KCfg c, const KState s, const PoolRec *pool, const KIO io) {
+__device__ __forceinline__ void relay_topup() {
+    __builtin_amdgcn_s_setprio(CAVOID_RELAY_PRIO_T);
+    unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));                            // (its own loads of the arguments, not the kernel's)
+    typedef const __attribute__((address_space(4))) RelayArgs *ArgP;
+    const ArgP ka = (ArgP)kp;
+    KCfg c;
+    uint32_t *episode, *hi;
+    const PoolRec *ring;
+    relay_load_args(c, &ka->c);
+    relay_load_args(episode, &ka->s.episode);
+    relay_load_args(ring, &ka->pool);
+    relay_load_args(hi, &ka->io.ahead_hi);
+    const int lane0 = threadIdx.x & 63;
+    const int wpw = c.wpw, lanes_used = wpw * N;
+    const int lw = lane0 / N, i0 = lane0 - lw * N;
+    const int64_t w = (int64_t)blockIdx.x * wpw + lw;
+    const bool active = lane0 < lanes_used && w < c.num_worlds;
+    const int base0 = lane0 < lanes_used ? lw * N : 0;
+    uint32_t ep = 0u, fh = 0u;
+    if (active) {
+        ep = episode[w];
+        fh = hi[w];
+    }
+    asm volatile("" : "+v"(ep), "+v"(fh));                  // (the loads stay in front of the barrier)
+    __syncthreads();
+    ahead_fill_range<N, true>(c, ep, fh, active, w, i0, base0, lane0, hi, const_cast<PoolRec *>(ring), c.ahead, 0, 1, nullptr, nullptr);
+}
+
+template <int N>
+__global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopupMaxN ? 4 : 1) env_relay_kernel(const KCfg c, const KState s, const PoolRec *pool, const KIO io) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *sp = smem;
     double *lds_tab = reinterpret_cast<double *>(sp); sp += lds_floats_block() * sizeof(float);
@@ -490,8 +545,8 @@ __global__ void __launch_bounds__(64 * (3 + kRelayMaxConsumers), 1) env_relay_ke
     RelayCoop<N> *coopb = reinterpret_cast<RelayCoop<N> *>(sp); sp += relay_coop_bytes<N>();   // (N < kRelayCoopFromN: nothing, never touched)
     float *tiles = reinterpret_cast<float *>(sp);
 
-    const int NC = (blockDim.x >> 6) - 3;
-    const int role = relay_role_of(threadIdx.x >> 6, NC);   // 0 D, 1 P, 2 .. 1+NC consumers, 2+NC L
+    const int NC = (blockDim.x >> 6) - 3 - (io.ahead_hi ? 1 : 0);   // (a launch with the top-up has one wavefront more)
+    const int role = relay_role_of(threadIdx.x >> 6, NC);   // 0 D, 1 P, 2 .. 1+NC consumers, 2+NC L, 3+NC T
     const int lane0 = threadIdx.x & 63;
     const int ostride = io.obs_stride;
     const int tile_floats = (c.tile_rows * ostride + 3) & ~3;
@@ -516,7 +571,7 @@ __global__ void __launch_bounds__(64 * (3 + kRelayMaxConsumers), 1) env_relay_ke
         if (role == 0 && lane0 == 0) {                      // (behind the zeroes: the same wavefront's LDS writes, in order)
             const unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
             seq->kernarg[0] = (int)(uint32_t)kp; seq->kernarg[1] = (int)(uint32_t)(kp >> 32);
-            seq->tile_id = (int)blockIdx.x;
+            seq->tile_id = (int)blockIdx.x | (NC << 16);    // (at most 512 tiles: cavoid_launch_relay)
         }
     }
 
@@ -852,6 +907,22 @@ __global__ void __launch_bounds__(64 * (3 + kRelayMaxConsumers), 1) env_relay_ke
             if (++idle_polls > kRelayPollLimit) __builtin_trap();
             __builtin_amdgcn_s_sleep(2);
         }
+    } else if (role == 3 + NC) {
+        // ================================================ T: top-up of the look-ahead rings =====================================
+        // Regenerates, for every world of the tile, the ring slots of the episodes (hi, episode at entry + R] -- what ahead_fill_kernel in
+        // front of the launch would have made.  No race inside the launch:
+        //  - at entry every ring holds at least the episodes (ep, ep + n_steps] (the host's rule, cavoid_ahead_prepare);
+        //  - the launch reads only the records of episodes ep + 1 .. ep + n_steps: the loader takes ep + 1 at entry and one more per restart
+        //    event, and D posts events only for steps t < n_steps - 1;
+        //  - this role writes only episodes > hi >= ep + n_steps and <= ep + R, into the slots of the episodes R below them: <= ep, consumed;
+        //  - episode[w] and hi[w] are loaded IN FRONT of the workgroup barrier, D's write-back of episode[w] comes behind it: every lane of a
+        //    world sees the entry value.  (A value D had already advanced would only top up further, over slots consumed all the same.)
+        // Its stores need to be visible only to the next launch.  GEN v1 only: GEN v2's wave-cooperative rejection sampling takes 20-32 us
+        // even over four wavefronts -- longer than a short launch -- and needs scratch LDS; it keeps the refill launch (the host passes no
+        // ahead_hi then).  No LDS counters, no waits, no part in relay_coop_last.
+        // Like relay_coop_last it derives what it needs from the kernel-argument segment on its own: none of it is live in scalar
+        // registers across the other roles' loops (written against the kernel's parameters it added 44 scalar spills at N = 4).
+        relay_topup<N>();
     } else {
         // ================================================ C: observation of every NC-th step ===================================
         __builtin_amdgcn_s_setprio(CAVOID_RELAY_PRIO_C);
@@ -919,5 +990,7 @@ __global__ void __launch_bounds__(64 * (3 + kRelayMaxConsumers), 1) env_relay_ke
         if (coop_role) relay_coop_last<N>(smem);
     }
 }
+static_assert(std::is_same<decltype(&env_relay_kernel<4>), void (*)(const KCfg, const KState, const PoolRec *, const KIO)>::value,
+              "relay_coop_last reloads the kernel's arguments through RelayArgs: keep the two in step");
 
 }  // namespace cavoid
