@@ -90,7 +90,8 @@ DYN_NAME = {0: "unicycle", 1: "unicycle_max_turn_rate", 2: "holonomic"}
 # over: every cavoid_cfg override (both sides); fields: the set fields held by "every field decides something"; plan: the launches, in
 # order, as (kind, slots, steps) with kind in single / slots / packed; acts: goal (goal-seeking table indices), edge (table indices with
 # out-of-range values), cont (continuous); expect: the events the case must see; pipe: CAVOID_PIPELINE while the env is created
-Case = collections.namedtuple("Case", "cid family N W seed over fields plan acts straight expect pipe forms")
+# offset: the env's world_offset (the generator is keyed on offset + world)
+Case = collections.namedtuple("Case", "cid family N W seed over fields plan acts straight expect pipe forms offset", defaults=(0,))
 
 
 def _numeric_plan(single, K, P):
@@ -172,7 +173,59 @@ def _cases():
                               ("ring-instep", 64, 20, dict(gen_pool_size=0))):
         out.append(Case("crowd-pressure-%s-%dx%d" % (tag, N, W), "crowd", N, W, 7, dict(base, max_time_ratio=0.01, **source), {}, press_plan, "goal", 2,
                         ("restart", "every_world_restarts"), None, None))
-    return out
+    return out + _topup_cases()
+
+
+# ---- the relay launch's ring top-up (tests/test_gpu_topup_oracle.py) -----------------------------------------------------------------
+# Look-ahead rings of R records per world, GEN v1 generated (gen_pool_size = 0), and nothing but K-step launches with K <= R / 2 behind the
+# reset: the first fill (ahead_fill_kernel) makes the records of episodes 1 .. R, every later record is made by the top-up wavefront of an
+# earlier relay launch (csrc/cavoid_relay.hpp, relay_topup).  A time budget of 0.03 x the straight-line time ends an episode every four or five
+# steps, at different steps in different worlds, so that within a case's steps EVERY world reads records three rings deep (`ring_turnover`):
+# records only the role can have made, from its own copy of the generator fields (RING, off their defaults), of max_time_ratio and of
+# world_offset.  No goal is reached under this budget: the goal-side step fields stay with the tile- cases.
+TOPUP_SEED = 11
+TOPUP_RATIO = 0.03
+UNICYCLE = dict(dynamics=0)                            # the plain unicycle on the default table of 11 actions (straight ahead at index 2 too)
+
+
+def _topup(tag, N, W, step_set, kinds, R=8, K=4, launches=48, ratio=TOPUP_RATIO, dyn=MAX_TURN, offset=0, exempt=(), **gen_over):
+    over = dict(STEP_SETS[step_set], **dyn)
+    over.update(RING)
+    over.update(gen_over)
+    over.update(max_time_ratio=ratio, gen_pool_size=0, gen_lookahead=R)
+    # what the role's own loads must carry (tests/test_cfg_regimes_host.py: each decides something in episodes above R).  By construction
+    # gen_min_agents decides nothing where it equals the world size (its default), and a world of one agent draws no policy (agent 0 always
+    # learns): gen_static_fraction and gen_nonlearning_fraction decide nothing at N = 1
+    fields = dict(RING, max_time_ratio=ratio, **gen_over)
+    if fields["gen_min_agents"] == N:
+        del fields["gen_min_agents"]
+    if N == 1:
+        del fields["gen_static_fraction"], fields["gen_nonlearning_fraction"]
+    plan = tuple((kinds[l % len(kinds)], K, K) for l in range(launches))
+    expect = tuple(e for e in ("restart", "collision", "staggered", "ring_turnover") if e not in exempt)
+    return Case("topup-" + tag, "topup", N, W, TOPUP_SEED, over, fields, plan, "goal", 2, expect, None, ("QUAD", "RELAY"), offset)
+
+
+def _topup_cases():
+    both = ("slots", "packed")
+    return [
+        _topup("clipped-n4x40", 4, 40, "CLIPPED", both),                            # 16 worlds per tile: a ragged last tile
+        _topup("unclipped-n5x33", 5, 33, "UNCLIPPED", ("packed",)),
+        _topup("clipped-n3x45", 3, 45, "CLIPPED", ("slots",), gen_min_agents=1),      # 21 worlds per tile, one idle lane, ragged
+        _topup("clipped-n2x33", 2, 33, "CLIPPED", ("slots",)),
+        # (a lone agent collides with nobody; the oracle's generator divides by zero if min_agents > N)
+        _topup("clipped-n1x70", 1, 70, "CLIPPED", ("slots",), exempt=("collision",), gen_min_agents=1),
+        _topup("clipped-n4x40-offset300", 4, 40, "CLIPPED", ("slots",), offset=300),  # (not a multiple of the tile's 16 worlds)
+        # the relay decodes table actions only (cavoid_relay.hip refuses io.cont, and the holonomic dynamics take nothing else: a continuous
+        # K-step launch runs the single-wavefront loop behind refill launches and never the role).  In place of continuous holonomic /
+        # unicycle cases at these shapes: the nearest configuration the relay carries, the plain unicycle (dynamics 0, which no other topup-
+        # case runs) on the default action table, per-step slots and packed records
+        _topup("unicycle-table-n4x40", 4, 40, "UNCLIPPED", both, dyn=UNICYCLE),
+        _topup("unicycle-table-n3x45", 3, 45, "CLIPPED", both, dyn=UNICYCLE, gen_min_agents=1),
+        # the benchmark's ring: one-step episodes, every world restarts at every step and every slot is regenerated and read.  6 launches,
+        # not 5: 3 R = 384 episodes.  (Collisions: gen_angle_jitter = 0.6 starts neighbours on top of each other.)
+        _topup("ring128-n4x40", 4, 40, "CLIPPED", both, R=128, K=64, launches=6, ratio=1e-9, exempt=("staggered",)),
+    ]
 
 
 CASES = _cases()
@@ -205,12 +258,14 @@ class OracleRun(object):
     """The float64 oracle on one case: reset, then the case's launches.  `draw(K)` hands out the next K action slices as (what the env is
     given, what the oracle is given); `step(fed)` advances one step and notes the events in `seen`."""
 
-    def __init__(self, case, **changed):
+    def __init__(self, case, start_episode=None, **changed):
+        """start_episode (uint32 [W]): the per-world counters the env is seeded with (`env.seed(seed, episode)`); the reset starts the next"""
         self.case = case
         self.cfg, self.gen = oracle_for(case, **changed)
         self.st = co.State.empty(case.W, case.N)
-        self.ep = np.zeros(case.W, np.uint32)
-        co.generate(self.cfg, self.gen, case.seed, self.st, self.ep)
+        self.ep0 = np.zeros(case.W, np.uint32) if start_episode is None else np.asarray(start_episode, np.uint32) + np.uint32(1)
+        self.ep = self.ep0.copy()
+        co.generate(self.cfg, self.gen, case.seed, self.st, self.ep, world_offset=case.offset)
         self.rng = np.random.default_rng(case.seed)
         self.seen = collections.Counter()
         self.t = 0
@@ -227,13 +282,15 @@ class OracleRun(object):
 
     def step(self, fed):
         c, cfg, st = self.case, self.cfg, self.st
-        out = co.step_autoreset(cfg, self.gen, c.seed, st, self.ep, None if c.acts == "cont" else fed, cont=fed if c.acts == "cont" else None)
+        out = co.step_autoreset(cfg, self.gen, c.seed, st, self.ep, None if c.acts == "cont" else fed, world_offset=c.offset,
+                                cont=fed if c.acts == "cont" else None)
         obs, rew, done, go = out
         self.t += 1
         s = self.seen
         present = (st.flags.reshape(c.W, c.N) & F_PRESENT) != 0         # (a restarted world: its new episode, as in the observation)
         n_world = present.sum(axis=1, keepdims=True)
         s["restart"] += int(go.sum())
+        s["staggered"] += int(0 < int(go.sum()) < c.W)                  # some worlds restart at this step and some do not
         r_goal, r_coll, r_step = clip(cfg, cfg.reward_at_goal), clip(cfg, cfg.reward_collision), cfg.reward_time_step
         s["goal"] += int((rew == r_goal).sum())
         s["collision"] += int((rew == r_coll).sum())
@@ -250,6 +307,10 @@ class OracleRun(object):
     def restart_share(self):
         return float((self.ep >= 1).mean())
 
+    def turns(self):
+        """episodes every world has started since the reset (uint32: the counters may wrap)"""
+        return self.ep - self.ep0
+
 
 # conditions, not measurements: the share of worlds that restarted within a continuous-action case's steps
 MIN_RESTART_SHARE = {17: 0.3, 24: 0.3, 33: 0.2, 64: 0.2}
@@ -262,6 +323,8 @@ def assert_events(case, run):
             assert run.restart_share() >= MIN_RESTART_SHARE[case.N], (case.cid, ev, run.restart_share())
         elif ev == "every_world_restarts":
             assert run.ep.min() >= 1, (case.cid, ev)
+        elif ev == "ring_turnover":                             # every world has read records that only a top-up launch can have made
+            assert run.turns().min() >= 3 * case.over["gen_lookahead"], (case.cid, ev, int(run.turns().min()))
         else:
             assert run.seen[ev] > 0, (case.cid, ev, dict(run.seen))
 
@@ -296,43 +359,79 @@ def _assert_state(tag, env, run, f64_tol=STATE_TOL):
     assert np.array_equal(env.episode.cpu().numpy().view(np.uint32), run.ep), tag
 
 
-def drive_gpu(case, env, single_form, k_form):
-    """`env` (configured with case.over, seeded with case.seed) reset and taken through the case's launches beside the oracle: flags,
-    float32 state, is_learning / num_other and the episode counters exact, float64 state <= 1e-9 (<= 1e-12 as generated), observations
-    and rewards <= 1e-5 -- after every single step, in every slot of a K-step launch (plain and packed records), the state after every
-    launch; every launch asserts the form that ran.  Returns the oracle run (its events: assert_events)."""
+def _form_is(env, want):
+    """`want`: (form, relay consumers) -- compared whole -- or the form's name alone, which leaves the consumer count UNCHECKED: only for a
+    caller that does not fix the count (the topup- cases run whatever CAVOID_RELAY_CONSUMERS' default gives; the consumer-count test passes
+    the tuple)"""
+    got = env.last_step_form
+    return got[0] == want if isinstance(want, str) else got == want
+
+
+def _same_bits(tag, env, twin, outs, twin_outs):
     import torch
-    run = OracleRun(case)
+    assert all(torch.equal(a, b) for a, b in zip(outs, twin_outs)), tag
+    assert all(torch.equal(a, b) for a, b in zip(env.get_state(), twin.get_state())) and torch.equal(env.episode, twin.episode), tag
+
+
+def drive_plan(case, env, run, plan, single_form, k_form, twin=None, twin_form=None, after_launch=None):
+    """the launches of `plan` on `env` beside the oracle run `run` (drive_gpu's checks).  `twin`: a second env taken through the same
+    launches and held BITWISE to `env` -- every output of every step, state and episodes after every launch (twin_form: the form of its
+    K-step launches where that is asserted too).  after_launch(launch index): called behind every launch's checks."""
+    import torch
     cont = case.acts == "cont"
-    obs0 = env.reset().cpu().numpy()
-    _assert_state((case.cid, "reset"), env, run, GEN_TOL)
-    oobs0 = co.observe(run.cfg, run.st)
-    assert float(rp.obs_diff(obs0, oobs0).max()) <= OBS_TOL and np.array_equal(obs0[..., :2], oobs0[..., :2].astype(np.float32)), case.cid
     wdt = env.obs_width
     slots = {}
-    for launch, (kind, K, n) in enumerate(case.plan):
+
+    def k_launch(e, a, kind, K, n):
+        key = (id(e), kind, K)
+        if key not in slots:
+            slots[key] = e.new_step_slots(K, packed=(kind == "packed"))
+        if kind == "packed":
+            pk, go = e.step_continuous_autoreset(a, n_steps=n, slots=slots[key]) if cont else e.step_autoreset_packed(a, slots[key], n_steps=n)
+            return pk[..., :wdt], pk[..., wdt], pk[..., wdt + 1].to(torch.uint8), go
+        return e.step_continuous_autoreset(a, n_steps=n, slots=slots[key]) if cont else e.step_autoreset_n(a, n_steps=n, slots=slots[key])
+
+    for launch, (kind, K, n) in enumerate(plan):
         raw, fed = run.draw(K)
         tag = (case.cid, kind, launch)
         if kind == "single":
             a = torch.from_numpy(raw[0]).cuda()
             out = env.step_continuous_autoreset(a) if cont else env.step_autoreset(a)
-            assert env.last_step_form == (single_form, 0), (tag, env.last_step_form)
+            assert _form_is(env, (single_form, 0)), (tag, env.last_step_form)
+            if twin is not None:
+                _same_bits(tag, env, twin, out, twin.step_continuous_autoreset(a) if cont else twin.step_autoreset(a))
             _assert_outputs(tag, *[v.cpu().numpy() for v in out], run.step(fed[0]))
             _assert_state(tag, env, run)
-            continue
-        key = (kind, K)
-        if key not in slots:
-            slots[key] = env.new_step_slots(K, packed=(kind == "packed"))
-        a = torch.from_numpy(raw).cuda()
-        if kind == "packed":
-            pk, go = env.step_continuous_autoreset(a, n_steps=n, slots=slots[key]) if cont else env.step_autoreset_packed(a, slots[key], n_steps=n)
-            obs, rew, done = pk[..., :wdt], pk[..., wdt], pk[..., wdt + 1].to(torch.uint8)
         else:
-            obs, rew, done, go = (env.step_continuous_autoreset(a, n_steps=n, slots=slots[key]) if cont
-                                  else env.step_autoreset_n(a, n_steps=n, slots=slots[key]))
-        assert env.last_step_form == k_form, (tag, env.last_step_form)
-        obs, rew, done, go = [v.cpu().numpy() for v in (obs, rew, done, go)]
-        for t in range(n):
-            _assert_outputs(tag + (t,), obs[t], rew[t], done[t], go[t], run.step(fed[t]))
-        _assert_state(tag, env, run)
+            a = torch.from_numpy(raw).cuda()
+            out = k_launch(env, a, kind, K, n)
+            assert _form_is(env, k_form), (tag, env.last_step_form)
+            if twin is not None:
+                twin_out = k_launch(twin, a, kind, K, n)
+                assert twin_form is None or _form_is(twin, twin_form), (tag, twin.last_step_form)
+                _same_bits(tag, env, twin, [v[:n] for v in out], [v[:n] for v in twin_out])
+            obs, rew, done, go = [v.cpu().numpy() for v in out]
+            for t in range(n):
+                _assert_outputs(tag + (t,), obs[t], rew[t], done[t], go[t], run.step(fed[t]))
+            _assert_state(tag, env, run)
+        if after_launch is not None:
+            after_launch(launch)
+
+
+def drive_gpu(case, env, single_form, k_form, start_episode=None, twin=None, twin_form=None, after_launch=None):
+    """`env` (configured with case.over, seeded with case.seed, at world_offset case.offset) reset and taken through the case's launches
+    beside the oracle: flags, float32 state, is_learning / num_other and the episode counters exact, float64 state <= 1e-9 (<= 1e-12 as
+    generated), observations and rewards <= 1e-5 -- after every single step, in every slot of a K-step launch (plain and packed records),
+    the state after every launch; every launch asserts the form that ran.  start_episode (uint32 [W]): the env is seeded with these
+    per-world episode counters first.  twin, twin_form, after_launch: drive_plan's.  Returns the oracle run (its events: assert_events)."""
+    import torch
+    run = OracleRun(case, start_episode)
+    for e in (env,) if twin is None else (env, twin):
+        if start_episode is not None:
+            e.seed(case.seed, torch.from_numpy(np.asarray(start_episode, np.uint32).view(np.int32).copy()).to(e.device))
+        obs0 = e.reset().cpu().numpy()
+        _assert_state((case.cid, "reset"), e, run, GEN_TOL)
+        oobs0 = co.observe(run.cfg, run.st)
+        assert float(rp.obs_diff(obs0, oobs0).max()) <= OBS_TOL and np.array_equal(obs0[..., :2], oobs0[..., :2].astype(np.float32)), case.cid
+    drive_plan(case, env, run, case.plan, single_form, k_form, twin, twin_form, after_launch)
     return run
