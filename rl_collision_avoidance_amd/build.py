@@ -231,10 +231,45 @@ def build_crowd_dev(verbose: bool = False) -> str:
     return out
 
 
+def build_plain_dist(verbose: bool = False) -> str:
+    """Development variant WITHOUT the two trims of the relay step (-DCAVOID_MIRROR_DIST=0: every pair distance computed on every lane;
+    -DCAVOID_RELAY_ROLE_ARGS=0: env_relay_kernel's roles read the kernel's own parameters), for tests/test_gpu_relay_trim.py, which holds
+    the product bitwise to it.  Dev-only N, widened to the agent counts that test runs (3 .. 6 and 10).  Built like the ulp-fault
+    variants; never loaded by the product."""
+    import glob
+    from concurrent.futures import ThreadPoolExecutor
+    out = variant_path("plaindist")
+    if os.path.exists(out):
+        return out
+    build()
+    objs = _compile_objects([], "", False, verbose)
+    jobs, swap = [], {}
+    for name in ("cavoid_capi.hip", "cavoid_multistep.hip", "cavoid_rvo.hip", "cavoid_relay.hip"):      # (the units with the pair pass of the tile forms)
+        src = os.path.join(CSRC, name)
+        obj = os.path.join(OBJ_DIR, name.replace(".hip", ".plaindist.o"))
+        jobs.append([hipcc()] + FLAGS + EXTRA_FLAGS.get(name, []) +
+                    ["-DCAVOID_MIRROR_DIST=0", "-DCAVOID_RELAY_ROLE_ARGS=0", "-DCAVOID_DEV_ONLY_N", "-DCAVOID_DEV_ENV_NS=3,4,5,6,10",
+                     "-DCAVOID_DEV_RELAY_NS=3,4,5,6", "-c", src, "-o", obj])
+        swap[os.path.join(OBJ_DIR, name.replace(".hip", ".o"))] = obj
+    if verbose:
+        for j in jobs:
+            print(" ".join(j), flush=True)
+    with ThreadPoolExecutor(max_workers=len(jobs)) as pool:
+        list(pool.map(subprocess.check_call, jobs))
+    for old in glob.glob(os.path.join(FAULT_DIR, "libcavoid_hip_plaindist-*.so")):
+        os.remove(old)
+    tmp = out + ".tmp"
+    _link([swap.get(o, o) for o in objs], tmp, verbose)
+    os.replace(tmp, out)
+    return out
+
+
 if __name__ == "__main__":
     import sys
     if "--trace" in sys.argv:
         print(build_trace(verbose=True))
+    elif "--plain-dist" in sys.argv:
+        print(build_plain_dist(verbose=True))
     elif "--crowd-dev" in sys.argv:
         print(build_crowd_dev(verbose=True))
     elif "--ulp-faults" in sys.argv:

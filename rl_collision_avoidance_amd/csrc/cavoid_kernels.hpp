@@ -436,6 +436,44 @@ __device__ __forceinline__ int other_index(int i, int o, int n) {
     return j >= n ? j - n : j;
 }
 
+// Mirrored pair distances (tile forms with one lane per agent).  Lane i, slot o and lane j = other_index(i, o), slot N-2-o are the same
+// unordered pair: rx and ry of the one are the exact negatives of the other's, so rx*rx + ry*ry -- and sqrt_dist2 of it -- come out bit for
+// bit equal on both lanes.  Each lane computes the slots o < N/2 (the self-mirrored middle slot of an even N among them) and fetches the
+// rest from its mirror lane: two lane moves instead of the ~15 float64 instructions of the chain.  Only d is exchanged; rx, ry and
+// everything made from d stay per lane.  A mirror lane lies in the lane's own world, so a lane enabled here always finds its mirror
+// enabled (whole worlds branch together); what a lane behind the last world fetches is never used.  -DCAVOID_MIRROR_DIST=0: every slot computed.
+#ifndef CAVOID_MIRROR_DIST
+#define CAVOID_MIRROR_DIST 1
+#endif
+template <int N>
+__host__ __device__ constexpr int mirror_computed() { return (CAVOID_MIRROR_DIST && N >= 3) ? N / 2 : (N > 1 ? N - 1 : 1); }   // slots below it are computed
+__host__ __device__ constexpr int other_index_c(int i, int o, int n) { return i + 1 + o >= n ? i + 1 + o - n : i + 1 + o; }   // other_index, for the asserts
+template <int N>
+__host__ __device__ constexpr bool mirror_split_ok() {     // every fetched slot's mirror is a computed one and points back at the lane
+    for (int i = 0; i < N; ++i)
+        for (int o = mirror_computed<N>(); o < N - 1; ++o)
+            if (N - 2 - o < 0 || N - 2 - o >= mirror_computed<N>() || other_index_c(other_index_c(i, o, N), N - 2 - o, N) != i) return false;
+    return true;
+}
+static_assert(mirror_split_ok<3>() && mirror_split_ok<4>() && mirror_split_ok<5>() && mirror_split_ok<6>() && mirror_split_ok<7>() && mirror_split_ok<8>() &&
+                  mirror_split_ok<9>() && mirror_split_ok<10>() && mirror_split_ok<11>() && mirror_split_ok<12>() && mirror_split_ok<13>() && mirror_split_ok<14>() &&
+                  mirror_split_ok<15>() && mirror_split_ok<16>(), "mirror_computed: a fetched slot must be one the mirror lane computes");
+#if CAVOID_MIRROR_DIST
+static_assert(mirror_computed<4>() == 2 && other_index_c(0, 2, 4) == ((0x93 >> 0) & 3) && other_index_c(1, 2, 4) == ((0x93 >> 2) & 3) &&
+                  other_index_c(2, 2, 4) == ((0x93 >> 4) & 3) && other_index_c(3, 2, 4) == ((0x93 >> 6) & 3),
+              "mirror_fetch<4>: quad_perm 0x93 must read lane other_index(i, 2, 4) of the quad");
+#endif
+// the distance of slot o >= mirror_computed<N>(): `mine` is this lane's slot N-2-o, src the mirror lane base + other_index(i, o, N)
+template <int N>
+__device__ __forceinline__ double mirror_fetch(double mine, int src) {
+    if (N == 4) {       // worlds are quads: slot 2 is slot 0 of the lane before this one in its quad (quad_perm [3, 0, 1, 2])
+        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(mine), 0x93, 0xF, 0xF, true);
+        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(mine), 0x93, 0xF, 0xF, true);
+        return __hiloint2double(hi, lo);
+    }
+    return __shfl(mine, src);
+}
+
 // float32 -> uint32 whose unsigned order is the float order (-0 canonicalised to +0 first)
 __device__ __forceinline__ uint32_t orderable(float f) {
     const uint32_t u = __float_as_uint(f + 0.0f);
@@ -557,15 +595,29 @@ __device__ __forceinline__ void pair_pass_impl(const KCfg &c, const Agent &a, co
     hit = false;
     min_gap = INFINITY;
     if (!PARK) { key[0].set(kKeySentinel, 0u); gapf[0] = 0.0f; }
+    // mirrored distances (mirror_fetch): the slots from kOwn on are fetched from the mirror lane's slot N-2-o.  NOT in the PARK forms (one
+    // step per launch, reset, observe at N >= 6): they roll the loop three neighbours at a time so that no slot's values stay live for a
+    // later one, and the mirror needs the first half's distances kept.  Unrolled for the mirror, the one-step kernels compile to N = 10
+    // up to 167 registers (one short of losing the third wavefront per SIMD) and N = 16 200 -> 256 with 12 bytes of scratch per lane
+    // (profiles/relay_trim_resources.txt): every slot is computed there, as before.
+    constexpr int kOwn = PARK ? K : mirror_computed<N>();
+    constexpr bool kMirror = kOwn < N - 1;
+    double dk[kMirror ? kOwn : 1];                          // the computed slots' distances, for the fetches (unused without the mirror)
     auto one = [&](int o) {
         const OtherState q = st.other(o);
         const float rjf = q.r;
         const double rx = q.px - a.px, ry = q.py - a.py;
+        double d;
+        if (!kMirror || o < kOwn) {
 #if defined(CAVOID_DEV_ULP_FAULT) && CAVOID_DEV_ULP_FAULT == 1     /* injected fault (tests/test_gpu_tie_classifier.py): one float32 product in the distance */
-        const double d = sqrt_dist2((double)((float)rx * (float)rx) + ry * ry);
+            d = sqrt_dist2((double)((float)rx * (float)rx) + ry * ry);
 #else
-        const double d = sqrt_dist2(rx * rx + ry * ry);
+            d = sqrt_dist2(rx * rx + ry * ry);
 #endif
+            if constexpr (kMirror) dk[o] = d;
+        } else {
+            d = mirror_fetch<N>(dk[N - 2 - o], st.base + other_index(st.i, o, N));
+        }
         const bool other = present && (rjf >= 0.0f);
         bool collides = other;
         if (SW) {

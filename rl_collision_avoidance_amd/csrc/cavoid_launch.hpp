@@ -55,8 +55,14 @@ namespace cavoid {
 template <int... Ns>
 struct NList {};
 #ifdef CAVOID_DEV_ONLY_N   /* development builds: instantiate a few sizes only (compile time) */
-using EnvNs = NList<4, 10>;                 // env_kernel, env_pipe_kernel, ahead_fill_kernel, actor_kernel, step_push_kernel
-using RelayNs = NList<4>;                   // env_relay_kernel
+#ifndef CAVOID_DEV_ENV_NS  /* ... these, unless the build names its own (-DCAVOID_DEV_ENV_NS=3,4,5: build.build_plain_dist) */
+#define CAVOID_DEV_ENV_NS 4, 10
+#endif
+#ifndef CAVOID_DEV_RELAY_NS
+#define CAVOID_DEV_RELAY_NS 4
+#endif
+using EnvNs = NList<CAVOID_DEV_ENV_NS>;     // env_kernel, env_pipe_kernel, ahead_fill_kernel, actor_kernel, step_push_kernel
+using RelayNs = NList<CAVOID_DEV_RELAY_NS>; // env_relay_kernel
 using QuadNs = NList<4>;                    // env_quad_kernel
 #else
 using EnvNs = NList<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>;

@@ -394,6 +394,54 @@ __device__ __forceinline__ void relay_load_args(T &dst, const __attribute__((add
     for (int k = 0; k < (int)(sizeof(T) / 4); ++k) d[k] = w[k];
     __builtin_memcpy(&dst, d, sizeof(T));
 }
+// A role's own copy of the kernel's arguments and the tile geometry made from them (env_relay_kernel): loaded from the kernel-argument
+// segment through a pointer the compiler cannot trace to the kernel's parameters, inside the role's branch -- ONE batch of scalar loads
+// of the fields the role reads (the rest of the structs is dead and never loaded), one wait in front of the first use, nothing live in
+// scalar registers (or spilled to lanes) on behalf of another role.  -DCAVOID_RELAY_ROLE_ARGS=0: the kernel's parameters themselves.
+#ifndef CAVOID_RELAY_ROLE_ARGS
+#define CAVOID_RELAY_ROLE_ARGS 1
+#endif
+typedef const __attribute__((address_space(4))) RelayArgs *RelayArgP;
+#if CAVOID_RELAY_ROLE_ARGS
+#define RELAY_ROLE_ARGS_LOAD()                                                                         \
+    unsigned long long kp_ = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();               \
+    asm volatile("" : "+s"(kp_));                                                                      \
+    KCfg c; KState s; const PoolRec *pool; KIO io;                                                     \
+    relay_load_args(s, &((RelayArgP)kp_)->s); relay_load_args(io, &((RelayArgP)kp_)->io);               \
+    relay_load_args(c, &((RelayArgP)kp_)->c); relay_load_args(pool, &((RelayArgP)kp_)->pool);            \
+    asm volatile("" : "+s"(c.wpw), "+s"(c.num_worlds))      /* (the geometry's words belong to the batch: not sunk behind a branch or the barrier) */
+/* pins argument words a role's first memory accesses start from into its batch of loads (left alone the compiler sinks their loads
+   into the `active` branch: a second, serial trip to the argument segment in front of the first global load) */
+#define RELAY_ROLE_PIN(...) asm volatile("" : __VA_ARGS__)
+#define RELAY_ROLE_STATE(name)                                                                         \
+    unsigned long long kps_ = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();              \
+    asm volatile("" : "+s"(kps_));                                                                     \
+    KState name;                                                                                       \
+    relay_load_args(name, &((RelayArgP)kps_)->s)
+#else
+#define RELAY_ROLE_ARGS_LOAD() const KCfg &c = c_; const KState &s = s_; const PoolRec *const pool = pool_; const KIO &io = io_
+#define RELAY_ROLE_STATE(name) const KState &name = s_
+#define RELAY_ROLE_PIN(...) do { } while (0)
+#endif
+#define RELAY_ROLE_ARGS()                                                                              \
+    RELAY_ROLE_ARGS_LOAD();                                                                            \
+    (void)s; (void)pool;                                                                               \
+    [[maybe_unused]] const int ostride = io.obs_stride;                                                \
+    [[maybe_unused]] const int tile_floats = (c.tile_rows * ostride + 3) & ~3;                         \
+    const int wpw = c.wpw, lanes_used = wpw * N;                                                       \
+    [[maybe_unused]] const int64_t wave = blockIdx.x;      /* one tile per workgroup */                \
+    const int64_t w0 = wave * wpw;                                                                     \
+    const int lw = lane0 / N;                                                                          \
+    [[maybe_unused]] const int i0 = lane0 - lw * N;                                                    \
+    [[maybe_unused]] const int64_t w = w0 + lw;                                                        \
+    [[maybe_unused]] const bool active = lane0 < lanes_used && w < c.num_worlds;                       \
+    [[maybe_unused]] const int base0 = lane0 < lanes_used ? lw * N : 0;                                \
+    [[maybe_unused]] const int64_t a_idx0 = w * N + i0;                                                \
+    [[maybe_unused]] const bool packed = io.packed != 0;                                               \
+    [[maybe_unused]] int64_t worlds_here = c.num_worlds - w0;                                          \
+    if (worlds_here > wpw) worlds_here = wpw;                                                          \
+    if (worlds_here < 0) worlds_here = 0;                                                              \
+    [[maybe_unused]] const int n_steps = io.n_steps
 template <int N>
 __device__ __forceinline__ void relay_coop_last(unsigned char *smem) {
     unsigned char *sp = smem + lds_floats_block() * sizeof(float);
@@ -532,7 +580,7 @@ __device__ __forceinline__ void relay_topup() {
 }
 
 template <int N>
-__global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopupMaxN ? 4 : 1) env_relay_kernel(const KCfg c, const KState s, const PoolRec *pool, const KIO io) {
+__global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopupMaxN ? 4 : 1) env_relay_kernel(const KCfg c_, const KState s_, const PoolRec *pool_, const KIO io_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *sp = smem;
     double *lds_tab = reinterpret_cast<double *>(sp); sp += lds_floats_block() * sizeof(float);
@@ -545,24 +593,12 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
     RelayCoop<N> *coopb = reinterpret_cast<RelayCoop<N> *>(sp); sp += relay_coop_bytes<N>();   // (N < kRelayCoopFromN: nothing, never touched)
     float *tiles = reinterpret_cast<float *>(sp);
 
-    const int NC = (blockDim.x >> 6) - 3 - (io.ahead_hi ? 1 : 0);   // (a launch with the top-up has one wavefront more)
+    // In front of the role branch: only what decides the role (block size, thread id, whether the launch carries the top-up) and what D
+    // zeroes.  Everything else -- the arguments a role uses and the tile geometry made from them -- each role loads and derives for itself
+    // (RELAY_ROLE_ARGS), so that no wavefront loads, keeps or spills what only another role reads.
+    const int NC = (blockDim.x >> 6) - 3 - (io_.ahead_hi ? 1 : 0);   // (a launch with the top-up has one wavefront more)
     const int role = relay_role_of(threadIdx.x >> 6, NC);   // 0 D, 1 P, 2 .. 1+NC consumers, 2+NC L, 3+NC T
     const int lane0 = threadIdx.x & 63;
-    const int ostride = io.obs_stride;
-    const int tile_floats = (c.tile_rows * ostride + 3) & ~3;
-    const int wpw = c.wpw, lanes_used = wpw * N;
-    const int64_t wave = blockIdx.x;                       // one tile per workgroup
-    const int64_t w0 = wave * wpw;
-    const int lw = lane0 / N, i0 = lane0 - lw * N;
-    const int64_t w = w0 + lw;
-    const bool active = lane0 < lanes_used && w < c.num_worlds;
-    const int base0 = lane0 < lanes_used ? lw * N : 0;
-    const int64_t a_idx0 = w * N + i0;
-    const bool packed = io.packed != 0;
-    int64_t worlds_here = c.num_worlds - w0;
-    if (worlds_here > wpw) worlds_here = wpw;
-    if (worlds_here < 0) worlds_here = 0;
-    const int n_steps = io.n_steps;
     constexpr bool kCoop = N >= kRelayCoopFromN;            // the last step's observation: D, P and L together (below the roles)
     const bool coop_role = role < 2 || role == 2 + NC;      // (the consumers are still at their own steps when the last one is settled)
 
@@ -578,6 +614,9 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
     if (role == 0) {
         // ================================================ D: state owner =====================================================
         __builtin_amdgcn_s_setprio(CAVOID_RELAY_PRIO_D);
+        RELAY_ROLE_ARGS();
+        RELAY_ROLE_PIN("+s"(s.px), "+s"(s.py), "+s"(s.heading), "+s"(s.t_rem), "+s"(s.gx), "+s"(s.gy), "+s"(s.radius), "+s"(s.pref), "+s"(s.flags),
+                       "+s"(s.episode), "+s"(io.actions), "+s"(c.action_table));   // the state, step 0's action and the table leave first
         RELAY_MARK(20);                                    // D: kernel entry
         KCfg cd = c;                                        // this role's constants, pinned in scalar registers (see P)
         asm volatile("" : "+s"(cd.dt), "+s"(cd.near_goal_sq), "+s"(cd.actions_fp32), "+s"(cd.dynamics),
@@ -750,20 +789,22 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
         RELAY_MARK(23);                                    // D: last step settled
         relay_post(&seq->stage, n_steps + 1);               // (the loader may leave: no restart is waiting for a record any more)
         // ---- state write-back (once per launch) ------------------------------------------------------------------------------
+        RELAY_ROLE_STATE(sw);                               // (the state's pointers, loaded again: eleven of them are not kept across the loop)
         if (restarted_any) {
-            store_agent(s, a_idx0, S);
-            if (i0 == 0) s.episode[w] = episode;
+            store_agent(sw, a_idx0, S);
+            if (i0 == 0) sw.episode[w] = episode;
         } else if (present_first) {
             if (moved_any) {
-                s.px[a_idx0] = S.px; s.py[a_idx0] = S.py; s.heading[a_idx0] = S.heading; s.t_rem[a_idx0] = S.t_rem;
+                sw.px[a_idx0] = S.px; sw.py[a_idx0] = S.py; sw.heading[a_idx0] = S.heading; sw.t_rem[a_idx0] = S.t_rem;
             }
-            s.speed[a_idx0] = S.speed;
-            s.flags[a_idx0] = S.flags;
+            sw.speed[a_idx0] = S.speed;
+            sw.flags[a_idx0] = S.flags;
         }
         RELAY_MARK(24);                                    // D: write-back issued
     } else if (role == 1) {
         // ================================================ P: pair pass, rewards, done ==========================================
         __builtin_amdgcn_s_setprio(CAVOID_RELAY_PRIO_P);
+        RELAY_ROLE_ARGS();
         // the constants of this role, pinned in scalar registers for the whole loop (left to itself the compiler re-loads
         // them from the kernel-argument segment inside the reward branches: seven scalar loads + waits on the loop-carried chain)
         KCfg cp = c;
@@ -793,12 +834,21 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
             double min_gap = INFINITY;
             const double ri = (double)a.radius;
             RELAY_STAMP(12);                               // P: own state read
+            constexpr int kOwn = mirror_computed<N>();      // the slots from here on: the mirror lane's distance (mirror_fetch, cavoid_kernels.hpp)
+            constexpr bool kMirror = kOwn < N - 1;
+            double dk[kMirror ? kOwn : 1];                  // the computed slots' distances, for the fetches
 #pragma unroll
             for (int o = 0; o < ((CAVOID_RELAY_ABL & 2) ? 0 : N - 1); ++o) {
                 const int j = base + other_index(i, o, N);
                 const float rjf = tent->r[j];
-                const double rx = tent->px[j] - a.px, ry = tent->py[j] - a.py;
-                const double d = sqrt_dist2(rx * rx + ry * ry);
+                double d;
+                if (!kMirror || o < kOwn) {
+                    const double rx = tent->px[j] - a.px, ry = tent->py[j] - a.py;
+                    d = sqrt_dist2(rx * rx + ry * ry);
+                    if constexpr (kMirror) dk[o] = d;
+                } else {
+                    d = mirror_fetch<N>(dk[N - 2 - o], j);
+                }
                 const bool other = present && (rjf >= 0.0f);
                 const double gap_c = d - (ri + (double)rjf);          // pair_pass: the unordered-pair gap
                 min_gap = other ? fmin(min_gap, gap_c) : min_gap;
@@ -836,6 +886,8 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
     } else if (role == 2 + NC) {
         // ================================================ L: actions and pool records ==========================================
         __builtin_amdgcn_s_setprio(CAVOID_RELAY_PRIO_L);
+        RELAY_ROLE_ARGS();
+        RELAY_ROLE_PIN("+s"(s.episode), "+s"(io.actions), "+s"(io.action_stride), "+s"(c.num_actions));
         RELAY_MARK(25);                                    // L: kernel entry
         uint32_t ep = 0u;
         if (active) ep = s.episode[w];
@@ -926,6 +978,7 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
     } else {
         // ================================================ C: observation of every NC-th step ===================================
         __builtin_amdgcn_s_setprio(CAVOID_RELAY_PRIO_C);
+        RELAY_ROLE_ARGS();
         KCfg cc = c;                                        // this role's switch word, pinned like the other roles' constants
         asm volatile("" : "+s"(cc.switches));
         const int cid = role - 2;
