@@ -517,8 +517,9 @@ int cavoid_policy_forward_rows(cavoid_policy *p, const float *x, int64_t rows, i
  * Forward + loss + the row-local part of the backward pass of the same network, for a batch of training rows
  * (x [rows, row_stride], y_r [rows] n-step returns, a_idx int32 [rows] actions taken), in two launches on the matrix
  * cores.  Needs cavoid_policy_load(with_backward = 1).  It leaves, in caller-owned buffers, the operand pair of every
- * weight-gradient GEMM (the layer's input rows and the gradient at its output rows); the caller forms X^T G with its GEMM
- * library, sums the bias gradients and takes the optimiser step:
+ * weight-gradient GEMM (the layer's input rows and the gradient at its output rows).  A caller either finishes the step inside the
+ * library -- cavoid_policy_weight_grads + cavoid_policy_apply, section 'the rest of the trainer step' below -- or forms X^T G with its
+ * own GEMM library, sums the bias gradients and takes the optimiser step itself:
  *   d fullyconnected1 = z2^T g3,  d layer2 = z1^T g2,  d layer1 (rows in packed order: 64 hidden, 4 host) = l1_in^T g1,
  *   d [logits_p | logits_v] = z3^T gh,  d lstm (rows: 64 hidden then 7 inputs; gate columns in packed order
  *   64w + 16 gate + u for unit 16w + u) = sum_t h_in[t]^T gl[t];   bias gradients (column sums of g3, g2, g1, gh, gl) come back in `db`.
@@ -604,6 +605,67 @@ int cavoid_policy_train_regression(cavoid_policy *p, const float *x, int64_t row
                                    const int32_t *a_idx, const cavoid_policy_train_buffers *buffers, void *stream);
 int cavoid_policy_train_regression_ws(cavoid_policy *p, const float *x, int64_t rows, int64_t row_stride, const float *y_r,
                                       const int32_t *a_idx, const cavoid_policy_train_ws_buffers *buffers, void *stream);
+
+/* ---- the rest of the trainer step (Server.train_model's tail: the weight gradients, NetworkVPCore.py:104-122's optimiser with
+ * USE_GRAD_CLIP, and the weight hand-over to the predictors) for the LSTM network, so that a caller without a GEMM library or an
+ * optimiser of its own trains through this header alone:
+ *     cavoid_policy_train (or _train_regression)  ->  cavoid_policy_weight_grads  ->  [the caller's all-reduce of grads_flat]  ->  cavoid_policy_apply
+ *
+ * ONE flat parameter vector.  cavoid_policy_param_layout (host code only: no handle, no device) defines it: the CAVOID_POLICY_PARAMS = 12
+ *   variables in the order of cavoid_policy_weights' pointers -- lstm_kernel, lstm_bias, layer1_kernel, layer1_bias, layer2_kernel,
+ *   layer2_bias, fc1_kernel, fc1_bias, p_kernel, p_bias, v_kernel, v_bias -- each in the checkpoint's shape (row-major), each starting
+ *   on a multiple of 64 floats: variable i occupies [offsets[i], offsets[i] + sizes[i]), *total = the end of the last one.  The
+ *   floats between two variables are padding: the calls below write zeros there (gradients) or leave them alone (optimiser state).
+ *   Gradients, both optimiser state vectors and a multi-GPU all-reduce use this layout.  max_other 1..64, num_actions 1..15, else CAVOID_EINVAL.
+ *
+ * cavoid_policy_weight_grads: every weight and bias gradient of the pass that just filled `buffers`, into grads_flat [total] in that layout --
+ *   the five contractions listed above on the float32 matrix instructions (exact float32 products, float32 accumulation) with the
+ *   un-permutations in the epilogue (packed gate columns and the "64 hidden, inputs, pad" row order of the LSTM and layer1 back to the
+ *   checkpoint's [7 + 64] / [4 + 64], the [256, 16] head block split into logits_p [256, A] and logits_v [256, 1], db into the six biases).
+ *   Two launches, whatever max_other and the row count: the rows are cut into slices of 1 024 (the LSTM's max_other * capacity_rows rows:
+ *   of 1 024, or 4 096 once there are more than 4 194 304 of them), one wavefront forms one 64 x 64 (or edge) tile of one slice's partial
+ *   product in `scratch`, and a second launch sums the partials of every entry in slice order and writes it where it belongs.  The
+ *   partition depends on capacity_rows and max_other only and there are no floating-point atomics: two calls on the same buffers give
+ *   the same bits.  The longest accumulation chain is the slice length plus the number of slices.
+ *   scratch: device memory of at least the floats cavoid_policy_weight_grads_scratch reports for this handle and capacity_rows, 16-byte
+ *   aligned like every per-row buffer (CAVOID_EINVAL otherwise, as for a NULL pointer, a wrong struct_size or a capacity_rows that is
+ *   not a positive multiple of 64).  ALL capacity_rows rows are read: call it after a pass that wrote them (a pass over rows = 0 rows
+ *   launches nothing and writes none).  Both LSTM handle kinds (max_other 1..19 and crowd handles, 20..64); CAVOID_EUNSUPPORTED on a
+ *   weight-sharing handle.
+ *
+ * cavoid_policy_apply: one optimiser step on the float32 MASTER weights and the re-pack.  `weights`: the struct of cavoid_policy_load whose
+ *   twelve variable pointers are the masters (device memory the caller owns; updated IN PLACE although the struct says const), with
+ *   min_policy / forget_bias / with_backward / avg / std as the caller would load them.  opt->kind:
+ *     CAVOID_OPT_ADAM     m = b1 m + (1 - b1) g,  v = b2 v + (1 - b2) g^2,  w -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ *                         (decay1 = b1, decay2 = b2, state1 = m, state2 = v, t = *step + 1: torch.optim.Adam without amsgrad / weight decay)
+ *     CAVOID_OPT_RMSPROP  ms = rho ms + (1 - rho) g^2,  mom = mu mom + lr g / sqrt(ms + eps),  w -= mom
+ *                         (decay1 = rho, decay2 = mu, state1 = ms, state2 = mom: tf.train.RMSPropOptimizer, not centred, eps INSIDE the
+ *                         root; the caller initialises ms to ones as TensorFlow does)
+ *   clip_average_norm = c > 0 (tf.clip_by_average_norm, GRAD_CLIP_NORM): per variable g <- g * c / max(||g||_2 / n, c), n its element
+ *   count, applied to what the update reads; grads_flat itself is not modified.  c = 0: off.  lr is passed by value (the reference
+ *   anneals it per step); the coefficients are formed in double and rounded to float32 once, the element arithmetic is float32.
+ *   state1 / state2: device float [total]; step: device int64, read as t - 1 and written back as t by one thread.  Launches: one for the
+ *   update, one more in front of it for the twelve norms when clipping (a fixed-order reduction per variable); then exactly
+ *   cavoid_policy_load on the updated masters on the same stream -- the handle afterwards is, bit for bit, what a fresh load gives.
+ *   CAVOID_EINVAL: NULL pointers, wrong struct sizes, an unknown kind, a negative clip; CAVOID_EUNSUPPORTED: a weight-sharing handle. */
+#define CAVOID_POLICY_PARAMS 12
+enum { CAVOID_OPT_ADAM = 0, CAVOID_OPT_RMSPROP = 1 };
+typedef struct cavoid_policy_optimizer {
+    int32_t struct_size;             /* sizeof(cavoid_policy_optimizer) */
+    int32_t kind;                    /* CAVOID_OPT_* */
+    double lr;
+    double decay1, decay2;           /* Adam: beta1, beta2; RMSProp: decay rho, momentum mu */
+    double eps;
+    double clip_average_norm;        /* 0 = off */
+    float *state1, *state2;          /* [total] each */
+    int64_t *step;                   /* [1] optimiser steps taken so far */
+} cavoid_policy_optimizer;
+int cavoid_policy_param_layout(int32_t max_other, int32_t num_actions, int64_t *offsets, int64_t *sizes, int64_t *total);
+int cavoid_policy_weight_grads_scratch(const cavoid_policy *p, int64_t capacity_rows, int64_t *floats);
+int cavoid_policy_weight_grads(cavoid_policy *p, const cavoid_policy_train_buffers *buffers, float *scratch, int64_t scratch_floats,
+                               float *grads_flat, void *stream);
+int cavoid_policy_apply(cavoid_policy *p, const cavoid_policy_weights *weights, const cavoid_policy_optimizer *opt, const float *grads_flat,
+                        void *stream);
 
 /* kernel timing helper: HIP events recorded on `stream` around the launches of the calls made
  * between begin and end; end synchronises and returns elapsed milliseconds */

@@ -74,6 +74,18 @@ class CavoidPolicyTrainWsBuffers(C.Structure):
         (n, C.c_void_p) for n in ("z1", "z2", "z3", "l1_in", "f_in", "gh", "loss", "g1", "g2", "g3", "gf", "db")]
 
 
+POLICY_PARAMS = 12       # CAVOID_POLICY_PARAMS: the variables of the flat parameter vector, in this order (cavoid_policy_param_layout)
+POLICY_PARAM_NAMES = ("lstm_kernel", "lstm_bias", "layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel", "fc1_bias",
+                      "p_kernel", "p_bias", "v_kernel", "v_bias")
+OPT_ADAM, OPT_RMSPROP = 0, 1
+
+
+class CavoidPolicyOptimizer(C.Structure):
+    """Mirror of ``struct cavoid_policy_optimizer`` (include/cavoid.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("lr", C.c_double), ("decay1", C.c_double), ("decay2", C.c_double),
+                ("eps", C.c_double), ("clip_average_norm", C.c_double), ("state1", C.c_void_p), ("state2", C.c_void_p), ("step", C.c_void_p)]
+
+
 class CavoidRolloutBuffers(C.Structure):
     """Mirror of ``struct cavoid_rollout_buffers`` (include/cavoid.h): the experience store handed to ``cavoid_actor_run``."""
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32)] + [
@@ -160,6 +172,10 @@ SYMBOLS = [
     ("cavoid_policy_train_ws", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_float, C.c_float, C.POINTER(CavoidPolicyTrainWsBuffers), _P]),
     ("cavoid_policy_train_regression", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(CavoidPolicyTrainBuffers), _P]),
     ("cavoid_policy_train_regression_ws", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.POINTER(CavoidPolicyTrainWsBuffers), _P]),
+    ("cavoid_policy_param_layout", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("cavoid_policy_weight_grads_scratch", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("cavoid_policy_weight_grads", C.c_int, [_P, C.POINTER(CavoidPolicyTrainBuffers), _P, C.c_int64, _P, _P]),
+    ("cavoid_policy_apply", C.c_int, [_P, C.POINTER(CavoidPolicyWeights), C.POINTER(CavoidPolicyOptimizer), _P, _P]),
     ("cavoid_timer_begin", C.c_int, [_P, _P]),
     ("cavoid_timer_end", C.c_int, [_P, _P, C.POINTER(C.c_float)]),
 ]
@@ -199,6 +215,13 @@ def lib():
             raise ImportError("libcavoid_hip.so ABI %d != binding ABI %d" % (handle.cavoid_abi_version(), ABI_VERSION))
         _lib = handle
     return _lib
+
+
+def policy_param_layout(max_other: int, num_actions: int):
+    """``cavoid_policy_param_layout``: (offsets, sizes, total) of the flat parameter vector, in floats; entry i is POLICY_PARAM_NAMES[i]."""
+    off, size, total = (C.c_int64 * POLICY_PARAMS)(), (C.c_int64 * POLICY_PARAMS)(), C.c_int64()
+    check(lib().cavoid_policy_param_layout(max_other, num_actions, off, size, C.byref(total)), "cavoid_policy_param_layout")
+    return list(off), list(size), int(total.value)
 
 
 def check(code: int, where: str) -> None:

@@ -34,6 +34,8 @@ struct cavoid_policy {
     int32_t *step_counter = nullptr;
     uint32_t *clamped_weights = nullptr;   // device counter: weights the float16 split saturated at the last cavoid_policy_load
     uint32_t *blocks_done = nullptr, *cu_tickets = nullptr;
+    float *clip_scale = nullptr;     // [16] per-variable gradient scales of cavoid_policy_apply's clip (cavoid_policy_step.hip)
+    uint32_t *apply_ticket = nullptr; // ... and its workgroup ticket: the last workgroup of the update launch writes the step count
     int row_tiles = 4;               // 16-row tiles per workgroup (64 rows, 2 workgroups per CU); the 32-row / 4-per-CU
                                      // instantiation was measured and dropped: 175 vs 132 us
 };
@@ -70,7 +72,7 @@ inline int policy_new_handle(int32_t max_other, int32_t num_actions, int device,
     const size_t o_sfrag = carve(with_split ? (size_t)kSpPackFrags8 * sizeof(uint4) : 0), o_sbias = carve(with_split ? kBiasFloats8 * sizeof(float) : 0);
     const size_t o_avg = carve(h->in_size * sizeof(float)), o_std = carve(h->in_size * sizeof(float));
     const size_t o_step = carve(sizeof(int32_t)), o_done = carve(sizeof(uint32_t)), o_tick = carve(kPolCuSlots * sizeof(uint32_t));
-    const size_t o_clamp = carve(sizeof(uint32_t));
+    const size_t o_clamp = carve(sizeof(uint32_t)), o_clip = carve(16 * sizeof(float)), o_ticket = carve(sizeof(uint32_t));
     if (hipMalloc(&h->slab, off) != hipSuccess) { delete h; return CAVOID_ENOMEM; }
     if (hipMemset(h->slab, 0, off) != hipSuccess) { g_last_hip_error = (int)hipGetLastError(); (void)hipFree(h->slab); delete h; return CAVOID_EHIP; }
     unsigned char *b = static_cast<unsigned char *>(h->slab);
@@ -80,6 +82,8 @@ inline int policy_new_handle(int32_t max_other, int32_t num_actions, int device,
     h->step_counter = reinterpret_cast<int32_t *>(b + o_step); h->blocks_done = reinterpret_cast<uint32_t *>(b + o_done);
     h->cu_tickets = reinterpret_cast<uint32_t *>(b + o_tick);
     h->clamped_weights = reinterpret_cast<uint32_t *>(b + o_clamp);
+    h->clip_scale = reinterpret_cast<float *>(b + o_clip);
+    h->apply_ticket = reinterpret_cast<uint32_t *>(b + o_ticket);
     if (hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->num_cus <= 0) h->num_cus = 256;
     *out = h;
     return CAVOID_OK;

@@ -99,17 +99,8 @@ class FusedPolicy(object):
         costs a stream synchronisation): fail loudly when a weight lies beyond the float16 split's +-65504 instead of running a
         network that silently differs from the reference's float32 predictor."""
         n = self.net
-        w = _lib.CavoidPolicyWeights()
-        w.struct_size = C.sizeof(_lib.CavoidPolicyWeights)
-        w.min_policy, w.forget_bias = float(n.min_policy), self.forget_bias
-        w.with_backward = 1 if with_backward else 0
+        w = self.weights_struct(with_backward)
         ptr = lambda t: C.c_void_p(self._f32(t).data_ptr())
-        self._keep = []                  # tensors that had to be made contiguous stay alive until the next refresh
-        if n.normalize:
-            w.avg, w.std = ptr(n.avg), ptr(n.std)
-        names = ("layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel", "fc1_bias", "p_kernel", "p_bias", "v_kernel", "v_bias")
-        for name in names if self.ws else ("lstm_kernel", "lstm_bias") + names:      # (weight_sharing: the lstm fields stay NULL)
-            setattr(w, name, ptr(getattr(n, name)))
         if self.ws:
             _lib.check(self._lib.cavoid_policy_load_ws(self._h, C.byref(w), ptr(n.other_kernel), ptr(n.other_bias), self._stream()),
                        "cavoid_policy_load_ws")
@@ -122,6 +113,23 @@ class FusedPolicy(object):
                           if self.crowd else "CAVOID_POLICY_PRODUCTS=3 (bf16 pieces, float32's range) or CAVOID_POLICY_F32=1")
                 raise ValueError("%d weight(s) lie beyond +-65504 (after the LSTM gates' log2 e scale): the default float16-split inference "
                                  "form would clamp them.  Create the policy with %s in the environment." % (bad, escape))
+
+    def weights_struct(self, with_backward: bool = False) -> "_lib.CavoidPolicyWeights":
+        """``cavoid_policy_weights`` over the module's current parameters (what ``refresh`` loads).  Parameters that are not contiguous
+        float32 on the device are handed over as copies, kept alive in ``_keep`` until the next call."""
+        n = self.net
+        w = _lib.CavoidPolicyWeights()
+        w.struct_size = C.sizeof(_lib.CavoidPolicyWeights)
+        w.min_policy, w.forget_bias = float(n.min_policy), self.forget_bias
+        w.with_backward = 1 if with_backward else 0
+        ptr = lambda t: C.c_void_p(self._f32(t).data_ptr())
+        self._keep = []                  # tensors that had to be made contiguous stay alive until the next refresh
+        if n.normalize:
+            w.avg, w.std = ptr(n.avg), ptr(n.std)
+        names = ("layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel", "fc1_bias", "p_kernel", "p_bias", "v_kernel", "v_bias")
+        for name in names if self.ws else ("lstm_kernel", "lstm_bias") + names:      # (weight_sharing: the lstm fields stay NULL)
+            setattr(w, name, ptr(getattr(n, name)))
+        return w
 
     def _f32(self, t: torch.Tensor) -> torch.Tensor:
         t = t.detach()
@@ -170,6 +178,88 @@ class FusedPolicy(object):
         return a, p, v
 
 
+# the reference's optimiser options (NetworkVPCore.py:104-122): RMSPROP_DECAY / RMSPROP_MOMENTUM / RMSPROP_EPSILON of Config.py, GRAD_CLIP_NORM
+RMSPROP_DEFAULTS = {"decay": 0.99, "momentum": 0.0, "eps": 0.1}
+GRAD_CLIP_NORM = 40.0
+# the row slices of cavoid_policy_weight_grads (kStepDenseSlice, kStepLstmSlice, kStepLstmSliceWide, kStepLstmWideFrom of
+# cavoid_policy_step.hpp -- tests/test_policy_step_host.py holds the scratch size they give to the library's own answer)
+STEP_DENSE_SLICE, STEP_LSTM_SLICE, STEP_LSTM_SLICE_WIDE, STEP_LSTM_WIDE_FROM = 1024, 1024, 4096, 4194304
+
+
+def step_partition(max_others: int, rows: int) -> Tuple[int, int, int]:
+    """(dense slices, LSTM slice length, LSTM slices) of ``cavoid_policy_weight_grads`` over ``rows`` buffer rows."""
+    t = rows * max_others
+    lstm_len = STEP_LSTM_SLICE_WIDE if t > STEP_LSTM_WIDE_FROM else STEP_LSTM_SLICE
+    return -(-rows // STEP_DENSE_SLICE), lstm_len, -(-t // lstm_len)
+
+
+class DeviceStepOptimizer(object):
+    """What ``FusedA3CTrainer(device_step=True).opt`` is: the optimiser whose step is ``cavoid_policy_apply`` -- flat float32 state vectors in
+    the layout of ``cavoid_policy_param_layout``, a device step count -- behind the part of ``torch.optim.Optimizer``'s surface the training
+    loop and the checkpoints use: ``param_groups`` (``lr`` is read from group 0 at every step), ``step``, ``zero_grad``, ``state_dict`` /
+    ``load_state_dict``.  'adam': the state dict is ``torch.optim.Adam``'s own, both ways, so a run resumes with or without the device
+    step.  'rmsprop': its own format, marked ``"kind": "rmsprop"``."""
+
+    def __init__(self, trainer: "FusedA3CTrainer", kind: str, adam: torch.optim.Adam, learning_rate: float):
+        self._trainer, self.kind, self._adam = trainer, kind, adam
+        total, dev = trainer._layout[2], trainer.device
+        self.state1 = torch.zeros(total, dtype=torch.float32, device=dev)      # Adam: exp_avg; RMSProp: ms
+        self.state2 = torch.zeros(total, dtype=torch.float32, device=dev)      # Adam: exp_avg_sq; RMSProp: mom
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        if kind == "rmsprop":
+            for v in trainer._views(self.state1).values():                        # TensorFlow's RMSProp starts ms at ones (the padding stays 0)
+                v.fill_(1.0)
+            self.param_groups = [dict(RMSPROP_DEFAULTS, lr=float(learning_rate))]
+        else:
+            self.param_groups = adam.param_groups
+
+    def step(self) -> None:
+        self._trainer._apply()
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        self._trainer._flat_grads.zero_()
+
+    def state_dict(self) -> dict:
+        step = int(self.step_count.item())
+        if self.kind == "rmsprop":
+            return {"kind": "rmsprop", "state": {"ms": self.state1.clone(), "mom": self.state2.clone(), "step": step},
+                    "param_groups": [dict(g) for g in self.param_groups]}
+        t, adam = self._trainer, self._adam
+        adam.state.clear()
+        if step > 0:
+            m, v = t._views(self.state1), t._views(self.state2)
+            for name, prm in t.net.named_parameters():
+                adam.state[prm] = {"step": torch.tensor(float(step), dtype=torch.float32, device=t.device),
+                                   "exp_avg": m[name].clone(), "exp_avg_sq": v[name].clone()}
+        return adam.state_dict()
+
+    def load_state_dict(self, sd: dict) -> None:
+        kind = sd.get("kind", "adam")
+        if kind != self.kind:
+            raise ValueError("the optimizer state is %s's, this trainer steps with %s" % (kind, self.kind))
+        t = self._trainer
+        if self.kind == "rmsprop":
+            self.state1.copy_(sd["state"]["ms"])
+            self.state2.copy_(sd["state"]["mom"])
+            self.step_count.fill_(int(sd["state"]["step"]))
+            for g, saved in zip(self.param_groups, sd["param_groups"]):
+                g.update(saved)
+            return
+        adam = self._adam
+        adam.load_state_dict(sd)
+        self.param_groups = adam.param_groups
+        self.state1.zero_()
+        self.state2.zero_()
+        m, v, step = t._views(self.state1), t._views(self.state2), 0
+        for name, prm in t.net.named_parameters():
+            st = adam.state.get(prm)
+            if st:
+                m[name].copy_(st["exp_avg"])
+                v[name].copy_(st["exp_avg_sq"])
+                step = int(st["step"])
+        self.step_count.fill_(step)
+
+
 class FusedA3CTrainer(object):
     """``Server.train_model`` (/root/reference/ga3c/GA3C/Server.py:114-124) with the network's forward pass, the A3C loss
     (NetworkVPCore.py:71-100) and the row-local half of the backward pass as two MFMA kernel launches
@@ -183,11 +273,29 @@ class FusedA3CTrainer(object):
     ``ws_crowd=True`` (opt-in; profiles/policy_wsring_timing.txt) does the same for a 'weight_sharing' network of MAX_OTHERS_WS + 1 ..
     MAX_OTHERS_WS_CROWD neighbours: ``cavoid_policy_train_ws`` on a ``FusedPolicy(net, ws_crowd=True)``, whose forward launch is the ring kernel
     of cavoid_policy_wsring.hpp (tests/test_gpu_policy_wsring.py); a ``policy`` that is already such a one has the same effect.  544 bytes per
-    buffer row and neighbour."""
+    buffer row and neighbour.
+    ``device_step=True`` (opt-in, 'rnn' only; profiles/policy_device_step_timing.txt) finishes the step inside the library:
+    ``cavoid_policy_weight_grads`` forms every gradient in ONE flat tensor in the checkpoint's layout (every parameter's ``.grad`` is a view of
+    it, the multi-GPU all-reduce runs on it as it is) and ``cavoid_policy_apply`` takes the optimiser step on the module's own parameter storage
+    and re-packs the weights -- no GEMM library, no ``index_select``, no ``torch.optim`` launch behind the two trainer kernels.  With it,
+    ``optimizer="rmsprop"`` (the reference's ``tf.train.RMSPropOptimizer``: RMSPROP_DEFAULTS) and ``grad_clip=c`` (``tf.clip_by_average_norm``
+    per variable; the reference's GRAD_CLIP_NORM is 40) are available; ``opt`` is then a ``DeviceStepOptimizer``
+    (tests/test_gpu_policy_step.py)."""
 
     def __init__(self, net: NetworkVP_rnn, policy: Optional[FusedPolicy] = None, learning_rate: float = 2e-5, group=None,
-                 distributed: Optional[bool] = None, crowd: bool = False, ws_crowd: bool = False):
+                 distributed: Optional[bool] = None, crowd: bool = False, ws_crowd: bool = False, device_step: bool = False,
+                 optimizer: str = "adam", grad_clip: Optional[float] = None):
         from .network import A3CTrainer
+        if optimizer not in ("adam", "rmsprop"):
+            raise ValueError("optimizer must be 'adam' or 'rmsprop', not %r" % (optimizer,))
+        if grad_clip is not None and not float(grad_clip) > 0.0:
+            raise ValueError("grad_clip must be a positive average norm (or None), not %r" % (grad_clip,))
+        if not device_step and (optimizer != "adam" or grad_clip is not None):
+            raise ValueError("optimizer=%r / grad_clip=%r are steps of cavoid_policy_apply: they need device_step=True" % (optimizer, grad_clip))
+        if device_step and net.arch == "weight_sharing":
+            raise ValueError("device_step=True carries the 'rnn' network only: the weight_sharing network's weight gradients and optimiser "
+                             "step stay with PyTorch (cavoid_policy_weight_grads is CAVOID_EUNSUPPORTED on a weight-sharing handle)")
+        self.device_step, self.optimizer, self.grad_clip = bool(device_step), optimizer, (float(grad_clip) if grad_clip is not None else None)
         self.ws = net.arch == "weight_sharing"          # cavoid_policy_train_ws (limit: FusedPolicy's MAX_OTHERS_WS, or _WS_CROWD)
         self.crowd = bool(crowd) and not self.ws and net.max_others > MAX_OTHERS
         # a weight-sharing network above MAX_OTHERS_WS: when asked to, or when the policy handed over already runs the ring kernels
@@ -222,6 +330,55 @@ class FusedA3CTrainer(object):
         self._lstm_flat = (rows.unsqueeze(1) * (4 * H) + self._k_of_c.unsqueeze(0)).reshape(-1)
         self._l1_rows = torch.cat([torch.arange(H, H + net.HOST), torch.arange(0, H)]).to(self.device)
         self.policy.refresh(with_backward=True)
+        if self.device_step:
+            self._layout = _lib.policy_param_layout(net.max_others, A)          # (offsets, sizes, total) in POLICY_PARAM_NAMES order
+            self._flat_grads = torch.zeros(self._layout[2], dtype=torch.float32, device=self.device)
+            self._grad_views = self._views(self._flat_grads)
+            self._grad_scratch = {}
+            for name, prm in net.named_parameters():
+                if prm.dtype != torch.float32 or not prm.is_contiguous() or prm.device != self.device:
+                    raise ValueError("device_step=True updates the module's own storage: %s must be contiguous float32 on %s" % (name, self.device))
+                prm.grad = self._grad_views[name]
+            self.opt = DeviceStepOptimizer(self, optimizer, self._base.opt, learning_rate)
+
+    def _views(self, flat: torch.Tensor) -> dict:
+        """{parameter name: view of ``flat`` in the parameter's shape} by the layout of ``cavoid_policy_param_layout``"""
+        off, size, _ = self._layout
+        return {name: flat[o:o + n].view_as(getattr(self.net, name)) for name, o, n in zip(_lib.POLICY_PARAM_NAMES, off, size)}
+
+    def _weight_grads(self, t: dict, cbuf, rows64: int) -> None:
+        """``cavoid_policy_weight_grads`` on the buffers the launch pair just filled: every ``.grad`` (a view of the flat tensor) is set."""
+        pol = self.policy
+        gs = self._grad_scratch.get(rows64)
+        if gs is None:
+            floats = C.c_int64()
+            _lib.check(pol._lib.cavoid_policy_weight_grads_scratch(pol._h, rows64, C.byref(floats)), "cavoid_policy_weight_grads_scratch")
+            gs = self._grad_scratch[rows64] = torch.empty(int(floats.value), dtype=torch.float32, device=self.device)
+            if len(self._grad_scratch) > 4:
+                self._grad_scratch.pop(next(iter(self._grad_scratch)))
+        _lib.check(pol._lib.cavoid_policy_weight_grads(pol._h, C.byref(cbuf), C.c_void_p(gs.data_ptr()), gs.numel(),
+                                                       C.c_void_p(self._flat_grads.data_ptr()), pol._stream()), "cavoid_policy_weight_grads")
+        for name, prm in self.net.named_parameters():      # (a caller's optimiser may have dropped them: zero_grad(set_to_none=True))
+            prm.grad = self._grad_views[name]
+
+    def _apply(self) -> None:
+        """``cavoid_policy_apply``: the optimiser step on the module's parameter storage from the flat gradients, then the re-pack."""
+        pol, opt = self.policy, self.opt
+        g = opt.param_groups[0]
+        o = _lib.CavoidPolicyOptimizer()
+        o.struct_size = C.sizeof(o)
+        if opt.kind == "rmsprop":
+            o.kind, o.decay1, o.decay2, o.eps = _lib.OPT_RMSPROP, float(g["decay"]), float(g["momentum"]), float(g["eps"])
+        else:
+            o.kind, o.decay1, o.decay2, o.eps = _lib.OPT_ADAM, float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+        o.lr = float(g["lr"])
+        o.clip_average_norm = self.grad_clip if self.grad_clip is not None else 0.0
+        o.state1, o.state2, o.step = C.c_void_p(opt.state1.data_ptr()), C.c_void_p(opt.state2.data_ptr()), C.c_void_p(opt.step_count.data_ptr())
+        w = pol.weights_struct(with_backward=True)
+        if pol._keep:
+            raise ValueError("device_step=True updates the module's own storage: its parameters must stay contiguous float32 on %s" % (self.device,))
+        _lib.check(pol._lib.cavoid_policy_apply(pol._h, C.byref(w), C.byref(o), C.c_void_p(self._flat_grads.data_ptr()), pol._stream()),
+                   "cavoid_policy_apply")
 
     training_step = property(lambda self: self._base.training_step,
                              lambda self, v: setattr(self._base, "training_step", v))
@@ -286,6 +443,9 @@ class FusedA3CTrainer(object):
         loss_args = () if regression else (float(net.beta), float(net.log_epsilon))
         _lib.check(getattr(pol._lib, name)(pol._h, ptr(x), n, x.stride(0), ptr(y_r), ptr(a_idx), *loss_args,
                                            C.byref(cbuf), pol._stream()), name)
+        if self.device_step:
+            self._weight_grads(t, cbuf, rows64)
+            return t
         A, H, M = net.num_actions, net.HIDDEN, net.max_others
         xtg = self._xtg
         d_head = xtg(t["z3"], t["gh"])
@@ -313,6 +473,20 @@ class FusedA3CTrainer(object):
         Returns the loss (cost_p + cost_v) as a 0-d device tensor: nothing here waits for the GPU."""
         net, pol = self.net, self.policy
         n = int(x.shape[0])
+        if self.device_step:
+            if n == 0:                                     # (the padding step below: zero gradients, the others' all-reduced ones move the weights)
+                self._flat_grads.zero_()
+                loss = torch.zeros((), dtype=torch.float32, device=self.device)
+            else:
+                a_idx = (a.argmax(dim=1) if a.dim() == 2 else a).to(torch.int32).contiguous()
+                loss = self._pass(x.to(torch.float32).contiguous(), y_r.to(torch.float32).contiguous(), a_idx, n)["loss"].sum()
+            if self._base.distributed:
+                import torch.distributed as dist
+                dist.all_reduce(self._flat_grads, op=dist.ReduceOp.SUM, group=self._base.group)     # the flat tensor itself: no cat, no clone
+            self._apply()                                  # optimiser step + re-pack: actors and the next pass see the new weights
+            self._base.training_step += 1
+            self._base.frame_counter += n
+            return loss
         if n == 0:
             # (multi-GPU padding step: this rank has no rows, but the all-reduced gradients of the others still move its
             #  parameters -- the packed MFMA weights must follow, or this replica's actors keep acting on stale weights)
@@ -352,5 +526,6 @@ class FusedA3CTrainer(object):
         a_idx = (a.argmax(dim=1) if a.dim() == 2 else a).to(torch.int32).contiguous()
         loss = self._pass(x, y_r, a_idx, n, regression=True)["loss"].clone()       # (the scratch is the next pass's)
         (opt if opt is not None else self.opt).step()
-        pol.refresh(with_backward=True)
+        if opt is not None or not self.device_step:        # (the device step re-packs itself)
+            pol.refresh(with_backward=True)
         return loss[0], loss[1]

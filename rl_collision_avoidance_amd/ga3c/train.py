@@ -55,6 +55,10 @@ def load_checkpoint(path: str, net: NetworkVP_rnn, trainer: A3CTrainer, device) 
     if arch != net.arch or (m is not None and int(m) != net.max_others):
         raise SystemExit("%s holds a %s network observing %s neighbours; this run builds a %s network observing %d (--arch / --observed)"
                          % (path, arch, m if m is not None else "?", net.arch, net.max_others))
+    # (the optimiser's kind: an entry without one is torch.optim.Adam's state dict, whichever trainer tail wrote it)
+    kind, mine = ck.get("optimizer", {}).get("kind", "adam"), getattr(trainer, "optimizer", "adam")
+    if "optimizer" in ck and kind != mine:
+        raise SystemExit("%s holds the state of the %s optimizer; this run steps with %s (--optimizer)" % (path, kind, mine))
     net.load_state_dict(ck["model"])
     if "optimizer" in ck:
         trainer.opt.load_state_dict(ck["optimizer"])
@@ -121,6 +125,15 @@ def main(argv=None) -> None:
                          "autograd; opt-in until a whole training run has been timed with and without it (profiles/policy_wsring_timing.txt holds "
                          "one act launch and one trainer step: tools/actbench.py, tools/trainbench.py --arch weight_sharing).  "
                          "--fused-regression then takes the supervised start through them too")
+    ap.add_argument("--device-step", action="store_true",
+                    help="finish the fused 'rnn' trainer's step inside the HIP library (FusedA3CTrainer(device_step=True): cavoid_policy_weight_grads "
+                         "+ cavoid_policy_apply) instead of PyTorch's GEMMs, index_selects and torch.optim.Adam; opt-in (one step with and "
+                         "without it: tools/trainbench.py --device-step)")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "rmsprop"],
+                    help="rmsprop: the reference's tf.train.RMSPropOptimizer (decay 0.99, momentum 0.0, epsilon 0.1); needs --device-step")
+    ap.add_argument("--grad-clip", type=float, default=None, metavar="C",
+                    help="USE_GRAD_CLIP: tf.clip_by_average_norm of every variable's gradient at C (the reference's GRAD_CLIP_NORM is 40); "
+                         "needs --device-step")
     ap.add_argument("--scenario", default="ring", choices=["ring", "box"],
                     help="scenario generator: ring = GEN v1 (antipodal goals on a ring), box = GEN v2 (random starts / goals in a box "
                          "with minimum separations: the shape of the reference's get_testcase_random, TEST_CASE_FN run-ws/config.yaml:281-283)")
@@ -228,10 +241,21 @@ def main(argv=None) -> None:
                   % ("the PyTorch network" if (torch_policy or net.arch != "rnn") else "the fused crowd policy kernel", POLICY_MAX_OTHERS, M),
                   flush=True)
     fused = None if torch_policy else FusedPolicy(net, seed=1000 * args.seed + rank, ws_crowd=ws_crowd)
+    if (args.device_step or args.optimizer != "adam" or args.grad_clip is not None) and (autograd_trainer or net.arch != "rnn" or not args.device_step):
+        raise SystemExit("--device-step runs behind the fused 'rnn' trainer kernels (not --autograd-trainer, --arch weight_sharing or rows this "
+                         "run trains through autograd), and --optimizer rmsprop / --grad-clip need --device-step")
     if autograd_trainer:
         trainer = A3CTrainer(net, learning_rate=args.lr)
     else:
-        trainer = FusedA3CTrainer(net, fused, learning_rate=args.lr, crowd=crowd_trainer, ws_crowd=ws_crowd)   # shares (or creates) the packed-weight handle
+        trainer = FusedA3CTrainer(net, fused, learning_rate=args.lr, crowd=crowd_trainer, ws_crowd=ws_crowd,   # shares (or creates) the packed-weight handle
+                                  device_step=args.device_step, optimizer=args.optimizer, grad_clip=args.grad_clip)
+    if rank == 0 and not args.play:
+        if args.device_step:
+            print("trainer tail: cavoid_policy_weight_grads + cavoid_policy_apply (%s%s) inside the HIP library"
+                  % (args.optimizer, ", clip_by_average_norm %g" % args.grad_clip if args.grad_clip is not None else ""), flush=True)
+        else:
+            print("trainer tail: PyTorch (%s, torch.optim.Adam)"
+                  % ("autograd" if autograd_trainer else "library GEMMs for the weight gradients"), flush=True)
     episodes_before = 0
     if args.load:
         episodes_before = load_checkpoint(args.load, net, trainer, device)

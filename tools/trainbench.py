@@ -8,7 +8,12 @@ warm-up steps, alternating
 (learning rate 0 on both sides: the weights stay put).  Row lengths are drawn uniformly from 0 .. max_other.  The fused trainer's scratch is
 printed with each line (FusedA3CTrainer.scratch_bytes).  Figures go to profiles/policy_crowd_train_timing.txt.
 --arch weight_sharing: the same for the weight-sharing network -- above 19 observed neighbours the ring forward kernel of
-cavoid_policy_wsring.hpp, ws_crowd=True; figures go to profiles/policy_wsring_timing.txt."""
+cavoid_policy_wsring.hpp, ws_crowd=True; figures go to profiles/policy_wsring_timing.txt.
+--device-step: another pair of legs ('rnn' only; `rows` and `max_other` are ignored: 32 768 rows at M = 3, 16 384 rows at M = 19 and 63) --
+  torch tail:   FusedA3CTrainer.train as above (library GEMMs, index_selects, torch.optim.Adam, re-pack)
+  device step:  FusedA3CTrainer(device_step=True).train (cavoid_policy_weight_grads + cavoid_policy_apply behind the same launch pair)
+alternating on the same rows, and the two new calls timed apart on the buffers of the last step.  Per leg: the rounds' medians, their
+median and their spread (max - min over the rounds); figures go to profiles/policy_device_step_timing.txt."""
 import argparse
 import os
 import statistics
@@ -37,6 +42,35 @@ def median_us(fn, reps):
     return statistics.median(times)
 
 
+def device_step_legs(reps, rounds):
+    print("M   rows    torch tail step (us)           device step (us)               weight_grads (us)     apply (us)            torch / device")
+    for M, B in ((3, 32768), (19, 16384), (63, 16384)):
+        class Cfg(EnvConfig):
+            def __init__(self):
+                self.MAX_NUM_AGENTS_IN_ENVIRONMENT = M + 1
+                EnvConfig.__init__(self)
+        net_t, net_d = NetworkVP_rnn(Cfg()).cuda(), NetworkVP_rnn(Cfg()).cuda()
+        g = torch.Generator().manual_seed(0)
+        x = torch.randn((B, net_t.input_size), generator=g) * net_t.std.cpu() + net_t.avg.cpu()
+        x[:, 0] = torch.randint(0, M + 1, (B,), generator=g).float()
+        x, y, a = x.cuda(), torch.randn(B, generator=g).cuda(), torch.randint(0, net_t.num_actions, (B,), generator=g).cuda()
+        tt = FusedA3CTrainer(net_t, learning_rate=0.0, crowd=M > MAX_OTHERS)
+        td = FusedA3CTrainer(net_d, learning_rate=0.0, crowd=M > MAX_OTHERS, device_step=True)
+        rows64 = FusedA3CTrainer.buffer_rows(B)
+        t_t, t_d, t_g, t_a = [], [], [], []
+        for _ in range(rounds):
+            t_t.append(median_us(lambda: tt.train(x, y, a), reps))
+            t_d.append(median_us(lambda: td.train(x, y, a), reps))
+            bufs, cbuf = td._scratch(rows64)                     # (filled by the step just timed)
+            t_g.append(median_us(lambda: td._weight_grads(bufs, cbuf, rows64), reps))
+            t_a.append(median_us(td._apply, reps))
+        cell = lambda t: "%s | %.0f +- %.0f" % (" ".join("%.0f" % v for v in t), statistics.median(t), max(t) - min(t))
+        print("%-3d %-7d %-30s %-30s %-21s %-21s %.2fx" % (M, B, cell(t_t), cell(t_d), cell(t_g), cell(t_a),
+                                                             statistics.median(t_t) / statistics.median(t_d)), flush=True)
+        del tt, td, net_t, net_d
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rows", type=int, nargs="?", default=16384)
@@ -44,7 +78,10 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--arch", default="rnn", choices=["rnn", "weight_sharing"])
+    ap.add_argument("--device-step", action="store_true")
     args = ap.parse_args()
+    if args.device_step:
+        return device_step_legs(args.reps, args.rounds)
     B = args.rows
     print("M   rows    scratch (GB)  fused step (us)                autograd step (us)             autograd / fused")
     for M in args.max_other:
