@@ -58,11 +58,7 @@ __global__ void __launch_bounds__(256, 2) crowd_actor_kernel(const KCfg c, const
     const int rows = (int)worlds_here * n;                   // policy rows = agent slots of this tile
     const int32_t step0 = *io.rollout_step, pstep0 = *p.step_counter;
 
-    if (tid0 == 0) {                                         // arrival parity on the CU -> static priority (see cavoid_policy.hpp)
-        const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        const uint32_t key = ((xcc & 15u) << 8) | ((hw >> 8) & 0xFFu);
-        ticket = (int)atomicAdd(p.cu_tickets + key, 1u);
-    }
+    if (tid0 == 0) ticket = policy_cu_ticket(p.cu_tickets);   // arrival parity on the CU -> static priority (policy_cu_ticket, cavoid_policy.hpp)
     __syncthreads();
     if (ticket & 1) __builtin_amdgcn_s_setprio(1);
 

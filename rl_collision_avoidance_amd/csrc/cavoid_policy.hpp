@@ -359,6 +359,16 @@ __device__ __forceinline__ void policy_finish(const PolicyArgs &p, int step, int
     }
 }
 
+// Arrival parity on the CU.  Two workgroups share a CU (one wavefront of each per SIMD); the parity of this ticket decides a static
+// priority (`if (ticket & 1) s_setprio(1)` behind the barrier that publishes it), so that the pair does not settle into lockstep (same
+// phase at the same time, the matrix pipe idle while both do their pointwise / barrier phases): without it CU pairs finish anywhere
+// between 85 and 131 us, with it every pair takes the same time.  Called by one thread of the workgroup; cu_tickets: [kPolCuSlots].
+__device__ __forceinline__ int policy_cu_ticket(uint32_t *cu_tickets) {
+    const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_ID, XCC_ID
+    const uint32_t key = ((xcc & 15u) << 8) | ((hw >> 8) & 0xFFu);        // cu_id[11:8] sh_id[12] se_id[15:13]
+    return (int)atomicAdd(cu_tickets + key, 1u);
+}
+
 // The trainer pass's loss head (compile-time): the A3C loss, or the supervised start's cost_regression.
 constexpr int kLossA3C = 0, kLossRegression = 1;
 
@@ -514,11 +524,21 @@ __device__ __forceinline__ void policy_heads(const PolicyArgs &p, const float *a
 
 // The forward pass of one 16*RT-row tile: policy_forward_kernel<RT, TRAIN> (LOSS = kLossA3C) and policy_regression_forward_kernel<RT>
 // (TRAIN with LOSS = kLossRegression) are thin kernels over it.
-template <int RT, bool TRAIN, int LOSS>
+//
+// Ring: whether the input slots at LDS columns kPolXCol + 8 + 8s hold the whole row (PolNoRing: M <= kPolMaxOthers) or are a ring of
+// R slots refilled from global memory while the LSTM runs (PolRing<R>: the trainer pass on wider rows; the protocol is described in
+// cavoid_policy_train_ring.hpp).  What SpNoRing / SpRing<R> are to policy_split_tile (cavoid_policy_split.hpp).
+struct PolNoRing { static constexpr bool on = false; };
+template <int R_>
+struct PolRing { static constexpr bool on = true; static constexpr int R = R_; };
+
+template <int RT, bool TRAIN, int LOSS, class Ring = PolNoRing>
 __device__ __forceinline__ void policy_forward_tile(const PolicyArgs &p) {
+    static_assert(!Ring::on || (RT == 4 && TRAIN), "the float32 LSTM ring is the trainer's: ring inference is the split kernel's SpRing");
     constexpr int kRows = 16 * RT;
     // LDS: activations [kRows][kPolStride], then the packed biases, then one int.  While the LSTM runs, a row is
-    //   cols 0..63 h | 80 raw num_other | 84..87 host | 88+8t..94+8t x_t (t-th observed agent), zeros between
+    //   cols 0..63 h | 80 raw num_other | 84..87 host | 88+8t..94+8t x_t (t-th observed agent; with a ring: 88+8s.. the agent in
+    //   slot s), zeros between
     extern __shared__ __attribute__((aligned(16))) float act[];
     float *lds_bias = act + kRows * kPolStride;
     int *wave_max = reinterpret_cast<int *>(lds_bias + kBiasFloats);
@@ -553,9 +573,11 @@ __device__ __forceinline__ void policy_forward_tile(const PolicyArgs &p) {
         __syncthreads();
     }
     const bool listed = !TRAIN && p.row_index != nullptr;
+    const float *src = listed ? p.x : p.x + row0 * p.stride;       // (never read for tile rows >= rows_here)
+    int staged = M;                                        // observed agents the staging parks (a ring: the first R)
+    if constexpr (Ring::on) staged = M < Ring::R ? M : Ring::R;
     {
-        const float *src = listed ? p.x : p.x + row0 * p.stride;
-        const int wpad = 16 + 8 * M + 8;                   // padded row: [num,0,0,0, host(4), M x (x_t(7),0), 16 zeros]
+        const int wpad = 16 + 8 * staged + 8;              // padded row: [num,0,0,0, host(4), staged x (x_t(7),0), 16 zeros]
         const float inv_wpad = 1.0f / (float)wpad;
         const int total = kRows * wpad;
         constexpr int U = 3 * RT;                          // M = 3: the whole tile in one pass
@@ -563,15 +585,7 @@ __device__ __forceinline__ void policy_forward_tile(const PolicyArgs &p) {
         float bias_v[(kBiasFloats + 255) / 256];
 #pragma unroll
         for (int u = 0; u < (kBiasFloats + 255) / 256; ++u) bias_v[u] = tid + 256 * u < kBiasFloats ? p.bias[tid + 256 * u] : 0.0f;
-        if (tid == 0) {
-            // Two workgroups share a CU (one wavefront of each per SIMD).  Arrival parity on the CU decides a static
-            // priority, so that the pair does not settle into lockstep (same phase at the same time, the matrix
-            // pipe idle while both do their pointwise / barrier phases): without it CU pairs finish anywhere between
-            // 85 and 131 us, with it every pair takes the same time.
-            const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-            const uint32_t key = ((xcc & 15u) << 8) | ((hw >> 8) & 0xFFu);        // cu_id[11:8] sh_id[12] se_id[15:13]
-            ticket = (int)atomicAdd(p.cu_tickets + key, 1u);
-        }
+        if (tid == 0) ticket = policy_cu_ticket(p.cu_tickets);
         for (int e0 = 0; e0 < total; e0 += 256 * U) {
             float v[U], av[U], sd[U];
             int dst[U];
@@ -582,7 +596,7 @@ __device__ __forceinline__ void policy_forward_tile(const PolicyArgs &p) {
                 int sc = -1;                               // source column of this slot (-1: padding)
                 if (c == 0) sc = 0;
                 else if (c >= 4 && c < 8) sc = c - 3;
-                else if (c >= 8 && c < 8 + 8 * M && (c & 7) != 7) sc = 1 + kPolHost + kPolOther * ((c - 8) >> 3) + (c & 7);
+                else if (c >= 8 && c < 8 + 8 * staged && (c & 7) != 7) sc = 1 + kPolHost + kPolOther * ((c - 8) >> 3) + (c & 7);
                 const bool in = e < total && sc >= 0 && r < rows_here;
                 dst[u] = e < total ? r * kPolStride + kPolXCol + c : -1;
                 v[u] = in ? src[(int64_t)(listed ? tile_row[r] : r) * p.stride + sc] : 0.0f;
@@ -627,27 +641,67 @@ __device__ __forceinline__ void policy_forward_tile(const PolicyArgs &p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) len_r[rt][r] = act[(16 * rt + 4 * (lane >> 4) + r) * kPolStride + kPolXCol];
 
+    // the ring's refill: element e = tid + 256 u of the 64 x 7 values of one agent -- tile row e / 7, input e % 7
+    [[maybe_unused]] int ring_dst[2], ring_row[2], ring_k[2];
+    if constexpr (Ring::on) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int e = tid + 256 * u;
+            ring_row[u] = e / kPolOther; ring_k[u] = e - ring_row[u] * kPolOther;
+            const bool mine = e < kRows * kPolOther && ring_row[u] < rows_here;
+            if (!mine) ring_row[u] = -1;
+            ring_dst[u] = e < kRows * kPolOther ? (e / kPolOther) * kPolStride + kPolXCol + 8 + ring_k[u] : -1;
+        }
+    }
+
     // ---- LSTM over the observed agents -------------------------------------------------------------------
     f32x4 cell[RT], hid[RT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) { cell[rt] = f32x4{0.f, 0.f, 0.f, 0.f}; hid[rt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    [[maybe_unused]] int slot = 0;                         // t % R
     for (int t = 0; t < steps; ++t) {
+        // agent t + R into registers (uniform: only when a row of the tile runs step t + R; t + R < steps <= M)
+        [[maybe_unused]] bool refill = false;
+        [[maybe_unused]] float rv[2], rav[2], rsd[2];
+        if constexpr (Ring::on) {
+            refill = t + Ring::R < steps;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int sc = 1 + kPolHost + kPolOther * (t + Ring::R) + ring_k[u];
+                const bool in = refill && ring_row[u] >= 0;
+                rv[u] = in ? src[(int64_t)ring_row[u] * p.stride + sc] : 0.0f;
+                const bool norm = in && p.avg != nullptr;
+                rav[u] = norm ? p.avg[sc] : 0.0f;
+                rsd[u] = norm ? p.std[sc] : 1.0f;
+            }
+        }
+        // The LDS column of agent t: slot t, or ring slot t % R.  The ring forms it once, here; without a ring it is the sum at each
+        // use.  Each is the form that instantiation had -- the compiler's output follows it, and every kernel keeps its instruction stream.
+        [[maybe_unused]] const int ring_col = kPolXCol + 8 + 8 * slot;
         if (TRAIN) {                                       // the step's input rows, for the LSTM weight gradient
             float *dst = p.h_in + ((int64_t)t * p.rows64 + row0) * 72;
             for (int e = tid; e < kRows * 72; e += 256) {
                 const int r = e / 72, k = e - r * 72;
                 dst[e] = k < kPolHidden ? act[r * kPolStride + k]
-                                        : (k < kPolHidden + kPolOther ? act[r * kPolStride + kPolXCol + 8 + 8 * t + (k - kPolHidden)] : 0.0f);
+                                        : (k < kPolHidden + kPolOther ? act[Ring::on ? r * kPolStride + ring_col + (k - kPolHidden)
+                                                                                     : r * kPolStride + kPolXCol + 8 + 8 * t + (k - kPolHidden)] : 0.0f);
             }
         }
         f32x4 acc[RT][4];
         policy_init_acc(lds_bias + kBiasLstm, 4 * wave, lane, acc);
         if (t == 1) POLICY_STAMP(8);
-        policy_gemm(act, w_lstm, t == 0 ? 4 : 0, kChLstm, kPolXCol + 8 + 8 * t, 4 * wave, lane, f0, acc);
+        policy_gemm(act, w_lstm, t == 0 ? 4 : 0, kChLstm, Ring::on ? ring_col : kPolXCol + 8 + 8 * t, 4 * wave, lane, f0, acc);
         if (t == 1) POLICY_STAMP(9);
         policy_load_b(f0, w_lstm, 4 * wave, lane, 0);      // the next step's first weight fragments
-        __syncthreads();                                   // every wavefront has read h
+        __syncthreads();                                   // every wavefront has read h and the input slots
         if (t == 1) POLICY_STAMP(10);
+        if constexpr (Ring::on) {
+            if (refill) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    if (ring_dst[u] >= 0) act[ring_dst[u] + 8 * slot] = (rv[u] - rav[u]) / rsd[u];
+            }
+        }
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -671,8 +725,9 @@ __device__ __forceinline__ void policy_forward_tile(const PolicyArgs &p) {
                 act[(16 * rt + 4 * (lane >> 4) + r) * kPolStride + 16 * wave + (lane & 15)] = hid[rt][r];
             }
         if (t == 1) POLICY_STAMP(11);
-        __syncthreads();                                   // the new h is in place
+        __syncthreads();                                   // the new h (and the refilled slot) is in place
         if (t == 1) POLICY_STAMP(12);
+        if constexpr (Ring::on) slot = slot + 1 == Ring::R ? 0 : slot + 1;
     }
     POLICY_STAMP(1);
     // ---- layer1 on [h | host] --------------------------------------------------------------------------------

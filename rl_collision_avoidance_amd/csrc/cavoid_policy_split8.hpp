@@ -461,11 +461,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
                                                   ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
 #endif
     if (tid < 64) tile_row[tid] = listed ? (tid < rows_here ? p.row_index[row0 + tid] : 0) : tid;
-    if (tid == 0) {
-        const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        const uint32_t key = ((xcc & 15u) << 8) | ((hw >> 8) & 0xFFu);
-        ticket = (int)atomicAdd(p.cu_tickets + key, 1u);
-    }
+    if (tid == 0) ticket = policy_cu_ticket(p.cu_tickets);
     __syncthreads();
     if (ticket & 1) __builtin_amdgcn_s_setprio(1);
     const float *src = listed ? p.x : p.x + row0 * p.stride;

@@ -126,15 +126,17 @@ struct PolicyWsArgs {
     float *f_in;                       // [M, rows64, 8] filter inputs [xn_i | is_on_i] (TRAIN only)
 };
 
-#ifndef CAVOID_POLICY_WS_LAYOUT_ONLY  /* cavoid_policy_wsring.hip takes the layout and the argument struct above, and none of the kernels below */
 // The forward pass of one 64-row tile: policy_ws_forward_kernel<TRAIN> (LOSS = kLossA3C) and policy_regression_ws_forward_kernel
-// (TRAIN with LOSS = kLossRegression) are thin kernels over it.
-template <bool TRAIN, int LOSS>
+// (TRAIN with LOSS = kLossRegression) are thin kernels over it.  Ring (PolNoRing / PolRing<R>, cavoid_policy.hpp): whether the input
+// slots hold the whole row (M <= kWsMaxOthers) or are a ring of R slots refilled while the slot loop runs (the kernels and the
+// protocol of cavoid_policy_wsring.hpp).
+template <bool TRAIN, int LOSS, class Ring = PolNoRing>
 __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
     constexpr int RT = 4, kRows = 64;
     const PolicyArgs &p = wa.a;
     // LDS: rows [kRows][kPolStride], the packed biases, 8 ints, the tile's row list.  While the slots run, a row is
     //   cols 0..63 f_i (filter outputs of the current slot) | 80 raw num_other | 84..87 host | 88+8i..94+8i xn_i, 95+8i is_on_i
+    //   (with a ring: 88+8s.. the slot parked in ring slot s)
     extern __shared__ __attribute__((aligned(16))) float act[];
     float *lds_bias = act + kRows * kPolStride;
     int *ticket_slot = reinterpret_cast<int *>(lds_bias + kBiasFloats);
@@ -159,20 +161,18 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
         __syncthreads();
     }
     const bool listed = !TRAIN && p.row_index != nullptr;
+    const float *src = listed ? p.x : p.x + row0 * p.stride;
+    int staged = M;                                        // slots the staging parks (a ring: the first R)
+    if constexpr (Ring::on) staged = M < Ring::R ? M : Ring::R;
     {
-        const float *src = listed ? p.x : p.x + row0 * p.stride;
-        const int wpad = 16 + 8 * M + 8;                   // [num,0,0,0, host(4), M x (xn_i(7), is_on_i), 16 zeros]
+        const int wpad = 16 + 8 * staged + 8;              // [num,0,0,0, host(4), staged x (xn_i(7), is_on_i), 16 zeros]
         const float inv_wpad = 1.0f / (float)wpad;
         const int total = kRows * wpad;
         constexpr int U = 3 * RT;
         float bias_v[(kBiasFloats + 255) / 256];
 #pragma unroll
         for (int u = 0; u < (kBiasFloats + 255) / 256; ++u) bias_v[u] = tid + 256 * u < kBiasFloats ? p.bias[tid + 256 * u] : 0.0f;
-        if (tid == 0) {                                    // the CU arrival parity of policy_forward_kernel (static priority)
-            const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-            const uint32_t key = ((xcc & 15u) << 8) | ((hw >> 8) & 0xFFu);
-            ticket = (int)atomicAdd(p.cu_tickets + key, 1u);
-        }
+        if (tid == 0) ticket = policy_cu_ticket(p.cu_tickets);
         for (int e0 = 0; e0 < total; e0 += 256 * U) {
             float v[U], av[U], sd[U], thr[U];
             int dst[U];
@@ -184,7 +184,7 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
                 float th = 0.0f;                           // > 0: is_on of slot th - 1 (source: the raw count)
                 if (c == 0) sc = 0;
                 else if (c >= 4 && c < 8) sc = c - 3;
-                else if (c >= 8 && c < 8 + 8 * M) {
+                else if (c >= 8 && c < 8 + 8 * staged) {
                     if ((c & 7) != 7) sc = 1 + kPolHost + kPolOther * ((c - 8) >> 3) + (c & 7);
                     else { sc = 0; th = (float)(((c - 8) >> 3) + 1); }
                 }
@@ -215,9 +215,27 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
             const int r = e >> 2, k = e & 3;
             p.l1_in[(row0 + r) * w1 + k] = act[r * kPolStride + kPolXCol + 4 + k];
         }
-        for (int e = tid; e < M * kRows * kWsFilterIn; e += 256) {
-            const int i = e / (kRows * kWsFilterIn), r = (e >> 3) & (kRows - 1), k = e & 7;
-            wa.f_in[((int64_t)i * p.rows64 + row0 + r) * kWsFilterIn + k] = act[r * kPolStride + kPolXCol + 8 + 8 * i + k];
+        if constexpr (!Ring::on) {                         // (a ring: per iteration, from the ring slot)
+            for (int e = tid; e < M * kRows * kWsFilterIn; e += 256) {
+                const int i = e / (kRows * kWsFilterIn), r = (e >> 3) & (kRows - 1), k = e & 7;
+                wa.f_in[((int64_t)i * p.rows64 + row0 + r) * kWsFilterIn + k] = act[r * kPolStride + kPolXCol + 8 + 8 * i + k];
+            }
+        }
+    }
+
+    // the ring's element e = tid + 256 u of one slot's 64 x 8 values -- tile row e / 8, column e % 8 (7: is_on).  ring_src: the row's
+    // first float in global memory, -1 for a tile row at or past rows_here (zeros); ring_cnt: the row's raw count
+    [[maybe_unused]] int ring_lds[2], ring_k[2];
+    [[maybe_unused]] int64_t ring_src[2];
+    [[maybe_unused]] float ring_cnt[2];
+    if constexpr (Ring::on) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int e = tid + 256 * u, r = e >> 3;
+            ring_k[u] = e & 7;
+            ring_lds[u] = r * kPolStride + kPolXCol + 8 + ring_k[u];
+            ring_src[u] = r < rows_here ? (int64_t)(listed ? tile_row[r] : r) * p.stride : -1;
+            ring_cnt[u] = act[r * kPolStride + kPolXCol];
         }
     }
 
@@ -229,20 +247,54 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
     const float *arow = act + (lane & 15) * kPolStride + 4 * (lane >> 4);
     float *frow = act + (4 * (lane >> 4)) * kPolStride + 16 * wave + (lane & 15);
     PolicyFrag<RT, 4> f0;
+    [[maybe_unused]] int slot = 0;                         // i % R
     for (int i = 0; i < M; ++i) {
         const f32x4 *l1 = p.frags + L.l1 + (int64_t)4 * i * kFragPerChunk;
         policy_load_b(f0, l1, 4 * wave, lane, 0);          // in flight across the filter and the barriers
+        // slot i + R into registers (uniform): in flight across the filter MFMAs and the first barrier
+        [[maybe_unused]] bool refill = false;
+        [[maybe_unused]] float rv[2], rav[2], rsd[2];
+        if constexpr (Ring::on) {
+            refill = i + Ring::R < M;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int sc = 1 + kPolHost + kPolOther * (i + Ring::R) + ring_k[u];
+                const bool in = refill && ring_src[u] >= 0 && ring_k[u] < kPolOther;
+                rv[u] = in ? src[ring_src[u] + sc] : 0.0f;
+                const bool norm = in && p.avg != nullptr;
+                rav[u] = norm ? p.avg[sc] : 0.0f;
+                rsd[u] = norm ? p.std[sc] : 1.0f;
+            }
+        }
+        const int scol = kPolXCol + 8 + 8 * (Ring::on ? slot : i);     // the LDS slot that holds input slot i
+        if constexpr (Ring::on) {
+            if (TRAIN) {                                   // the slot's filter input rows, for the filter's weight gradient
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    wa.f_in[((int64_t)i * p.rows64 + row0 + ((tid + 256 * u) >> 3)) * kWsFilterIn + ring_k[u]] = act[ring_lds[u] + 8 * slot];
+            }
+        }
         f32x4 fa[RT], facc[RT];
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-            fa[rt] = *reinterpret_cast<const f32x4 *>(arow + 16 * rt * kPolStride + kPolXCol + 8 + 8 * i);
+            fa[rt] = *reinterpret_cast<const f32x4 *>(arow + 16 * rt * kPolStride + scol);
             facc[rt] = f32x4{fb, fb, fb, fb};
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) facc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[rt][s], fw[s], facc[rt], 0, 0, 0);
-        __syncthreads();                                   // every wavefront has read f_{i-1}
+        __syncthreads();                                   // every wavefront has read f_{i-1} (and ring slot i % R)
+        if constexpr (Ring::on) {
+            if (refill) {                                  // is_on from the raw count, as the staging takes it
+                const float thr = (float)(i + Ring::R + 1);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const float on = ring_src[u] >= 0 && ring_cnt[u] >= thr ? 1.0f : 0.0f;
+                    act[ring_lds[u] + 8 * slot] = ring_k[u] == kPolOther ? on : (rv[u] - rav[u]) / rsd[u];
+                }
+            }
+        }
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -251,9 +303,10 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
                 frow[(16 * rt + r) * kPolStride] = z;
                 if (TRAIN) p.l1_in[(row0 + 16 * rt + 4 * (lane >> 4) + r) * w1 + kPolHost + kPolHidden * i + 16 * wave + (lane & 15)] = z;
             }
-        __syncthreads();                                   // f_i is in place
+        __syncthreads();                                   // f_i (and the refilled slot) is in place
         // the last slot also takes the host chunk (chunk 4 reads the host columns, as layer1 of the LSTM kernel does)
         policy_gemm(act, l1, 0, i + 1 < M ? 4 : 5, kPolXCol + 4, 4 * wave, lane, f0, acc);
+        if constexpr (Ring::on) slot = slot + 1 == Ring::R ? 0 : slot + 1;
     }
     policy_load_b(f0, p.frags + L.l2, 4 * wave, lane, 0);
     __syncthreads();
@@ -289,6 +342,7 @@ __global__ void __launch_bounds__(256, TRAIN ? 1 : 2) policy_ws_forward_kernel(c
     policy_ws_forward_tile<TRAIN, kLossA3C>(wa);
 }
 
+#ifdef CAVOID_POLICY_WS_KERNELS  /* non-template kernels: compiled by cavoid_policy_ws.hip only */
 // The supervised start's trainer pass (cavoid_policy_train_regression_ws): the TRAIN forward with the regression head.  It leaves
 // what policy_ws_forward_kernel<true> leaves, so that policy_ws_backward_kernel runs behind it unchanged.
 __global__ void __launch_bounds__(256, 1) policy_regression_ws_forward_kernel(const PolicyWsArgs wa) {
@@ -352,7 +406,6 @@ __global__ void __launch_bounds__(256, 1) policy_ws_backward_kernel(const Policy
         if (lane < 16) atomicAdd(p.db + kBiasOther + col, bsum);
     }
 }
-
-#endif  /* CAVOID_POLICY_WS_LAYOUT_ONLY */
+#endif
 
 }  // namespace cavoid

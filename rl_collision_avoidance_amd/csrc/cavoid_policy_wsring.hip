@@ -6,7 +6,6 @@
 
 #include "cavoid.h"
 #include "cavoid_host.hpp"
-#define CAVOID_POLICY_WS_LAYOUT_ONLY 1
 #define CAVOID_POLICY_WSRING_KERNELS 1
 #include "cavoid_policy_wsring.hpp"
 #include "cavoid_policy_host.hpp"
