@@ -423,6 +423,22 @@ int cavoid_crowd_actor_run(cavoid_env *env, cavoid_policy *policy, cavoid_rollou
                            float *obs_cur, float *obs_next, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values,
                            int32_t n_steps, int32_t greedy, void *stream);
 
+/* cavoid_actor_run for the WEIGHT-SHARING network (cavoid_policy_create_ws; cavoid_actor_run, _run_mix and cavoid_crowd_actor_run refuse such a
+ * handle): the same closed loop, K steps in one launch -- per tile of floor(64/N) worlds a workgroup runs the weight-sharing pass
+ * (cavoid_policy_forward's arithmetic on a weight-sharing handle: float32 MFMA) on the tile's rows, draws the actions, steps the tile's worlds and
+ * records the step.  Arguments, buffers, counters, the ORCA / in-step box routing and the rule for the rows that need an action exactly as
+ * cavoid_actor_run; results are bit-identical to the step-by-step entry points (cavoid_rollout_active_rows, cavoid_policy_forward[_rows],
+ * cavoid_step_push).  `policy`: a loaded cavoid_policy_create_ws handle whose max_other (1..19) is the env's.
+ * CAVOID_EINVAL: null or mismatching handles and buffers (cavoid_actor_run's checks).  CAVOID_EUNSUPPORTED (use the step-by-step entry
+ * points): an LSTM handle (cavoid_actor_run carries it), a cavoid_policy_create_ws_crowd handle (the ring form, 20..64 observed agents), an env of
+ * more than 16 agents per world, holonomic dynamics, an env whose generator makes frozen-network agents (gen_frozen_fraction > 0 with
+ * gen_nonlearning_fraction > 0: one network per launch, no _mix form; the refusal looks at the generator's fractions only, as
+ * cavoid_actor_run's), and an env step whose LDS (with rvo_enabled: the ORCA lines) does not fit the 66 560 bytes of activation rows the pass
+ * lends it.  n_steps == 0: CAVOID_OK, nothing is launched. */
+int cavoid_actor_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_rollout *rollout, const cavoid_rollout_buffers *buffers,
+                        float *obs_cur, float *obs_next, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values,
+                        int32_t n_steps, int32_t greedy, void *stream);
+
 /* cavoid_step_autoreset + cavoid_rollout_push as ONE launch: the env step of every world and the Experience bookkeeping of its slots
  * (ProcessAgent.py:149-211) -- the fused actor's env phase for actors whose policy is a launch of its own (frozen-network agents,
  * a caller-supplied policy).  obs_cur [W,N,1+D]: the observation `actions` / `values` (V(s_t)) were computed on; the step writes the
@@ -565,7 +581,7 @@ int cavoid_policy_train(cavoid_policy *p, const float *x, int64_t rows, int64_t 
  *   cavoid_policy_forward / _forward_rows / _seed / _info / _destroy take either kind of handle (same arguments, same action draw;
  *       _info reports use_split = 0, split_products = 0).  cavoid_policy_load / _train on a weight-sharing handle, and _load_ws /
  *       _train_ws on an LSTM handle, are CAVOID_EINVAL; cavoid_actor_run / _run_mix with one (as policy or frozen) are
- *       CAVOID_EUNSUPPORTED.  CAVOID_POLICY_F32 / _PRODUCTS / _FORM do not apply.
+ *       CAVOID_EUNSUPPORTED (cavoid_actor_run_ws is this network's closed actor loop).  CAVOID_POLICY_F32 / _PRODUCTS / _FORM do not apply.
  *   cavoid_policy_train_ws : the trainer pass of cavoid_policy_train for this network (load with with_backward = 1).  The caller's GEMMs:
  *       d fullyconnected1 = z2^T g3,  d layer2 = z1^T g2,  d [logits_p | logits_v] = z3^T gh,
  *       d layer1 = l1_in^T g1 (rows in the checkpoint's order),  d other_kernel = f_in^T gf over all max_other * capacity_rows rows;

@@ -16,7 +16,8 @@ SOURCES = [os.path.join(CSRC, "cavoid_capi.hip"), os.path.join(CSRC, "cavoid_mul
            os.path.join(CSRC, "cavoid_actor_rvo.hip"), os.path.join(CSRC, "cavoid_actor_frozen.hip"), os.path.join(CSRC, "cavoid_crowd.hip"),
            os.path.join(CSRC, "cavoid_policy_ws.hip"), os.path.join(CSRC, "cavoid_policy_train_ring.hip"),
            os.path.join(CSRC, "cavoid_policy_wsring.hip"), os.path.join(CSRC, "cavoid_crowd_push.hip"), os.path.join(CSRC, "cavoid_crowd_rvo.hip"),
-           os.path.join(CSRC, "cavoid_crowd_actor.hip"), os.path.join(CSRC, "cavoid_policy_step.hip")]
+           os.path.join(CSRC, "cavoid_crowd_actor.hip"), os.path.join(CSRC, "cavoid_policy_step.hip"), os.path.join(CSRC, "cavoid_actor_ws.hip"),
+           os.path.join(CSRC, "cavoid_actor_ws_rvo.hip")]
 HEADERS = {
     "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp"],
     "cavoid_multistep.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
@@ -45,6 +46,11 @@ HEADERS = {
     "cavoid_policy_wsring.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp",
                                  "cavoid_host.hpp"],
     "cavoid_policy_ws.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
+    "cavoid_actor_ws.hip": ["cavoid_actor_ws.hpp", "cavoid_actor_ws_host.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp",
+                            "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp",
+                            "cavoid_rollout_host.hpp", "cavoid_host.hpp"],
+    "cavoid_actor_ws_rvo.hip": ["cavoid_actor_ws.hpp", "cavoid_actor_ws_host.hpp", "cavoid_actor.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp",
+                                "cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
     "cavoid_policy_step.hip": ["cavoid_policy_step.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
 }
 # per-file extra flags.  The multi-step env kernels run their step loop inside the launch; MachineLICM would hoist every
@@ -63,7 +69,9 @@ EXTRA_FLAGS = {"cavoid_multistep.hip": ["-mllvm", "-disable-machine-licm"], "cav
                # crowd_rvo_kernel / crowd_rvo_push_kernel (cavoid_crowd_rvo.hpp): the same step loop with the ORCA solve inside
                "cavoid_crowd_rvo.hip": ["-mllvm", "-disable-machine-licm"],
                # crowd_actor_kernel (cavoid_crowd_actor.hpp): policy + crowd env step + bookkeeping inside one step loop, as cavoid_actor.hip
-               "cavoid_crowd_actor.hip": ["-mllvm", "-disable-machine-licm"]}
+               "cavoid_crowd_actor.hip": ["-mllvm", "-disable-machine-licm"],
+               # actor_ws_kernel (cavoid_actor_ws.hpp): the weight-sharing pass + env step + bookkeeping inside one step loop, as cavoid_actor.hip
+               "cavoid_actor_ws.hip": ["-mllvm", "-disable-machine-licm"], "cavoid_actor_ws_rvo.hip": ["-mllvm", "-disable-machine-licm"]}
 STAMP_PATH = os.path.join(PKG_DIR, "libcavoid_hip.so.stamp")
 DEPS = SOURCES + [os.path.join(CSRC, h) for hs in HEADERS.values() for h in hs] + [os.path.join(ROOT, "include", "cavoid.h")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")

@@ -85,6 +85,13 @@ static int actor_run(cavoid_env *e, cavoid_policy *h, cavoid_policy *frozen, cav
     return CAVOID_OK;
 }
 
+// actor_finish_kernel for the actor launches of other translation units (cavoid_actor_ws.hip)
+int cavoid_launch_actor_finish(int32_t *rollout_step, int32_t *policy_step, int32_t n_steps, hipStream_t s) {
+    hipLaunchKernelGGL(actor_finish_kernel, dim3(1), dim3(1), 0, s, rollout_step, policy_step, n_steps);
+    HIP_TRY(hipGetLastError());
+    return CAVOID_OK;
+}
+
 extern "C" int cavoid_actor_run(cavoid_env *e, cavoid_policy *h, cavoid_rollout *r, const cavoid_rollout_buffers *b, float *obs_cur, float *obs_next,
                                 float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps,
                                 int32_t greedy, void *stream) {

@@ -74,3 +74,5 @@ int cavoid_launch_crowd_push(cavoid_env *e, const cavoid::RolloutCfg &rc, const 
 // rvo_enabled to the ORCA-carrying instantiation); CAVOID_EUNSUPPORTED as cavoid_launch_crowd_push
 int cavoid_launch_crowd_actor(cavoid_env *e, const cavoid::SplitArgs &sa, const cavoid::RolloutCfg &rc, const cavoid::RolloutState &rs,
                               const cavoid::RolloutIO &rio, const cavoid::ActorIO &io, hipStream_t s);
+// cavoid_actor.hip: actor_finish_kernel behind an actor launch (the two device-side counters move on by n_steps; policy_step may be null)
+int cavoid_launch_actor_finish(int32_t *rollout_step, int32_t *policy_step, int32_t n_steps, hipStream_t s);

@@ -406,8 +406,9 @@ __device__ __forceinline__ float policy_regression_head(const PolicyArgs &p, int
 // with its gradient, the action draw, the loss / db atomics.  The one epilogue of every float32-MFMA forward pass (LSTM and
 // weight-sharing).  Wavefront w < RT does rows 16w..16w+15 x 16 columns (A logits, the value, padding).  hb: the heads' weight
 // fragments -- all 16 loaded by the caller (PRELOADED: 2 wavefronts per SIMD, the registers are there), or hb[0 .. 8) by the caller
-// and the other half here (tighter register budget).
-template <int RT, bool TRAIN, int LOSS, bool PRELOADED>
+// and the other half here (tighter register budget).  P_OUT = false: no p.p_out (the fused weight-sharing actor loop, cavoid_actor_ws.hpp,
+// keeps the action and the value only).
+template <int RT, bool TRAIN, int LOSS, bool PRELOADED, bool P_OUT = true>
 __device__ __forceinline__ void policy_heads(const PolicyArgs &p, const float *act, const float *lds_bias, const f32x4 *head,
                                              f32x4 (&hb)[kChHead], const int *tile_row, bool listed, int64_t row0, int rows_here,
                                              int step, int wave, int lane) {
@@ -451,7 +452,7 @@ __device__ __forceinline__ void policy_heads(const PolicyArgs &p, const float *a
         const float sm = e / sum;                      // softmax
         const float pj = col < A ? (sm + p.min_policy) * scale : 0.0f;
         if (!TRAIN && row < p.rows) {
-            if (col < A) p.p_out[row * A + col] = pj;
+            if (col < A) { if (P_OUT) p.p_out[row * A + col] = pj; }
             else if (col == A) p.v_out[row] = z;
         }
         if (TRAIN && LOSS == kLossRegression) {

@@ -130,8 +130,16 @@ struct PolicyWsArgs {
 // (TRAIN with LOSS = kLossRegression) are thin kernels over it.  Ring (PolNoRing / PolRing<R>, cavoid_policy.hpp): whether the input
 // slots hold the whole row (M <= kWsMaxOthers) or are a ring of R slots refilled while the slot loop runs (the kernels and the
 // protocol of cavoid_policy_wsring.hpp).
-template <bool TRAIN, int LOSS, class Ring = PolNoRing>
-__device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
+//
+// FUSED = true: the pass as ONE PHASE of a kernel that goes on (actor_ws_kernel, cavoid_actor_ws.hpp) instead of a whole launch.  The
+// caller hands over what the launch forms derive from the grid and the device-side counters: the thread id (`tid_in`; its step loop
+// re-materialises it), the tile's rows as a list it has written to the LDS row list (ws_tile_row(): `rows_in` GLOBAL rows, the row-list
+// form's gather from p.x and its scatter of the outputs) and the step that keys the action draw (`step_in`).  The CU ticket is the
+// caller's (taken once per launch, at ws_ticket_slot()[4]), there is no policy_finish and no p.p_out.  Every statement that computes a
+// row's outputs is the launch forms': the results are theirs bit for bit.
+template <bool TRAIN, int LOSS, class Ring = PolNoRing, bool FUSED = false>
+__device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa, int tid_in = 0, int rows_in = 0, int step_in = 0) {
+    static_assert(!FUSED || (!TRAIN && !Ring::on), "the fused phase is the actors' whole-row pass");
     constexpr int RT = 4, kRows = 64;
     const PolicyArgs &p = wa.a;
     // LDS: rows [kRows][kPolStride], the packed biases, 8 ints, the tile's row list.  While the slots run, a row is
@@ -142,13 +150,19 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
     int *ticket_slot = reinterpret_cast<int *>(lds_bias + kBiasFloats);
     int &ticket = ticket_slot[4];
     int *tile_row = ticket_slot + 8;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t row0 = (int64_t)blockIdx.x * kRows;
-    const int64_t n_rows = (!TRAIN && p.row_count) ? (int64_t)*p.row_count : p.rows;
-    const int rows_here = n_rows - row0 < kRows ? (int)(n_rows - row0 > 0 ? n_rows - row0 : 0) : kRows;
+    const int tid = FUSED ? tid_in : (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t row0 = FUSED ? 0 : (int64_t)blockIdx.x * kRows;
+    int rows_here_v, step_v;
+    if constexpr (FUSED) {
+        rows_here_v = rows_in; step_v = step_in;
+    } else {
+        const int64_t n_rows = (!TRAIN && p.row_count) ? (int64_t)*p.row_count : p.rows;
+        rows_here_v = n_rows - row0 < kRows ? (int)(n_rows - row0 > 0 ? n_rows - row0 : 0) : kRows;
+        step_v = (!TRAIN && p.actions_out) ? *p.step_counter : 0;
+    }
+    const int rows_here = rows_here_v, step = step_v;
     const int M = p.max_other;
-    const int step = (!TRAIN && p.actions_out) ? *p.step_counter : 0;
-    if (!TRAIN && p.row_index && rows_here == 0) {
+    if (!FUSED && !TRAIN && p.row_index && rows_here == 0) {
         if (p.actions_out) policy_finish(p, step, tid);
         return;
     }
@@ -156,11 +170,11 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
     const int w1 = kPolHost + kPolHidden * M;              // layer1's input width (TRAIN: the row stride of l1_in)
 
     // ---- input tile: gather + normalise into the padded layout, is_on_i from the raw count ----------------------------
-    if (!TRAIN && p.row_index) {
+    if (!FUSED && !TRAIN && p.row_index) {
         if (tid < kRows) tile_row[tid] = tid < rows_here ? p.row_index[row0 + tid] : 0;
         __syncthreads();
     }
-    const bool listed = !TRAIN && p.row_index != nullptr;
+    const bool listed = FUSED || (!TRAIN && p.row_index != nullptr);      // (FUSED: the caller's list, behind a barrier of its own)
     const float *src = listed ? p.x : p.x + row0 * p.stride;
     int staged = M;                                        // slots the staging parks (a ring: the first R)
     if constexpr (Ring::on) staged = M < Ring::R ? M : Ring::R;
@@ -172,7 +186,7 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
         float bias_v[(kBiasFloats + 255) / 256];
 #pragma unroll
         for (int u = 0; u < (kBiasFloats + 255) / 256; ++u) bias_v[u] = tid + 256 * u < kBiasFloats ? p.bias[tid + 256 * u] : 0.0f;
-        if (tid == 0) ticket = policy_cu_ticket(p.cu_tickets);
+        if (!FUSED && tid == 0) ticket = policy_cu_ticket(p.cu_tickets);
         for (int e0 = 0; e0 < total; e0 += 256 * U) {
             float v[U], av[U], sd[U], thr[U];
             int dst[U];
@@ -209,7 +223,7 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
         }
     }
     __syncthreads();
-    if (ticket & 1) __builtin_amdgcn_s_setprio(1);
+    if (!FUSED && (ticket & 1)) __builtin_amdgcn_s_setprio(1);
     if (TRAIN) {                                           // the host columns of layer1's input rows, and every slot's filter input
         for (int e = tid; e < kRows * kPolHost; e += 256) {
             const int r = e >> 2, k = e & 3;
@@ -333,9 +347,14 @@ __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa) {
 #pragma unroll
         for (int ch = 0; ch < kChHead / 2; ++ch) hb[ch] = p.frags[L.head + lane + 64 * ch];
     }
-    policy_heads<RT, TRAIN, LOSS, false>(p, act, lds_bias, p.frags + L.head, hb, tile_row, listed, row0, rows_here, step, wave, lane);
-    if (!TRAIN && p.actions_out) policy_finish(p, step, tid);
+    policy_heads<RT, TRAIN, LOSS, false, !FUSED>(p, act, lds_bias, p.frags + L.head, hb, tile_row, listed, row0, rows_here, step, wave, lane);
+    if (!FUSED && !TRAIN && p.actions_out) policy_finish(p, step, tid);
 }
+
+// the tile's LDS words behind the activation rows and the packed biases (policy_lds_bytes(4)): 8 ints ([4]: the CU ticket) and the
+// 64-entry row list -- for a caller of the FUSED form, which owns the ticket and writes the list
+__device__ __forceinline__ int *ws_ticket_slot(float *act) { return reinterpret_cast<int *>(act + 64 * kPolStride + kBiasFloats); }
+__device__ __forceinline__ int *ws_tile_row(float *act) { return ws_ticket_slot(act) + 8; }
 
 template <bool TRAIN>
 __global__ void __launch_bounds__(256, TRAIN ? 1 : 2) policy_ws_forward_kernel(const PolicyWsArgs wa) {

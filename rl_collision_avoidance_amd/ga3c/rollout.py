@@ -21,6 +21,7 @@ import torch
 from .. import _lib
 from ..batched_env import BatchedCollisionAvoidanceEnv
 from .policy_kernel import MAX_OTHERS as POLICY_MAX_OTHERS
+from .policy_kernel import MAX_OTHERS_WS
 
 Policy = Callable[[torch.Tensor], Tuple[torch.Tensor, torch.Tensor]]   # x[B, D] -> (p[B, A], v[B])
 
@@ -59,6 +60,55 @@ def crowd_actor_unavailable_reason(agents_per_world: int, dynamics: int, arch: s
         return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy_max_others), int(env_max_other))
     if frozen_agents:
         return "frozen-network agents (the crowd actor kernel carries one network: no _mix form)"
+    return None
+
+
+# what the weight-sharing pass lends the env step inside actor_ws_kernel: its 64 activation rows of kPolStride floats
+# (actor_ws_lent_bytes(), csrc/cavoid_actor_ws.hpp)
+WS_ACTOR_LENT_BYTES = 64 * 260 * 4
+
+
+def env_step_lds_bytes(agents_per_world: int, obs_width: int, rvo_enabled: bool) -> int:
+    """An upper bound of the LDS one wavefront's env step of a tile env takes (``actor_env_lds_bytes``, csrc/cavoid_actor.hpp): the
+    action table, the staged records, the ORCA lines and the observation tile at the LARGEST tile ``cavoid_create`` chooses -- every
+    row of the wavefront in one pass, shrunk by whole rows of 4 (down to 4) until the carve fits the 64 KiB a workgroup may ask for."""
+    n, row = int(agents_per_world), int(obs_width) + 2
+    fixed = 128 + (128 if n >= 6 else 64) * 8 + (64 * 2 * (n - 1) * 4 * 2 if rvo_enabled else 0)
+    park = max((3 * (n - 1) * 64 if n >= 6 and not rvo_enabled else 0) + 256, 64 * 2 * 4 + 64)
+    rows = (64 // n) * n
+    need = lambda r: 4 * (fixed + max((r * row + 3) & ~3, park))
+    while rows > 4 and need(rows) > 65536:
+        rows = (rows - 1) & ~3
+    return need(rows)
+
+
+def ws_actor_unavailable_reason(agents_per_world: int, dynamics: int, arch: str, ws_ring: bool, policy_max_others: int, env_max_other: int,
+                                frozen_agents: bool, env_step_lds: int = 0, fused_policy: bool = True) -> Optional[str]:
+    """Why ``BatchedRollout.run_fused_ws`` (``cavoid_actor_run_ws``: the closed actor loop of the weight_sharing network, K steps in one
+    launch) does not apply -- None when it does.  A pure function of host values, the refusals of the C entry point one for one: a
+    ``FusedPolicy`` of the ``weight_sharing`` network on the whole-row kernels (up to ``MAX_OTHERS_WS`` observed neighbours, not the ring
+    handle of ``ws_crowd=True``) whose neighbour count is the env's, tile worlds (up to 16 agents), table actions, no frozen-network
+    agents (the launch carries one network), and an env step whose LDS (``env_step_lds`` bytes) fits the rows the pass lends it."""
+    n = int(agents_per_world)
+    if not 1 <= n <= _lib.MAX_AGENTS:
+        raise ValueError("agents per world must be 1..%d" % _lib.MAX_AGENTS)
+    if not fused_policy:
+        return "the policy is not a FusedPolicy"
+    if arch != "weight_sharing":
+        return "the policy is the %s network (the weight_sharing actor kernel embeds the weight_sharing pass; run_fused / cavoid_actor_run carries rnn)" % (arch,)
+    if ws_ring or int(policy_max_others) > MAX_OTHERS_WS:
+        return ("the policy observes %d neighbours on the ring kernels (the weight_sharing actor kernel parks the whole row: up to %d; "
+                "the ring form acts step by step)" % (int(policy_max_others), MAX_OTHERS_WS))
+    if int(policy_max_others) != int(env_max_other):
+        return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy_max_others), int(env_max_other))
+    if n > _lib.TILE_MAX_AGENTS:
+        return "%d agents per world: crowd worlds (more than %d) act step by step with the weight_sharing network" % (n, _lib.TILE_MAX_AGENTS)
+    if int(dynamics) == 2:
+        return "holonomic (velocity) actions"
+    if frozen_agents:
+        return "frozen-network agents (the weight_sharing actor kernel carries one network: no _mix form)"
+    if int(env_step_lds) > WS_ACTOR_LENT_BYTES:
+        return "the env step's LDS (%d bytes) does not fit the %d bytes the weight_sharing pass lends it" % (int(env_step_lds), WS_ACTOR_LENT_BYTES)
     return None
 
 
@@ -395,6 +445,58 @@ class BatchedRollout(object):
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             self.run_fused_crowd(steps_per_graph)
+        self.step_index -= steps_per_graph                # capture records, it does not execute
+        self._graph_steps = steps_per_graph
+
+    # -- the fused actor of the weight_sharing network: opt-in, beside the step-by-step path ---------------------------------------
+    @property
+    def ws_fused_unavailable_reason(self) -> Optional[str]:
+        """Why ``run_fused_ws`` does not apply to this rollout (None: it does) -- ``ws_actor_unavailable_reason`` on its values."""
+        cfg, pol = self.env.cfg, self.policy
+        return ws_actor_unavailable_reason(
+            self.env.max_agents, cfg.dynamics, getattr(pol, "arch", "rnn"), bool(getattr(pol, "ws", False) and getattr(pol, "crowd", False)),
+            getattr(pol, "max_others", -1), cfg.max_other,
+            self.frozen_policy is not None or (cfg.gen_frozen_fraction > 0.0 and cfg.gen_nonlearning_fraction > 0.0),
+            env_step_lds=(env_step_lds_bytes(self.env.max_agents, self.env.obs_width, bool(cfg.rvo_enabled))
+                          if self.env.max_agents <= _lib.TILE_MAX_AGENTS else 0),
+            fused_policy=bool(getattr(pol, "accepts_strided_obs", False)))
+
+    @property
+    def ws_fused_available(self) -> bool:
+        """``run_fused_ws`` applies (``fused_available`` stays False for the weight_sharing network: the default paths do not change)."""
+        return self.ws_fused_unavailable_reason is None
+
+    def run_fused_ws(self, n_steps: int) -> None:
+        """``run_fused`` for the weight_sharing network: ``n_steps`` closed-loop steps of every world in ONE launch
+        (``cavoid_actor_run_ws``) -- per tile of floor(64/N) worlds a workgroup runs the weight_sharing pass (float32 MFMA) on its own
+        rows, steps its worlds and records the step.  Bit-identical to ``n_steps`` calls of ``step()``; capturable into a hipGraph."""
+        why = self.ws_fused_unavailable_reason
+        if why is not None:
+            raise RuntimeError("run_fused_ws does not apply: " + why)
+        env, pol = self.env, self.policy
+        b = self._actor_buffers()
+        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
+        p = BatchedCollisionAvoidanceEnv._ptr
+        _lib.check(self._lib.cavoid_actor_run_ws(env._h, pol._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done),
+                                                 p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps), 1 if self.greedy else 0,
+                                                 env._stream()), "cavoid_actor_run_ws")
+        self._cur = (self._cur + int(n_steps)) & 1
+        self.step_index += int(n_steps)
+
+    def capture_fused_ws(self, steps_per_graph: int = 4) -> None:
+        """``run_fused_ws(steps_per_graph)`` as a one-node hipGraph, as ``capture_fused``: an even step count (the two observation
+        buffers alternate), two warm-up steps outside the capture; ``replay`` serves it."""
+        if steps_per_graph < 2 or steps_per_graph % 2:
+            raise ValueError("steps_per_graph must be a positive even number")
+        side = torch.cuda.Stream(device=self.env.device)
+        side.wait_stream(torch.cuda.current_stream(self.env.device))
+        with torch.cuda.stream(side):
+            self.run_fused_ws(2)
+        torch.cuda.current_stream(self.env.device).wait_stream(side)
+        torch.cuda.synchronize(self.env.device)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self.run_fused_ws(steps_per_graph)
         self.step_index -= steps_per_graph                # capture records, it does not execute
         self._graph_steps = steps_per_graph
 

@@ -155,6 +155,13 @@ def main(argv=None) -> None:
                          "per phase in a hipGraph; the run ends if the configuration is one the kernel does not carry (frozen-network agents, "
                          "the weight_sharing network, the PyTorch policy).  Opt-in until a whole training run has been timed with and without it "
                          "(profiles/crowd_actor_timing.txt holds the actor loop alone: tools/crowdactorbench.py)")
+    ap.add_argument("--fused-ws-actor", action="store_true",
+                    help="run the actors of the weight_sharing network (--arch weight_sharing, up to 16 agents per world and 19 observed "
+                         "neighbours) as ONE launch per --steps-per-graph env steps (cavoid_actor_run_ws: the weight_sharing pass, action draw, "
+                         "env.step and Experience bookkeeping per tile of worlds inside one kernel) instead of one launch per phase in a "
+                         "hipGraph; the run ends if the configuration is one the kernel does not carry (the rnn network, the ring form above 19 "
+                         "neighbours, crowd worlds, frozen-network agents, the PyTorch policy).  Opt-in until a whole training run has been "
+                         "timed with and without it (profiles/ws_actor_timing.txt holds the actor loop alone: tools/wsactorbench.py)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--print-every", type=int, default=2000, help="stats line every n episodes (rank 0)")
     ap.add_argument("--faithful-reflush", action="store_true", help="keep the reference's post-done re-flush quirk")
@@ -330,6 +337,12 @@ def main(argv=None) -> None:
             raise SystemExit("--fused-crowd-actor: the crowd actor kernel (cavoid_crowd_actor_run) does not apply: " + why)
         roll.capture_fused_crowd(steps_per_graph=args.steps_per_graph)
         actors = "fused crowd actor kernel (cavoid_crowd_actor_run), %d env steps per launch" % args.steps_per_graph
+    elif args.fused_ws_actor:
+        why = roll.ws_fused_unavailable_reason
+        if why is not None:
+            raise SystemExit("--fused-ws-actor: the weight_sharing actor kernel (cavoid_actor_run_ws) does not apply: " + why)
+        roll.capture_fused_ws(steps_per_graph=args.steps_per_graph)
+        actors = "fused weight_sharing actor kernel (cavoid_actor_run_ws), %d env steps per launch" % args.steps_per_graph
     elif roll.fused_available and not args.no_actor_kernel:
         roll.capture_fused(steps_per_graph=args.steps_per_graph)       # K closed-loop steps per launch (cavoid_actor_run)
         actors = "%s, %d env steps per launch" % (roll.actor_path, args.steps_per_graph)

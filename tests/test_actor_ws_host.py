@@ -1,0 +1,119 @@
+"""Host-side tests (no GPU) of the weight_sharing network's fused actor loop (`cavoid_actor_run_ws`, csrc/cavoid_actor_ws.hpp):
+`ws_actor_unavailable_reason` -- the pure function behind `BatchedRollout.ws_fused_unavailable_reason` and `ga3c.train
+--fused-ws-actor` -- against the refusals the C entry point documents, the entry point's declaration and export, and the constants
+the Python side mirrors."""
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "rl_collision_avoidance_amd", "csrc")
+
+
+def _reason(**over):
+    from rl_collision_avoidance_amd.ga3c.rollout import ws_actor_unavailable_reason
+    # the WS-8 shape: 4 agents per world, 7 observed neighbours, the weight_sharing network on the whole-row kernels
+    kw = dict(agents_per_world=4, dynamics=0, arch="weight_sharing", ws_ring=False, policy_max_others=7, env_max_other=7, frozen_agents=False,
+              env_step_lds=20000, fused_policy=True)
+    kw.update(over)
+    return ws_actor_unavailable_reason(**kw)
+
+
+def test_the_ws8_shape_runs():
+    assert _reason() is None
+    for n in range(1, 17):
+        assert _reason(agents_per_world=n) is None, n
+    for m in range(1, 20):
+        assert _reason(policy_max_others=m, env_max_other=m) is None, m
+
+
+@pytest.mark.parametrize("over,word", [
+    (dict(arch="rnn"), "rnn network"),
+    (dict(ws_ring=True, policy_max_others=24, env_max_other=24), "ring"),
+    (dict(agents_per_world=17), "crowd worlds"),
+    (dict(agents_per_world=20, policy_max_others=19, env_max_other=19), "20 agents per world"),
+    (dict(dynamics=2), "holonomic"),
+    (dict(frozen_agents=True), "frozen-network agents"),
+    (dict(env_step_lds=66564), "does not fit"),
+    (dict(policy_max_others=3), "the env's rows carry 7"),
+    (dict(fused_policy=False), "not a FusedPolicy"),
+])
+def test_each_refusal_names_its_cause(over, word):
+    why = _reason(**over)
+    assert why is not None and word in why, why
+
+
+def test_agent_count_out_of_range_is_an_error():
+    for n in (0, 65):
+        with pytest.raises(ValueError):
+            _reason(agents_per_world=n)
+
+
+def test_the_neighbour_limit_is_the_kernels():
+    """MAX_OTHERS_WS bounds the reason function as kWsMaxOthers bounds the C check (the entry point refuses h->max_other > kWsMaxOthers)."""
+    from rl_collision_avoidance_amd.ga3c.policy_kernel import MAX_OTHERS, MAX_OTHERS_WS
+    assert _reason(policy_max_others=MAX_OTHERS_WS, env_max_other=MAX_OTHERS_WS) is None
+    why = _reason(policy_max_others=MAX_OTHERS_WS + 1, env_max_other=MAX_OTHERS_WS + 1)
+    assert why is not None and "up to %d" % MAX_OTHERS_WS in why
+    ws = open(os.path.join(CSRC, "cavoid_policy_ws.hpp")).read()
+    pol = open(os.path.join(CSRC, "cavoid_policy.hpp")).read()
+    assert re.search(r"constexpr\s+int\s+kWsMaxOthers\s*=\s*kPolMaxOthers\s*;", ws)
+    assert int(re.search(r"constexpr\s+int\s+kPolMaxOthers\s*=\s*(\d+)\s*;", pol).group(1)) == MAX_OTHERS_WS == MAX_OTHERS
+    assert re.search(r"h->max_other\s*>\s*kWsMaxOthers", open(os.path.join(CSRC, "cavoid_actor_ws.hip")).read())
+
+
+def test_the_loan_is_the_kernels_activation_rows():
+    from rl_collision_avoidance_amd.ga3c import rollout
+    pol = open(os.path.join(CSRC, "cavoid_policy.hpp")).read()
+    stride = int(re.search(r"constexpr\s+int\s+kPolStride\s*=\s*(\d+)\s*;", pol).group(1))
+    assert rollout.WS_ACTOR_LENT_BYTES == 64 * stride * 4 == 66560
+    assert re.search(r"actor_ws_lent_bytes\(\)\s*\{\s*return\s*\(size_t\)64\s*\*\s*kPolStride\s*\*\s*sizeof\(float\)", open(os.path.join(CSRC, "cavoid_actor_ws.hpp")).read())
+    assert _reason(env_step_lds=rollout.WS_ACTOR_LENT_BYTES) is None
+    # an env cavoid_create accepts keeps one wavefront's carve inside 64 KiB: inside the loan, ORCA lines included
+    for n in range(1, 17):
+        for m in (1, 7, 19):
+            for rvo in (False, True):
+                need = rollout.env_step_lds_bytes(n, 2 + 4 + 7 * m, rvo)
+                assert need <= 65536 or (rvo and n == 16), (n, m, rvo, need)
+
+
+def test_the_entry_point_is_declared_exported_and_bound():
+    from rl_collision_avoidance_amd import _lib
+    header = open(os.path.join(ROOT, "include", "cavoid.h")).read()
+    assert re.search(r"\bint\s+cavoid_actor_run_ws\s*\(", header)
+    bound = {name: args for name, _, args in _lib.SYMBOLS}
+    assert "cavoid_actor_run_ws" in bound and len(bound["cavoid_actor_run_ws"]) == len(bound["cavoid_actor_run"]) == 14
+    assert hasattr(_lib.lib(), "cavoid_actor_run_ws")
+
+
+def test_the_rollout_has_the_ws_forms_and_keeps_the_default_ones():
+    from rl_collision_avoidance_amd.ga3c.rollout import BatchedRollout
+    for name in ("ws_fused_unavailable_reason", "ws_fused_available", "run_fused_ws", "capture_fused_ws", "fused_available", "actor_path"):
+        assert hasattr(BatchedRollout, name), name
+
+
+def test_train_cli_knows_the_flag():
+    from rl_collision_avoidance_amd.ga3c import train
+    with pytest.raises(SystemExit):                          # (an unknown flag is an error)
+        train.main(["--fused-ws-actor-typo"])
+    src = open(os.path.join(ROOT, "rl_collision_avoidance_amd", "ga3c", "train.py")).read()
+    assert '"--fused-ws-actor"' in src and "fused weight_sharing actor kernel (cavoid_actor_run_ws), %d env steps per launch" in src
+
+
+def test_actor_ws_kernels_fit_two_workgroups_per_cu():
+    """Every instantiation within 256 registers per lane (two workgroups per CU), 256 threads, and the ones the default shapes run -- N up to 15
+    without ORCA, the WS-8 shape among them -- free of scratch (profiles/ws_actor_resources.txt lists all of them)."""
+    from tests.test_crowd_host import LLVM, _kernel_notes
+    if not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))):
+        pytest.skip("llvm-objdump / llvm-readelf of the ROCm toolchain not present")
+    text = _kernel_notes()
+    found = re.findall(r"\.name:\s+\S*actor_ws_kernelILi(\d+)ELb(\d)E\S*\s*\n\s*\.private_segment_fixed_size:\s+(\d+)", text)
+    scratch = {(int(n), int(rvo)): int(size) for n, rvo, size in found}
+    assert sorted(scratch) == sorted((n, rvo) for n in range(1, 17) for rvo in (0, 1)), sorted(scratch)
+    assert all(scratch[(n, 0)] == 0 for n in range(1, 16)), scratch
+    assert all(scratch[(n, 1)] == 0 for n in range(1, 10)), scratch
+    sizes = re.findall(r"\.max_flat_workgroup_size:\s+(\d+)\s*\n\s*\.name:\s+\S*actor_ws_kernel", text)
+    assert sizes == ["256"] * 32, sizes
+    vgprs = re.findall(r"\.name:\s+\S*actor_ws_kernel\S*\s*\n(?:\s+\.(?!name)\S+:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text)
+    assert len(vgprs) == 32 and all(int(v) <= 256 for v in vgprs), vgprs
