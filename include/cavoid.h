@@ -582,7 +582,8 @@ int cavoid_policy_train(cavoid_policy *p, const float *x, int64_t rows, int64_t 
  *       _info reports use_split = 0, split_products = 0).  cavoid_policy_load / _train on a weight-sharing handle, and _load_ws /
  *       _train_ws on an LSTM handle, are CAVOID_EINVAL; cavoid_actor_run / _run_mix with one (as policy or frozen) are
  *       CAVOID_EUNSUPPORTED (cavoid_actor_run_ws is this network's closed actor loop).  CAVOID_POLICY_F32 / _PRODUCTS / _FORM do not apply.
- *   cavoid_policy_train_ws : the trainer pass of cavoid_policy_train for this network (load with with_backward = 1).  The caller's GEMMs:
+ *   cavoid_policy_train_ws : the trainer pass of cavoid_policy_train for this network (load with with_backward = 1).  The contractions it
+ *       leaves the operands of (cavoid_policy_weight_grads_ws forms them, or the caller's own GEMM library):
  *       d fullyconnected1 = z2^T g3,  d layer2 = z1^T g2,  d [logits_p | logits_v] = z3^T gh,
  *       d layer1 = l1_in^T g1 (rows in the checkpoint's order),  d other_kernel = f_in^T gf over all max_other * capacity_rows rows;
  *       bias gradients in db: other_bias at 0..63, then layer1 / layer2 / fullyconnected1 / heads at 256 / 512 / 768 / 1024. */
@@ -647,7 +648,7 @@ int cavoid_policy_train_regression_ws(cavoid_policy *p, const float *x, int64_t 
  *   aligned like every per-row buffer (CAVOID_EINVAL otherwise, as for a NULL pointer, a wrong struct_size or a capacity_rows that is
  *   not a positive multiple of 64).  ALL capacity_rows rows are read: call it after a pass that wrote them (a pass over rows = 0 rows
  *   launches nothing and writes none).  Both LSTM handle kinds (max_other 1..19 and crowd handles, 20..64); CAVOID_EUNSUPPORTED on a
- *   weight-sharing handle.
+ *   weight-sharing handle (cavoid_policy_weight_grads_ws below).
  *
  * cavoid_policy_apply: one optimiser step on the float32 MASTER weights and the re-pack.  `weights`: the struct of cavoid_policy_load whose
  *   twelve variable pointers are the masters (device memory the caller owns; updated IN PLACE although the struct says const), with
@@ -663,7 +664,7 @@ int cavoid_policy_train_regression_ws(cavoid_policy *p, const float *x, int64_t 
  *   state1 / state2: device float [total]; step: device int64, read as t - 1 and written back as t by one thread.  Launches: one for the
  *   update, one more in front of it for the twelve norms when clipping (a fixed-order reduction per variable); then exactly
  *   cavoid_policy_load on the updated masters on the same stream -- the handle afterwards is, bit for bit, what a fresh load gives.
- *   CAVOID_EINVAL: NULL pointers, wrong struct sizes, an unknown kind, a negative clip; CAVOID_EUNSUPPORTED: a weight-sharing handle. */
+ *   CAVOID_EINVAL: NULL pointers, wrong struct sizes, an unknown kind, a negative clip; CAVOID_EUNSUPPORTED: a weight-sharing handle (cavoid_policy_apply_ws below). */
 #define CAVOID_POLICY_PARAMS 12
 enum { CAVOID_OPT_ADAM = 0, CAVOID_OPT_RMSPROP = 1 };
 typedef struct cavoid_policy_optimizer {
@@ -682,6 +683,46 @@ int cavoid_policy_weight_grads(cavoid_policy *p, const cavoid_policy_train_buffe
                                float *grads_flat, void *stream);
 int cavoid_policy_apply(cavoid_policy *p, const cavoid_policy_weights *weights, const cavoid_policy_optimizer *opt, const float *grads_flat,
                         void *stream);
+
+/* ---- the rest of the trainer step for the WEIGHT-SHARING network: the same sequence on a cavoid_policy_create_ws / _create_ws_crowd handle
+ *     cavoid_policy_train_ws (or _train_regression_ws)  ->  cavoid_policy_weight_grads_ws  ->  [the caller's all-reduce of grads_flat]  ->  cavoid_policy_apply_ws
+ * with cavoid_policy_optimizer and cavoid_policy_train_ws_buffers as they are.  The three LSTM calls above stay CAVOID_EUNSUPPORTED on such
+ * a handle, and these are CAVOID_EUNSUPPORTED on an LSTM handle.
+ *
+ * cavoid_policy_param_layout_ws (host code only): the flat vector of this network -- CAVOID_POLICY_PARAMS = 12 variables in the order
+ *   other_kernel [8, 64], other_bias [64], layer1_kernel [4 + 64 max_other, 256], layer1_bias, layer2_kernel, layer2_bias, fc1_kernel,
+ *   fc1_bias, p_kernel [256, A], p_bias, v_kernel, v_bias -- each in the checkpoint's shape, each starting on a multiple of 64 floats, the
+ *   padding as above.  Unlike the LSTM layout it depends on max_other.  max_other 1..64, num_actions 1..15, no NULL, else CAVOID_EINVAL.
+ *
+ * cavoid_policy_weight_grads_ws: every weight and bias gradient of the pass that just filled `buffers`, into grads_flat [total]: the five
+ *   contractions of cavoid_policy_train_ws's comment on the float32 matrix instructions (exact float32 products, float32 accumulation).
+ *   Nothing is permuted -- l1_in's columns and f_in's [xn | is_on] are in the checkpoint's order: layer1 is max_other 64-row blocks plus a
+ *   4-row host edge, other_kernel an 8-row edge over the flat max_other * capacity_rows rows; absent columns of an edge tile are zeros that
+ *   are never loaded.  db is moved into the six biases.  Two launches, whatever max_other and the row count.  The row slices, by
+ *   capacity_rows (R) and max_other (M) only:
+ *     fullyconnected1, layer2, heads   1 024 rows;                                     D = ceil(R / 1 024) slices
+ *     layer1                           1 024 rows;                                     L = D
+ *     other_kernel                     1 024 flat rows, 4 096 once M R > 4 194 304;    F = ceil(M R / that)
+ *   (a layer1 partial is 4 MB at M = 63, so 16 384 rows there take 66 MB of partials, a tenth of the pass's own buffers: longer slices
+ *   measured slower by the time of one long tile).  One wavefront forms one
+ *   64 x 64 (or edge) tile of one slice's partial in `scratch`, the second launch sums every entry's partials in slice order: no
+ *   floating-point atomics, the same bits for the same buffers; the longest accumulation chain is the slice length plus the number of
+ *   slices.  Every float of grads_flat is written (zeros in the padding); ALL capacity_rows rows are read.
+ *   scratch: at least the floats cavoid_policy_weight_grads_scratch_ws reports,
+ *       L * (4 + 64 M) * 256  +  D * 135 168  +  F * 512,
+ *   16-byte aligned like every per-row buffer.  CAVOID_EINVAL: a NULL or misaligned pointer, a wrong struct_size, a capacity_rows that is
+ *   not a positive multiple of 64, too small a scratch.
+ *
+ * cavoid_policy_apply_ws: cavoid_policy_apply's launches (the same kernels, the same optimiser rules and clip) over this layout.  The
+ *   twelve masters are other_kernel, other_bias and the ten non-LSTM pointers of `weights` (its lstm fields are ignored, as in
+ *   cavoid_policy_load_ws); then exactly cavoid_policy_load_ws on the updated masters on the same stream -- the handle afterwards is, bit
+ *   for bit, what a fresh load gives.  Error codes as for cavoid_policy_apply; a refused call does not step. */
+int cavoid_policy_param_layout_ws(int32_t max_other, int32_t num_actions, int64_t *offsets, int64_t *sizes, int64_t *total);
+int cavoid_policy_weight_grads_scratch_ws(const cavoid_policy *p, int64_t capacity_rows, int64_t *floats);
+int cavoid_policy_weight_grads_ws(cavoid_policy *p, const cavoid_policy_train_ws_buffers *buffers, float *scratch, int64_t scratch_floats,
+                                  float *grads_flat, void *stream);
+int cavoid_policy_apply_ws(cavoid_policy *p, const cavoid_policy_weights *weights, const float *other_kernel, const float *other_bias,
+                           const cavoid_policy_optimizer *opt, const float *grads_flat, void *stream);
 
 /* kernel timing helper: HIP events recorded on `stream` around the launches of the calls made
  * between begin and end; end synchronises and returns elapsed milliseconds */

@@ -77,6 +77,8 @@ class CavoidPolicyTrainWsBuffers(C.Structure):
 POLICY_PARAMS = 12       # CAVOID_POLICY_PARAMS: the variables of the flat parameter vector, in this order (cavoid_policy_param_layout)
 POLICY_PARAM_NAMES = ("lstm_kernel", "lstm_bias", "layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel", "fc1_bias",
                       "p_kernel", "p_bias", "v_kernel", "v_bias")
+# ... and of the weight-sharing network's (cavoid_policy_param_layout_ws)
+POLICY_PARAM_NAMES_WS = ("other_kernel", "other_bias") + POLICY_PARAM_NAMES[2:]
 OPT_ADAM, OPT_RMSPROP = 0, 1
 
 
@@ -177,6 +179,10 @@ SYMBOLS = [
     ("cavoid_policy_weight_grads_scratch", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64)]),
     ("cavoid_policy_weight_grads", C.c_int, [_P, C.POINTER(CavoidPolicyTrainBuffers), _P, C.c_int64, _P, _P]),
     ("cavoid_policy_apply", C.c_int, [_P, C.POINTER(CavoidPolicyWeights), C.POINTER(CavoidPolicyOptimizer), _P, _P]),
+    ("cavoid_policy_param_layout_ws", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("cavoid_policy_weight_grads_scratch_ws", C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("cavoid_policy_weight_grads_ws", C.c_int, [_P, C.POINTER(CavoidPolicyTrainWsBuffers), _P, C.c_int64, _P, _P]),
+    ("cavoid_policy_apply_ws", C.c_int, [_P, C.POINTER(CavoidPolicyWeights), _P, _P, C.POINTER(CavoidPolicyOptimizer), _P, _P]),
     ("cavoid_timer_begin", C.c_int, [_P, _P]),
     ("cavoid_timer_end", C.c_int, [_P, _P, C.POINTER(C.c_float)]),
 ]
@@ -222,6 +228,13 @@ def policy_param_layout(max_other: int, num_actions: int):
     """``cavoid_policy_param_layout``: (offsets, sizes, total) of the flat parameter vector, in floats; entry i is POLICY_PARAM_NAMES[i]."""
     off, size, total = (C.c_int64 * POLICY_PARAMS)(), (C.c_int64 * POLICY_PARAMS)(), C.c_int64()
     check(lib().cavoid_policy_param_layout(max_other, num_actions, off, size, C.byref(total)), "cavoid_policy_param_layout")
+    return list(off), list(size), int(total.value)
+
+
+def policy_param_layout_ws(max_other: int, num_actions: int):
+    """``cavoid_policy_param_layout_ws``: the same for the weight-sharing network; entry i is POLICY_PARAM_NAMES_WS[i]."""
+    off, size, total = (C.c_int64 * POLICY_PARAMS)(), (C.c_int64 * POLICY_PARAMS)(), C.c_int64()
+    check(lib().cavoid_policy_param_layout_ws(max_other, num_actions, off, size, C.byref(total)), "cavoid_policy_param_layout_ws")
     return list(off), list(size), int(total.value)
 
 

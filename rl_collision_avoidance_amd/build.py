@@ -17,7 +17,7 @@ SOURCES = [os.path.join(CSRC, "cavoid_capi.hip"), os.path.join(CSRC, "cavoid_mul
            os.path.join(CSRC, "cavoid_policy_ws.hip"), os.path.join(CSRC, "cavoid_policy_train_ring.hip"),
            os.path.join(CSRC, "cavoid_policy_wsring.hip"), os.path.join(CSRC, "cavoid_crowd_push.hip"), os.path.join(CSRC, "cavoid_crowd_rvo.hip"),
            os.path.join(CSRC, "cavoid_crowd_actor.hip"), os.path.join(CSRC, "cavoid_policy_step.hip"), os.path.join(CSRC, "cavoid_actor_ws.hip"),
-           os.path.join(CSRC, "cavoid_actor_ws_rvo.hip")]
+           os.path.join(CSRC, "cavoid_actor_ws_rvo.hip"), os.path.join(CSRC, "cavoid_policy_step_ws.hip")]
 HEADERS = {
     "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp"],
     "cavoid_multistep.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
@@ -52,6 +52,8 @@ HEADERS = {
     "cavoid_actor_ws_rvo.hip": ["cavoid_actor_ws.hpp", "cavoid_actor_ws_host.hpp", "cavoid_actor.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp",
                                 "cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
     "cavoid_policy_step.hip": ["cavoid_policy_step.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
+    "cavoid_policy_step_ws.hip": ["cavoid_policy_step_ws.hpp", "cavoid_policy_step.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp",
+                                  "cavoid_host.hpp"],
 }
 # per-file extra flags.  The multi-step env kernels run their step loop inside the launch; MachineLICM would hoist every
 # constant materialisation of the body (float64 polynomial coefficients, config scalars) out of that loop into

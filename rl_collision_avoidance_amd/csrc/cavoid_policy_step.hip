@@ -22,8 +22,6 @@ extern "C" int cavoid_policy_param_layout(int32_t max_other, int32_t num_actions
     return CAVOID_OK;
 }
 
-static bool step_rows_ok(int64_t capacity_rows) { return capacity_rows > 0 && capacity_rows % 64 == 0 && capacity_rows / 64 <= 0x7fffffffLL; }
-
 static int64_t step_scratch_floats(int64_t capacity_rows, int32_t max_other) {
     const StepPartition p = step_partition(capacity_rows, max_other);
     return p.dense_slices * kStepDensePartial + p.lstm_slices * kStepLstmPartial;
@@ -37,12 +35,10 @@ extern "C" int cavoid_policy_weight_grads_scratch(const cavoid_policy *h, int64_
     return CAVOID_OK;
 }
 
-static bool step_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 extern "C" int cavoid_policy_weight_grads(cavoid_policy *h, const cavoid_policy_train_buffers *b, float *scratch, int64_t scratch_floats,
                                           float *grads_flat, void *stream) {
     if (!h) return CAVOID_EINVAL;
-    if (h->ws) return CAVOID_EUNSUPPORTED;                 // (the weight-sharing network's gradients are the caller's GEMMs)
+    if (h->ws) return CAVOID_EUNSUPPORTED;                 // (cavoid_policy_weight_grads_ws: other buffers, other jobs)
     if (!b || b->struct_size != (int32_t)sizeof(cavoid_policy_train_buffers) || !scratch || !grads_flat) return CAVOID_EINVAL;
     if (!step_rows_ok(b->capacity_rows)) return CAVOID_EINVAL;
     const float *const operands[] = {b->z1, b->z2, b->z3, b->l1_in, b->h_in, b->gh, b->g1, b->g2, b->g3, b->gl};
@@ -71,24 +67,8 @@ extern "C" int cavoid_policy_weight_grads(cavoid_policy *h, const cavoid_policy_
     return CAVOID_OK;
 }
 
-extern "C" int cavoid_policy_apply(cavoid_policy *h, const cavoid_policy_weights *w, const cavoid_policy_optimizer *opt, const float *grads_flat,
-                                   void *stream) {
-    if (!h) return CAVOID_EINVAL;
-    if (h->ws) return CAVOID_EUNSUPPORTED;
-    if (!w || w->struct_size != (int32_t)sizeof(cavoid_policy_weights) || !opt || opt->struct_size != (int32_t)sizeof(cavoid_policy_optimizer) ||
-        !grads_flat)
-        return CAVOID_EINVAL;
-    if ((opt->kind != CAVOID_OPT_ADAM && opt->kind != CAVOID_OPT_RMSPROP) || !opt->state1 || !opt->state2 || !opt->step ||
-        !(opt->clip_average_norm >= 0.0))
-        return CAVOID_EINVAL;
-    const float *const masters[kStepParams] = {w->lstm_kernel, w->lstm_bias, w->layer1_kernel, w->layer1_bias, w->layer2_kernel, w->layer2_bias,
-                                               w->fc1_kernel, w->fc1_bias, w->p_kernel, w->p_bias, w->v_kernel, w->v_bias};
-    for (const float *p : masters)
-        if (!p) return CAVOID_EINVAL;
-    if ((w->avg == nullptr) != (w->std == nullptr)) return CAVOID_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(h->device));
-    const StepLayout l = step_layout(h->num_actions);
+int cavoid_policy_step_update(cavoid_policy *h, float *const *masters, const StepLayout &l, const cavoid_policy_optimizer *opt, const float *grads_flat,
+                              hipStream_t s) {
     const bool clip = opt->clip_average_norm > 0.0;
     if (clip) {
         StepNormArgs n{};
@@ -98,10 +78,28 @@ extern "C" int cavoid_policy_apply(cavoid_policy *h, const cavoid_policy_weights
         HIP_TRY(hipGetLastError());
     }
     StepApplyArgs a{};
-    for (int i = 0; i < kStepParams; ++i) { a.w[i] = const_cast<float *>(masters[i]); a.off[i] = l.off[i]; a.size[i] = l.size[i]; }
+    for (int i = 0; i < kStepParams; ++i) { a.w[i] = masters[i]; a.off[i] = l.off[i]; a.size[i] = l.size[i]; }
     a.grads = grads_flat; a.clip_scale = clip ? h->clip_scale : nullptr; a.state1 = opt->state1; a.state2 = opt->state2; a.step = opt->step;
     a.ticket = h->apply_ticket; a.total = l.total; a.lr = opt->lr; a.decay1 = opt->decay1; a.decay2 = opt->decay2; a.eps = opt->eps; a.kind = opt->kind;
     hipLaunchKernelGGL(step_apply_kernel, dim3((unsigned)((l.total + 255) / 256)), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
+    return CAVOID_OK;
+}
+
+extern "C" int cavoid_policy_apply(cavoid_policy *h, const cavoid_policy_weights *w, const cavoid_policy_optimizer *opt, const float *grads_flat,
+                                   void *stream) {
+    if (!h) return CAVOID_EINVAL;
+    if (h->ws) return CAVOID_EUNSUPPORTED;                 // (cavoid_policy_apply_ws: another layout, another pack)
+    if (!w || w->struct_size != (int32_t)sizeof(cavoid_policy_weights) || !step_optimizer_ok(opt) || !grads_flat) return CAVOID_EINVAL;
+    float *const masters[kStepParams] = {const_cast<float *>(w->lstm_kernel), const_cast<float *>(w->lstm_bias), const_cast<float *>(w->layer1_kernel),
+                                         const_cast<float *>(w->layer1_bias), const_cast<float *>(w->layer2_kernel), const_cast<float *>(w->layer2_bias),
+                                         const_cast<float *>(w->fc1_kernel), const_cast<float *>(w->fc1_bias), const_cast<float *>(w->p_kernel),
+                                         const_cast<float *>(w->p_bias), const_cast<float *>(w->v_kernel), const_cast<float *>(w->v_bias)};
+    for (const float *p : masters)
+        if (!p) return CAVOID_EINVAL;
+    if ((w->avg == nullptr) != (w->std == nullptr)) return CAVOID_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(h->device));
+    if (const int rc = cavoid_policy_step_update(h, masters, step_layout(h->num_actions), opt, grads_flat, s)) return rc;
     return cavoid_policy_load(h, w, s);                    // the pack path itself: the handle is what a fresh load of the masters gives
 }

@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cavoid.h"
+
 namespace cavoid {
 
 typedef float step_f32x4 __attribute__((ext_vector_type(4)));
@@ -97,7 +99,8 @@ struct StepNormArgs {
     double clip;
 };
 
-#ifdef CAVOID_POLICY_STEP_KERNELS
+#if defined(CAVOID_POLICY_STEP_KERNELS) || defined(CAVOID_POLICY_STEP_TILES)
+// the tiles: every translation unit with step GEMM jobs of its own instantiates them (cavoid_policy_step.hip, cavoid_policy_step_ws.hip)
 
 #define STEP_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -131,15 +134,19 @@ __device__ __forceinline__ void step_gemm_44(const float *x, int ldx, const floa
         }
 }
 
-// edge tile of a 72-wide x: its columns 64..71 against a 64-column block of g.  x points at (first row, column 0), out at (row 0,
-// the block's first column) of the [72, ldo] partial
-__device__ __forceinline__ void step_gemm_14(const float *x, int ldx, const float *g, int ldg, int64_t n, float *out, int ldo, int lane) {
+// edge tile: LIVE (4 or 8) columns of x against a 64-column block of g -- the 72-wide operands' columns 64..71, the weight-sharing
+// network's host columns 0..3 of l1_in and its 8-wide f_in.  x points at (first row, first live column), out at (first live row, the
+// block's first column) of the partial.  The tile's columns LIVE..15 do not exist: zero, and never loaded (the address is clamped into
+// the live ones)
+template <int LIVE>
+__device__ __forceinline__ void step_gemm_edge(const float *x, int ldx, const float *g, int ldg, int64_t n, float *out, int ldo, int lane) {
+    static_assert(LIVE == 4 || LIVE == 8, "whole C/D row quads");
     step_f32x4 acc[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) acc[cb] = step_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     const int kq = lane >> 4, i = lane & 15, c4 = 4 * i;
-    const bool live = i < kStepIn - 64;                            // columns 72..79 of the tile do not exist: zero, and never loaded
-    const float *xp = x + (int64_t)kq * ldx + 64 + (i & 7), *gp = g + (int64_t)kq * ldg + c4;
+    const bool live = i < LIVE;
+    const float *xp = x + (int64_t)kq * ldx + (i & (LIVE - 1)), *gp = g + (int64_t)kq * ldg + c4;
     float v = xp[0];
     step_f32x4 b = *reinterpret_cast<const step_f32x4 *>(gp);
     for (int64_t r = 0; r < n; r += 4) {
@@ -151,10 +158,10 @@ __device__ __forceinline__ void step_gemm_14(const float *x, int ldx, const floa
         for (int cb = 0; cb < 4; ++cb) acc[cb] = STEP_MFMA(a, b[cb], acc[cb]);
         v = vn; b = bn;
     }
-    if (kq < 2) {                                                  // C/D rows 4 kq + r: the 8 live ones
+    if (4 * kq < LIVE) {                                           // C/D rows 4 kq + r: the live ones
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            *reinterpret_cast<step_f32x4 *>(out + (int64_t)(64 + 4 * kq + r) * ldo + c4) = step_f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+            *reinterpret_cast<step_f32x4 *>(out + (int64_t)(4 * kq + r) * ldo + c4) = step_f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
     }
 }
 
@@ -181,6 +188,13 @@ __device__ __forceinline__ void step_gemm_41(const float *x, int ldx, const floa
         for (int r = 0; r < 4; ++r) out[(int64_t)(4 * (4 * kq + r) + ca) * kStepHeads + j] = acc[ca][r];
 }
 
+#undef STEP_MFMA
+#endif  // the tiles
+
+#ifdef CAVOID_POLICY_STEP_KERNELS
+// the kernels: cavoid_policy_step.hip alone (step_norm_kernel and step_apply_kernel take the layout as an argument: the weight-sharing
+// network's step launches them through step_launch_update below)
+
 // grid: dense_slices * kStepDenseJobs + lstm_slices * kStepLstmJobs workgroups of ONE wavefront
 __global__ __launch_bounds__(64) void step_gemm_kernel(const StepGemmArgs a) {
     const int lane = threadIdx.x;
@@ -200,7 +214,8 @@ __global__ __launch_bounds__(64) void step_gemm_kernel(const StepGemmArgs a) {
             step_gemm_44(a.l1_in + r0 * kStepIn, kStepIn, a.g1 + r0 * kStepW + 64 * tg, kStepW, n, part + kStepOffL1 + 64 * tg, kStepW, lane);
         } else if (j < 40) {                                       // ... rows 64..71
             const int tg = j - 36;
-            step_gemm_14(a.l1_in + r0 * kStepIn, kStepIn, a.g1 + r0 * kStepW + 64 * tg, kStepW, n, part + kStepOffL1 + 64 * tg, kStepW, lane);
+            step_gemm_edge<kStepIn - 64>(a.l1_in + r0 * kStepIn + 64, kStepIn, a.g1 + r0 * kStepW + 64 * tg, kStepW, n,
+                                         part + kStepOffL1 + 64 * kStepW + 64 * tg, kStepW, lane);
         } else {                                                   // heads = z3^T gh
             const int tx = j - 40;
             step_gemm_41(a.z3 + r0 * kStepW + 64 * tx, kStepW, a.gh + r0 * kStepHeads, n, part + kStepOffHead + (int64_t)64 * tx * kStepHeads, lane);
@@ -211,7 +226,7 @@ __global__ __launch_bounds__(64) void step_gemm_kernel(const StepGemmArgs a) {
         const int64_t n = (a.lstm_rows - r0 < a.lstm_len) ? a.lstm_rows - r0 : a.lstm_len;
         float *part = a.scratch + a.dense_slices * kStepDensePartial + s * kStepLstmPartial + 64 * tg;
         if (j < 4) step_gemm_44(a.h_in + r0 * kStepIn, kStepIn, a.gl + r0 * kStepW + 64 * tg, kStepW, n, part, kStepW, lane);
-        else step_gemm_14(a.h_in + r0 * kStepIn, kStepIn, a.gl + r0 * kStepW + 64 * tg, kStepW, n, part, kStepW, lane);
+        else step_gemm_edge<kStepIn - 64>(a.h_in + r0 * kStepIn + 64, kStepIn, a.gl + r0 * kStepW + 64 * tg, kStepW, n, part + 64 * kStepW, kStepW, lane);
     }
 }
 
@@ -335,7 +350,19 @@ __global__ __launch_bounds__(256) void step_apply_kernel(const StepApplyArgs a) 
     }
 }
 
-#undef STEP_MFMA
 #endif  // CAVOID_POLICY_STEP_KERNELS
 
+// ---- host side, shared by cavoid_policy_step.hip and cavoid_policy_step_ws.hip ------------------------------------------------------
+inline bool step_rows_ok(int64_t capacity_rows) { return capacity_rows > 0 && capacity_rows % 64 == 0 && capacity_rows / 64 <= 0x7fffffffLL; }
+inline bool step_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool step_optimizer_ok(const cavoid_policy_optimizer *opt) {
+    return opt && opt->struct_size == (int32_t)sizeof(cavoid_policy_optimizer) && (opt->kind == CAVOID_OPT_ADAM || opt->kind == CAVOID_OPT_RMSPROP) &&
+           opt->state1 && opt->state2 && opt->step && opt->clip_average_norm >= 0.0;
+}
+
 }  // namespace cavoid
+
+// step_norm_kernel (when clipping) and step_apply_kernel on the twelve masters in layout `l` (cavoid_policy_step.hip): the update of
+// cavoid_policy_apply and cavoid_policy_apply_ws, up to the re-pack.  The caller has checked its arguments (step_optimizer_ok among them).
+int cavoid_policy_step_update(cavoid_policy *h, float *const *masters, const cavoid::StepLayout &l, const cavoid_policy_optimizer *opt,
+                              const float *grads_flat, hipStream_t stream);

@@ -193,9 +193,30 @@ def step_partition(max_others: int, rows: int) -> Tuple[int, int, int]:
     return -(-rows // STEP_DENSE_SLICE), lstm_len, -(-t // lstm_len)
 
 
+# the row slices of cavoid_policy_weight_grads_ws (kStepWsL1Slice, kStepWsFilterSlice, kStepWsFilterSliceWide, kStepWsFilterWideFrom of
+# cavoid_policy_step_ws.hpp -- tests/test_policy_step_ws_host.py holds them to the header's text, tests/test_gpu_policy_step_ws.py the
+# scratch size they give to the library's own answer)
+STEP_WS_L1_SLICE, STEP_WS_FILTER_SLICE, STEP_WS_FILTER_SLICE_WIDE, STEP_WS_FILTER_WIDE_FROM = 1024, 1024, 4096, 4194304
+
+
+def step_partition_ws(max_others: int, rows: int) -> Tuple[int, int, int, int, int]:
+    """(dense slices, layer1 slice length, layer1 slices, filter slice length, filter slices) of ``cavoid_policy_weight_grads_ws`` over
+    ``rows`` buffer rows: the dense slices are STEP_DENSE_SLICE rows, the filter's run over the flat ``max_others * rows`` rows."""
+    t = rows * max_others
+    l1_len = STEP_WS_L1_SLICE
+    f_len = STEP_WS_FILTER_SLICE_WIDE if t > STEP_WS_FILTER_WIDE_FROM else STEP_WS_FILTER_SLICE
+    return -(-rows // STEP_DENSE_SLICE), l1_len, -(-rows // l1_len), f_len, -(-t // f_len)
+
+
+def step_scratch_floats_ws(max_others: int, rows: int) -> int:
+    """the floats ``cavoid_policy_weight_grads_scratch_ws`` reports: one partial per slice (include/cavoid.h)"""
+    dense, _, l1, _, f = step_partition_ws(max_others, rows)
+    return l1 * (4 + 64 * max_others) * 256 + dense * (2 * 65536 + 256 * 16) + f * 8 * 64
+
+
 class DeviceStepOptimizer(object):
-    """What ``FusedA3CTrainer(device_step=True).opt`` is: the optimiser whose step is ``cavoid_policy_apply`` -- flat float32 state vectors in
-    the layout of ``cavoid_policy_param_layout``, a device step count -- behind the part of ``torch.optim.Optimizer``'s surface the training
+    """What ``FusedA3CTrainer(device_step=True).opt`` (or ``ws_device_step=True``) is: the optimiser whose step is ``cavoid_policy_apply`` (``_ws``)
+    -- flat float32 state vectors in the layout of ``cavoid_policy_param_layout`` (``_ws``), a device step count -- behind the part of ``torch.optim.Optimizer``'s surface the training
     loop and the checkpoints use: ``param_groups`` (``lr`` is read from group 0 at every step), ``step``, ``zero_grad``, ``state_dict`` /
     ``load_state_dict``.  'adam': the state dict is ``torch.optim.Adam``'s own, both ways, so a run resumes with or without the device
     step.  'rmsprop': its own format, marked ``"kind": "rmsprop"``."""
@@ -280,22 +301,30 @@ class FusedA3CTrainer(object):
     and re-packs the weights -- no GEMM library, no ``index_select``, no ``torch.optim`` launch behind the two trainer kernels.  With it,
     ``optimizer="rmsprop"`` (the reference's ``tf.train.RMSPropOptimizer``: RMSPROP_DEFAULTS) and ``grad_clip=c`` (``tf.clip_by_average_norm``
     per variable; the reference's GRAD_CLIP_NORM is 40) are available; ``opt`` is then a ``DeviceStepOptimizer``
-    (tests/test_gpu_policy_step.py)."""
+    (tests/test_gpu_policy_step.py).
+    ``ws_device_step=True`` (opt-in, 'weight_sharing' only, with or without ``ws_crowd``; profiles/policy_ws_device_step_timing.txt) is the
+    same for the weight-sharing network: ``cavoid_policy_weight_grads_ws`` and ``cavoid_policy_apply_ws`` on the layout of
+    ``cavoid_policy_param_layout_ws``; it sets ``device_step``, and everything above holds (tests/test_gpu_policy_step_ws.py)."""
 
     def __init__(self, net: NetworkVP_rnn, policy: Optional[FusedPolicy] = None, learning_rate: float = 2e-5, group=None,
                  distributed: Optional[bool] = None, crowd: bool = False, ws_crowd: bool = False, device_step: bool = False,
-                 optimizer: str = "adam", grad_clip: Optional[float] = None):
+                 optimizer: str = "adam", grad_clip: Optional[float] = None, ws_device_step: bool = False):
         from .network import A3CTrainer
         if optimizer not in ("adam", "rmsprop"):
             raise ValueError("optimizer must be 'adam' or 'rmsprop', not %r" % (optimizer,))
         if grad_clip is not None and not float(grad_clip) > 0.0:
             raise ValueError("grad_clip must be a positive average norm (or None), not %r" % (grad_clip,))
-        if not device_step and (optimizer != "adam" or grad_clip is not None):
-            raise ValueError("optimizer=%r / grad_clip=%r are steps of cavoid_policy_apply: they need device_step=True" % (optimizer, grad_clip))
+        if not device_step and not ws_device_step and (optimizer != "adam" or grad_clip is not None):
+            raise ValueError("optimizer=%r / grad_clip=%r are steps of cavoid_policy_apply: they need device_step=True (the weight_sharing "
+                             "network: ws_device_step=True)" % (optimizer, grad_clip))
         if device_step and net.arch == "weight_sharing":
-            raise ValueError("device_step=True carries the 'rnn' network only: the weight_sharing network's weight gradients and optimiser "
-                             "step stay with PyTorch (cavoid_policy_weight_grads is CAVOID_EUNSUPPORTED on a weight-sharing handle)")
-        self.device_step, self.optimizer, self.grad_clip = bool(device_step), optimizer, (float(grad_clip) if grad_clip is not None else None)
+            raise ValueError("device_step=True carries the 'rnn' network only (cavoid_policy_weight_grads is CAVOID_EUNSUPPORTED on a "
+                             "weight-sharing handle): the weight_sharing network finishes its step in the library with ws_device_step=True")
+        if ws_device_step and net.arch != "weight_sharing":
+            raise ValueError("ws_device_step=True carries the 'weight_sharing' network only, not %r: device_step=True is the 'rnn' network's"
+                             % (net.arch,))
+        self.device_step = bool(device_step) or bool(ws_device_step)
+        self.optimizer, self.grad_clip = optimizer, (float(grad_clip) if grad_clip is not None else None)
         self.ws = net.arch == "weight_sharing"          # cavoid_policy_train_ws (limit: FusedPolicy's MAX_OTHERS_WS, or _WS_CROWD)
         self.crowd = bool(crowd) and not self.ws and net.max_others > MAX_OTHERS
         # a weight-sharing network above MAX_OTHERS_WS: when asked to, or when the policy handed over already runs the ring kernels
@@ -320,6 +349,8 @@ class FusedA3CTrainer(object):
         H, A = net.HIDDEN, net.num_actions
         if self.ws:
             self.policy.refresh(with_backward=True)
+            if self.device_step:
+                self._begin_device_step(_lib.POLICY_PARAM_NAMES_WS, _lib.policy_param_layout_ws(net.max_others, A), optimizer, learning_rate)
             return
         # packed gate column k = 64w + 16 gate + u  <->  checkpoint column c = 64 gate + 16w + u
         c = torch.arange(4 * H, device=self.device)
@@ -331,38 +362,43 @@ class FusedA3CTrainer(object):
         self._l1_rows = torch.cat([torch.arange(H, H + net.HOST), torch.arange(0, H)]).to(self.device)
         self.policy.refresh(with_backward=True)
         if self.device_step:
-            self._layout = _lib.policy_param_layout(net.max_others, A)          # (offsets, sizes, total) in POLICY_PARAM_NAMES order
-            self._flat_grads = torch.zeros(self._layout[2], dtype=torch.float32, device=self.device)
-            self._grad_views = self._views(self._flat_grads)
-            self._grad_scratch = {}
-            for name, prm in net.named_parameters():
-                if prm.dtype != torch.float32 or not prm.is_contiguous() or prm.device != self.device:
-                    raise ValueError("device_step=True updates the module's own storage: %s must be contiguous float32 on %s" % (name, self.device))
-                prm.grad = self._grad_views[name]
-            self.opt = DeviceStepOptimizer(self, optimizer, self._base.opt, learning_rate)
+            self._begin_device_step(_lib.POLICY_PARAM_NAMES, _lib.policy_param_layout(net.max_others, A), optimizer, learning_rate)
+
+    def _begin_device_step(self, names, layout, optimizer: str, learning_rate: float) -> None:
+        """the flat gradient tensor in `layout` -- (offsets, sizes, total) in the order of `names` --, every ``.grad`` a view of it, and the optimiser"""
+        net = self.net
+        self._param_names, self._layout = names, layout
+        self._flat_grads = torch.zeros(self._layout[2], dtype=torch.float32, device=self.device)
+        self._grad_views = self._views(self._flat_grads)
+        self._grad_scratch = {}
+        for name, prm in net.named_parameters():
+            if prm.dtype != torch.float32 or not prm.is_contiguous() or prm.device != self.device:
+                raise ValueError("device_step=True updates the module's own storage: %s must be contiguous float32 on %s" % (name, self.device))
+            prm.grad = self._grad_views[name]
+        self.opt = DeviceStepOptimizer(self, optimizer, self._base.opt, learning_rate)
 
     def _views(self, flat: torch.Tensor) -> dict:
-        """{parameter name: view of ``flat`` in the parameter's shape} by the layout of ``cavoid_policy_param_layout``"""
+        """{parameter name: view of ``flat`` in the parameter's shape} by the layout of ``cavoid_policy_param_layout`` (``_ws``)"""
         off, size, _ = self._layout
-        return {name: flat[o:o + n].view_as(getattr(self.net, name)) for name, o, n in zip(_lib.POLICY_PARAM_NAMES, off, size)}
+        return {name: flat[o:o + n].view_as(getattr(self.net, name)) for name, o, n in zip(self._param_names, off, size)}
 
     def _weight_grads(self, t: dict, cbuf, rows64: int) -> None:
-        """``cavoid_policy_weight_grads`` on the buffers the launch pair just filled: every ``.grad`` (a view of the flat tensor) is set."""
-        pol = self.policy
+        """``cavoid_policy_weight_grads`` (``_ws``) on the buffers the launch pair just filled: every ``.grad`` (a view of the flat tensor) is set."""
+        pol, ws = self.policy, "_ws" if self.ws else ""
         gs = self._grad_scratch.get(rows64)
         if gs is None:
             floats = C.c_int64()
-            _lib.check(pol._lib.cavoid_policy_weight_grads_scratch(pol._h, rows64, C.byref(floats)), "cavoid_policy_weight_grads_scratch")
+            _lib.check(getattr(pol._lib, "cavoid_policy_weight_grads_scratch" + ws)(pol._h, rows64, C.byref(floats)), "cavoid_policy_weight_grads_scratch" + ws)
             gs = self._grad_scratch[rows64] = torch.empty(int(floats.value), dtype=torch.float32, device=self.device)
-            if len(self._grad_scratch) > 4:
+            if len(self._grad_scratch) > (2 if self.ws_crowd else 4):
                 self._grad_scratch.pop(next(iter(self._grad_scratch)))
-        _lib.check(pol._lib.cavoid_policy_weight_grads(pol._h, C.byref(cbuf), C.c_void_p(gs.data_ptr()), gs.numel(),
-                                                       C.c_void_p(self._flat_grads.data_ptr()), pol._stream()), "cavoid_policy_weight_grads")
+        _lib.check(getattr(pol._lib, "cavoid_policy_weight_grads" + ws)(pol._h, C.byref(cbuf), C.c_void_p(gs.data_ptr()), gs.numel(),
+                                                                        C.c_void_p(self._flat_grads.data_ptr()), pol._stream()), "cavoid_policy_weight_grads" + ws)
         for name, prm in self.net.named_parameters():      # (a caller's optimiser may have dropped them: zero_grad(set_to_none=True))
             prm.grad = self._grad_views[name]
 
     def _apply(self) -> None:
-        """``cavoid_policy_apply``: the optimiser step on the module's parameter storage from the flat gradients, then the re-pack."""
+        """``cavoid_policy_apply`` (``_ws``): the optimiser step on the module's parameter storage from the flat gradients, then the re-pack."""
         pol, opt = self.policy, self.opt
         g = opt.param_groups[0]
         o = _lib.CavoidPolicyOptimizer()
@@ -377,6 +413,13 @@ class FusedA3CTrainer(object):
         w = pol.weights_struct(with_backward=True)
         if pol._keep:
             raise ValueError("device_step=True updates the module's own storage: its parameters must stay contiguous float32 on %s" % (self.device,))
+        if self.ws:                                        # (the filter's two variables are not in the struct: the same check for them)
+            n = self.net
+            if any(t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device for t in (n.other_kernel, n.other_bias)):
+                raise ValueError("device_step=True updates the module's own storage: its parameters must stay contiguous float32 on %s" % (self.device,))
+            _lib.check(pol._lib.cavoid_policy_apply_ws(pol._h, C.byref(w), C.c_void_p(n.other_kernel.data_ptr()), C.c_void_p(n.other_bias.data_ptr()),
+                                                       C.byref(o), C.c_void_p(self._flat_grads.data_ptr()), pol._stream()), "cavoid_policy_apply_ws")
+            return
         _lib.check(pol._lib.cavoid_policy_apply(pol._h, C.byref(w), C.byref(o), C.c_void_p(self._flat_grads.data_ptr()), pol._stream()),
                    "cavoid_policy_apply")
 

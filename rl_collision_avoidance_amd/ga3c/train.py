@@ -129,11 +129,16 @@ def main(argv=None) -> None:
                     help="finish the fused 'rnn' trainer's step inside the HIP library (FusedA3CTrainer(device_step=True): cavoid_policy_weight_grads "
                          "+ cavoid_policy_apply) instead of PyTorch's GEMMs, index_selects and torch.optim.Adam; opt-in (one step with and "
                          "without it: tools/trainbench.py --device-step)")
+    ap.add_argument("--ws-device-step", action="store_true",
+                    help="the same for the fused 'weight_sharing' trainer (--arch weight_sharing, with or without --fused-crowd-ws; "
+                         "FusedA3CTrainer(ws_device_step=True): cavoid_policy_weight_grads_ws + cavoid_policy_apply_ws); opt-in (one step with and "
+                         "without it: tools/trainbench.py --ws-device-step)")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "rmsprop"],
-                    help="rmsprop: the reference's tf.train.RMSPropOptimizer (decay 0.99, momentum 0.0, epsilon 0.1); needs --device-step")
+                    help="rmsprop: the reference's tf.train.RMSPropOptimizer (decay 0.99, momentum 0.0, epsilon 0.1); needs --device-step "
+                         "(--ws-device-step for --arch weight_sharing)")
     ap.add_argument("--grad-clip", type=float, default=None, metavar="C",
                     help="USE_GRAD_CLIP: tf.clip_by_average_norm of every variable's gradient at C (the reference's GRAD_CLIP_NORM is 40); "
-                         "needs --device-step")
+                         "needs --device-step (--ws-device-step for --arch weight_sharing)")
     ap.add_argument("--scenario", default="ring", choices=["ring", "box"],
                     help="scenario generator: ring = GEN v1 (antipodal goals on a ring), box = GEN v2 (random starts / goals in a box "
                          "with minimum separations: the shape of the reference's get_testcase_random, TEST_CASE_FN run-ws/config.yaml:281-283)")
@@ -248,18 +253,24 @@ def main(argv=None) -> None:
                   % ("the PyTorch network" if (torch_policy or net.arch != "rnn") else "the fused crowd policy kernel", POLICY_MAX_OTHERS, M),
                   flush=True)
     fused = None if torch_policy else FusedPolicy(net, seed=1000 * args.seed + rank, ws_crowd=ws_crowd)
-    if (args.device_step or args.optimizer != "adam" or args.grad_clip is not None) and (autograd_trainer or net.arch != "rnn" or not args.device_step):
-        raise SystemExit("--device-step runs behind the fused 'rnn' trainer kernels (not --autograd-trainer, --arch weight_sharing or rows this "
-                         "run trains through autograd), and --optimizer rmsprop / --grad-clip need --device-step")
+    step_flag = "--ws-device-step" if net.arch == "weight_sharing" else "--device-step"
+    on_device = args.ws_device_step if net.arch == "weight_sharing" else args.device_step
+    if (args.device_step or args.ws_device_step or args.optimizer != "adam" or args.grad_clip is not None) and (
+            autograd_trainer or not on_device or (args.device_step and args.ws_device_step)):
+        raise SystemExit("--device-step runs behind the fused 'rnn' trainer kernels and --ws-device-step behind the fused 'weight_sharing' ones "
+                         "(neither with --autograd-trainer or rows this run trains through autograd), and --optimizer rmsprop / --grad-clip "
+                         "need the one of the two that is this network's: %s" % step_flag)
     if autograd_trainer:
         trainer = A3CTrainer(net, learning_rate=args.lr)
     else:
         trainer = FusedA3CTrainer(net, fused, learning_rate=args.lr, crowd=crowd_trainer, ws_crowd=ws_crowd,   # shares (or creates) the packed-weight handle
-                                  device_step=args.device_step, optimizer=args.optimizer, grad_clip=args.grad_clip)
+                                  device_step=args.device_step, optimizer=args.optimizer, grad_clip=args.grad_clip,
+                                  ws_device_step=args.ws_device_step)
     if rank == 0 and not args.play:
-        if args.device_step:
-            print("trainer tail: cavoid_policy_weight_grads + cavoid_policy_apply (%s%s) inside the HIP library"
-                  % (args.optimizer, ", clip_by_average_norm %g" % args.grad_clip if args.grad_clip is not None else ""), flush=True)
+        if on_device:
+            print("trainer tail: cavoid_policy_weight_grads%s + cavoid_policy_apply%s (%s%s) inside the HIP library"
+                  % ((("_ws", "_ws") if args.ws_device_step else ("", "")) +
+                     (args.optimizer, ", clip_by_average_norm %g" % args.grad_clip if args.grad_clip is not None else "")), flush=True)
         else:
             print("trainer tail: PyTorch (%s, torch.optim.Adam)"
                   % ("autograd" if autograd_trainer else "library GEMMs for the weight gradients"), flush=True)

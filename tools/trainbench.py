@@ -13,7 +13,10 @@ cavoid_policy_wsring.hpp, ws_crowd=True; figures go to profiles/policy_wsring_ti
   torch tail:   FusedA3CTrainer.train as above (library GEMMs, index_selects, torch.optim.Adam, re-pack)
   device step:  FusedA3CTrainer(device_step=True).train (cavoid_policy_weight_grads + cavoid_policy_apply behind the same launch pair)
 alternating on the same rows, and the two new calls timed apart on the buffers of the last step.  Per leg: the rounds' medians, their
-median and their spread (max - min over the rounds); figures go to profiles/policy_device_step_timing.txt."""
+median and their spread (max - min over the rounds); figures go to profiles/policy_device_step_timing.txt.
+--ws-device-step: the same two legs for the weight-sharing network (32 768 rows at M = 7, 16 384 rows at M = 19 and at M = 63, ws_crowd) --
+FusedA3CTrainer.train against FusedA3CTrainer(ws_device_step=True).train (cavoid_policy_weight_grads_ws + cavoid_policy_apply_ws), and the two
+new calls apart; figures go to profiles/policy_ws_device_step_timing.txt."""
 import argparse
 import os
 import statistics
@@ -42,20 +45,26 @@ def median_us(fn, reps):
     return statistics.median(times)
 
 
-def device_step_legs(reps, rounds):
-    print("M   rows    torch tail step (us)           device step (us)               weight_grads (us)     apply (us)            torch / device")
-    for M, B in ((3, 32768), (19, 16384), (63, 16384)):
+def device_step_legs(reps, rounds, ws=False):
+    print("M   rows    torch tail step (us)           device step (us)               weight_grads%s (us)     apply%s (us)            torch / device"
+          % (("_ws", "_ws") if ws else ("", "")))
+    for M, B in ((7 if ws else 3, 32768), (19, 16384), (63, 16384)):
         class Cfg(EnvConfig):
             def __init__(self):
                 self.MAX_NUM_AGENTS_IN_ENVIRONMENT = M + 1
                 EnvConfig.__init__(self)
-        net_t, net_d = NetworkVP_rnn(Cfg()).cuda(), NetworkVP_rnn(Cfg()).cuda()
+        arch = "weight_sharing" if ws else "rnn"
+        net_t, net_d = NetworkVP_rnn(Cfg(), arch=arch).cuda(), NetworkVP_rnn(Cfg(), arch=arch).cuda()
         g = torch.Generator().manual_seed(0)
         x = torch.randn((B, net_t.input_size), generator=g) * net_t.std.cpu() + net_t.avg.cpu()
         x[:, 0] = torch.randint(0, M + 1, (B,), generator=g).float()
         x, y, a = x.cuda(), torch.randn(B, generator=g).cuda(), torch.randint(0, net_t.num_actions, (B,), generator=g).cuda()
-        tt = FusedA3CTrainer(net_t, learning_rate=0.0, crowd=M > MAX_OTHERS)
-        td = FusedA3CTrainer(net_d, learning_rate=0.0, crowd=M > MAX_OTHERS, device_step=True)
+        if ws:
+            tt = FusedA3CTrainer(net_t, learning_rate=0.0, ws_crowd=M > MAX_OTHERS_WS)
+            td = FusedA3CTrainer(net_d, learning_rate=0.0, ws_crowd=M > MAX_OTHERS_WS, ws_device_step=True)
+        else:
+            tt = FusedA3CTrainer(net_t, learning_rate=0.0, crowd=M > MAX_OTHERS)
+            td = FusedA3CTrainer(net_d, learning_rate=0.0, crowd=M > MAX_OTHERS, device_step=True)
         rows64 = FusedA3CTrainer.buffer_rows(B)
         t_t, t_d, t_g, t_a = [], [], [], []
         for _ in range(rounds):
@@ -79,9 +88,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--arch", default="rnn", choices=["rnn", "weight_sharing"])
     ap.add_argument("--device-step", action="store_true")
+    ap.add_argument("--ws-device-step", action="store_true")
     args = ap.parse_args()
-    if args.device_step:
-        return device_step_legs(args.reps, args.rounds)
+    if args.device_step or args.ws_device_step:
+        return device_step_legs(args.reps, args.rounds, ws=args.ws_device_step)
     B = args.rows
     print("M   rows    scratch (GB)  fused step (us)                autograd step (us)             autograd / fused")
     for M in args.max_other:
