@@ -439,6 +439,49 @@ int cavoid_actor_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_rollout *
                         float *obs_cur, float *obs_next, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values,
                         int32_t n_steps, int32_t greedy, void *stream);
 
+/* ---- evaluation: K greedy (or sampled) steps of every world in ONE launch, with outcome records ------------------------------------
+ * The EVALUATE_MODE loop (argmax actions, ga3c/GA3C/ProcessAgent.py:98-103; every agent of a world must finish) without the host in it:
+ * per tile of floor(64/N) worlds a workgroup runs cavoid_policy_forward's arithmetic on the tile's rows that still need an action (a
+ * learning agent whose state carries no terminal flag; the other rows are handed action 0 / value 0), steps the tile's worlds WITHOUT
+ * auto-reset (cavoid_step's arithmetic: a world that is over stays as it is) and records the outcome -- up to n_steps times, and a tile
+ * whose worlds are all over leaves the loop at once.  "Over" is cavoid_step's game_over: no learning agent -- with evaluate_mode no agent
+ * at all -- of the world is still running; at the first step of a launch it is read from the world state's flags, so a launch on
+ * finished worlds does nothing, and a chain of launches continues where the last one stopped.  Trajectories are bit-identical to calling
+ * cavoid_policy_forward (+ cavoid_policy_forward_rows on `frozen` for the CAVOID_POLICY_FROZEN_NET rows) and cavoid_step per step.
+ *   obs [W,N,1+D]: the current observation on entry (cavoid_reset's, or the last launch's); every step writes the next one into the SAME
+ *   buffer, so on return it holds, per tile, the observation after that tile's last step.
+ *   rewards / done / game_over / actions int32 [W,N] / values float [W,N]: per-step outputs, per tile its last step's; never read.
+ *   buffers: the records, caller-owned device memory that the caller zeroes before an episode's first launch; read at a tile's first
+ *   step of the launch and written back when it leaves.
+ *     ret double [W*N]         An agent's return sums the rewards up to and including the step at which its world is over.
+ *                              (float64, added in step order.  Rewards cavoid_step would go on paying a finished world -- with a
+ *                              reward_time_step every step -- are NOT in it: the kernel never takes those steps.)
+ *     goal_step int32 [W*N]    the world's step count at the step that first left the agent with CAVOID_F_AT_GOAL (time to goal =
+ *                              goal_step * dt); 0: not reached
+ *     world_steps int32 [W]    steps the world has taken = the step at which it was over, once it is
+ *     worlds_running int32 [1] OUTPUT: worlds not over when their tile left this launch.  Zeroed by the call on the stream, then one
+ *                              atomic add per tile; read it after the launch to decide whether another one is needed.
+ *   greedy != 0: argmax; 0: the Philox draw of cavoid_policy_forward for (seed, row, step counter + t).  The policy's step counter
+ *   advances by n_steps on the device, whatever the tiles did.
+ * Routing as cavoid_actor_run / _run_mix: rvo_enabled (and in-step box scenarios) run over the env step's ORCA instantiation, a `frozen`
+ * handle (may be NULL) drives the frozen-network agents by its argmax; CAVOID_ACTOR_QUAD applies.  The scenario look-ahead is not
+ * touched: nothing restarts.
+ * CAVOID_EINVAL: null handles, buffers or record pointers, a wrong struct_size, handles that do not describe the same batch
+ * (cavoid_actor_run's checks).  CAVOID_EUNSUPPORTED (evaluate step by step): exactly what cavoid_actor_run / _run_mix refuse -- a
+ * weight-sharing handle, more than 16 agents per world, a policy (or frozen) handle of more than 19 observed agents, holonomic dynamics,
+ * CAVOID_POLICY_F32 / a non-default CAVOID_POLICY_PRODUCTS, an env step whose LDS does not fit what the policy lends it, and an env whose
+ * generator makes frozen-network agents when `frozen` is NULL.  n_steps == 0: CAVOID_OK, nothing is launched or written. */
+typedef struct cavoid_eval_buffers {
+    int32_t struct_size;             /* sizeof(cavoid_eval_buffers) */
+    double *ret;                     /* [W*N] */
+    int32_t *goal_step;              /* [W*N] */
+    int32_t *world_steps;            /* [W] */
+    int32_t *worlds_running;         /* [1] */
+} cavoid_eval_buffers;
+int cavoid_eval_run(cavoid_env *env, cavoid_policy *policy, cavoid_policy *frozen /* or NULL */, const cavoid_eval_buffers *buffers,
+                    float *obs, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps,
+                    int32_t greedy, void *stream);
+
 /* cavoid_step_autoreset + cavoid_rollout_push as ONE launch: the env step of every world and the Experience bookkeeping of its slots
  * (ProcessAgent.py:149-211) -- the fused actor's env phase for actors whose policy is a launch of its own (frozen-network agents,
  * a caller-supplied policy).  obs_cur [W,N,1+D]: the observation `actions` / `values` (V(s_t)) were computed on; the step writes the

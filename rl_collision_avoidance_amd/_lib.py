@@ -95,6 +95,11 @@ class CavoidRolloutBuffers(C.Structure):
         ("dup_capacity", C.c_int64), ("ep_out", C.c_void_p), ("ep_count", C.c_void_p), ("ep_capacity", C.c_int64)]
 
 
+class CavoidEvalBuffers(C.Structure):
+    """Mirror of ``struct cavoid_eval_buffers`` (include/cavoid.h): the outcome records handed to ``cavoid_eval_run``."""
+    _fields_ = [("struct_size", C.c_int32)] + [(n, C.c_void_p) for n in ("ret", "goal_step", "world_steps", "worlds_running")]
+
+
 class CavoidError(RuntimeError):
     def __init__(self, code: int, where: str):
         msg = lib().cavoid_strerror(code).decode()
@@ -158,6 +163,7 @@ SYMBOLS = [
     ("cavoid_actor_run_mix", C.c_int, [_P, _P, _P, _P, C.POINTER(CavoidRolloutBuffers)] + [_P] * 7 + [C.c_int32, C.c_int32, _P]),
     ("cavoid_crowd_actor_run", C.c_int, [_P, _P, _P, C.POINTER(CavoidRolloutBuffers)] + [_P] * 7 + [C.c_int32, C.c_int32, _P]),
     ("cavoid_actor_run_ws", C.c_int, [_P, _P, _P, C.POINTER(CavoidRolloutBuffers)] + [_P] * 7 + [C.c_int32, C.c_int32, _P]),
+    ("cavoid_eval_run", C.c_int, [_P, _P, _P, C.POINTER(CavoidEvalBuffers)] + [_P] * 6 + [C.c_int32, C.c_int32, _P]),
     ("cavoid_step_push", C.c_int, [_P, _P, C.POINTER(CavoidRolloutBuffers)] + [_P] * 7 + [C.c_int32, _P]),
     ("cavoid_rollout_compact", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32] + [_P] * 9 + [C.c_int64, _P]),
     ("cavoid_rollout_active_rows", C.c_int, [_P] * 7),

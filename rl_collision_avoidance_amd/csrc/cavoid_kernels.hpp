@@ -1333,7 +1333,8 @@ enum : int { MODE_STEP = 0, MODE_STEP_AUTORESET = 1, MODE_OBSERVE = 2, MODE_RESE
 // registers (N = 10: +40 VGPRs and scratch) for code it never runs.
 // what the last step of a tile left in the lane's registers, for a caller that goes on in the same kernel (the fused actor:
 // cavoid_actor.hpp hands it to the experience bookkeeping)
-struct StepOut { float reward; bool done, game_over; bool learning_next; };   // learning_next: column 0 of the NEXT observation (after a restart: the new agent's)
+struct StepOut { float reward; bool done, game_over; bool learning_next; uint32_t flags; };   // learning_next: column 0 of the NEXT observation (after a restart: the new agent's)
+                                                                                            // flags: the agent's flags as the step left them, before a restart (the evaluation recorder, cavoid_eval.hpp)
 
 // The body of env_kernel for ONE tile (one wavefront): lds_tab = the workgroup's action-table copy, wbase = the wavefront's
 // private LDS (staging arrays, obs tile, ORCA scratch), wave = the tile's index.  A device function so that the fused actor
@@ -1615,7 +1616,7 @@ __device__ __forceinline__ void env_tile(const KCfg &c, const KState &s, const P
         const bool game_over = (running & wmask) == 0ull;
         rew_f = (float)r;
         done_f = done ? 1.0f : 0.0f;
-        if (out) { out->reward = rew_f; out->done = done; out->game_over = game_over; }
+        if (out) { out->reward = rew_f; out->done = done; out->game_over = game_over; out->flags = a.flags; }
         if (active) {
             if (!packed) {
                 io.rew[slot_w * N + a_idx] = rew_f;

@@ -116,8 +116,9 @@ __device__ __forceinline__ void quad_rows(const KCfg &c, QuadShared<N> &sh, cons
 
 // One auto-reset step of tile `wave` by the four wavefronts (role = 0..3, wave-uniform) of a workgroup.  smem: quad_lds_bytes<N>(tile
 // floats) of the workgroup's LDS.  Contains workgroup barriers: every thread of the four wavefronts calls it.  out (role 0 only): what
-// env_tile hands a caller that goes on in the same kernel.
-template <int N>
+// env_tile hands a caller that goes on in the same kernel.  AUTO = false: the step WITHOUT auto-reset (env_tile<N, MODE_STEP>'s: a world that is
+// over stays as it is; the evaluation kernel, cavoid_eval.hpp) -- the restart rounds and their barriers are then never taken.
+template <int N, bool AUTO = true>
 __device__ __forceinline__ void quad_env_tile(const KCfg &c, const KState &s, const PoolRec *pool, const KIO &io, unsigned char *smem, const int role,
                                               const int lane, const int64_t wave, StepOut *out = nullptr) {
     constexpr int K = Others<N>::K;
@@ -251,7 +252,7 @@ __device__ __forceinline__ void quad_env_tile(const KCfg &c, const KState &s, co
         const unsigned long long wmask = ((1ull << N) - 1ull) << base;
         const bool game_over = (running & wmask) == 0ull;
         const float rew_f = (float)r, done_f = done ? 1.0f : 0.0f;
-        if (out) { out->reward = rew_f; out->done = done; out->game_over = game_over; }
+        if (out) { out->reward = rew_f; out->done = done; out->game_over = game_over; out->flags = a.flags; }
         if (active) {
             if (!packed) {
                 io.rew[a_idx] = rew_f;
@@ -259,8 +260,8 @@ __device__ __forceinline__ void quad_env_tile(const KCfg &c, const KState &s, co
             }
             if (i == 0) io.game_over[w] = game_over ? 1 : 0;
         }
-        const bool restart = active && game_over;
-        const bool any_restart = __ballot(restart) != 0ull;     // (wave-uniform)
+        const bool restart = AUTO && active && game_over;
+        const bool any_restart = AUTO && __ballot(restart) != 0ull;     // (wave-uniform)
         if (CAVOID_RARE(any_restart)) {                         // some world of this tile restarts: restage, one more pair round
             if (restart) {
                 episode += 1u;

@@ -108,6 +108,12 @@ def main(argv=None) -> None:
     ap.add_argument("--evaluate", type=int, default=0, metavar="ROUNDS",
                     help="EVALUATE_MODE instead of training: ROUNDS x --worlds episodes with argmax actions, every agent must "
                          "finish; prints success / collision / timeout rates (use with --load)")
+    ap.add_argument("--fused-evaluate", action="store_true",
+                    help="with --evaluate: run each round as launches of --steps-per-graph env steps of ONE kernel (cavoid_eval_run: policy, "
+                         "argmax, env.step without auto-reset and the outcome record per tile of worlds, finished tiles leave early) instead of "
+                         "one policy launch, one env launch and one host synchronisation per env step; same numbers.  The run ends if the "
+                         "configuration is one the kernel does not carry (crowd worlds, the weight_sharing network, more than 19 observed "
+                         "neighbours, the PyTorch policy).  Opt-in (profiles/eval_fused_timing.txt: tools/evalbench.py)")
     ap.add_argument("--pretrain-steps", type=int, default=0,
                     help="supervised initialisation before RL (the role of Regression.py): Adam steps on teacher-driven rollouts")
     ap.add_argument("--fused-regression", action="store_true",
@@ -296,10 +302,21 @@ def main(argv=None) -> None:
         return FusedPolicy(frozen_net, seed=0, ws_crowd=ws_crowd)
     if args.evaluate:
         frozen = make_frozen()
-        from .evaluate import evaluate
+        from .evaluate import evaluate, evaluate_fused_unavailable_reason
         if fused is not None:
             fused.refresh(check_range=True)                   # (a checkpoint may have been loaded: a weight beyond the float16 split's range fails loudly)
-        res = evaluate(env, fused if fused is not None else net.predict_p_and_v, rounds=args.evaluate, frozen_policy=frozen)
+        eval_policy = fused if fused is not None else net.predict_p_and_v
+        if args.fused_evaluate:
+            why = evaluate_fused_unavailable_reason(env, eval_policy, frozen)
+            if why is not None:
+                raise SystemExit("--fused-evaluate: the fused evaluation kernel (cavoid_eval_run) does not apply: " + why)
+            if args.steps_per_graph < 1:
+                raise SystemExit("--steps-per-graph must be >= 1")
+            if rank == 0:
+                print("[Evaluate] fused evaluation kernel (cavoid_eval_run), %d env steps per launch" % args.steps_per_graph, flush=True)
+            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused=True, steps_per_launch=args.steps_per_graph)
+        else:
+            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen)
         if rank == 0:
             print("[Evaluate] " + "  ".join("%s %.4f" % (k, v) if isinstance(v, float) else "%s %d" % (k, v) for k, v in res.items()),
                   flush=True)
