@@ -288,6 +288,10 @@ extern "C" int cavoid_create(const cavoid_cfg *cfg, int64_t num_worlds, int64_t 
         const int v = std::atoi(ov);
         if (v >= 1 && v <= cavoid::kRelayMaxConsumers) e->relay_consumers = v;
     }
+    if (const char *ov = std::getenv("CAVOID_RELAY_TILES")) {
+        const int v = std::atoi(ov);
+        if (v == 1 || v == 2) e->relay_tiles = v;
+    }
     if (crowd_form(N)) {
         // the crowd form (cavoid_crowd.hpp): one wavefront per workgroup, floor(64/N) worlds per wavefront; the obs tile shares the
         // sort keys' region (N-1 x 64 x 8 bytes) and takes as many whole rows of 4 as that holds -- the rows go out in passes

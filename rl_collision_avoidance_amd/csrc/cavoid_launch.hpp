@@ -31,6 +31,11 @@ struct cavoid_env {
     int relay_topup_nc = -1;            // env_relay_kernel's top-up wavefront: the shape (consumers, dynamic LDS) the occupancy calculator was last
     size_t relay_topup_lds = 0;         // asked about, and whether two workgroups per CU are resident with it
     bool relay_topup_fits = false;
+    int relay_tiles = 0;                // env_relay_kernel's tiles per workgroup: 0 = where it pays (cavoid_relay.hip, relay_duo_wanted), 1 / 2 forced (CAVOID_RELAY_TILES)
+    int relay_duo_nc = -1;              // ... the two-tile shape (consumers, dynamic LDS) the device was last asked about, and whether one workgroup of it
+    size_t relay_duo_lds = 0;           // is resident: bit 0 without, bit 1 with the top-up wavefronts
+    int relay_duo_fit = 0;
+    int relay_cus = 0;                  // the device's CU count, once asked (relay_duo_wanted)
     void *slab = nullptr;
     void *pool_slab = nullptr;
     double *d_actions = nullptr;
@@ -38,7 +43,8 @@ struct cavoid_env {
     int grid = 0;
     int pipeline = 2;            // latency mode, multi-step launches: 2 = env_relay_kernel (roles on 5-7 wavefronts per tile), 1 = env_pipe_kernel
                                  // (two wavefronts per tile), 0 = one wavefront per tile (CAVOID_PIPELINE)
-    int relay_consumers = 3;     // observation wavefronts per tile of env_relay_kernel (CAVOID_RELAY_CONSUMERS, 1..4)
+    int relay_consumers = 0;     // observation wavefronts per tile of env_relay_kernel (CAVOID_RELAY_CONSUMERS, 1..4); 0: the launcher's default
+                                 // (3 with one tile per workgroup, 4 with two: cavoid_relay.hip)
     int latency_mode = 0;        // small batch: multi-step launches keep the next pool record in registers (MODE_STEP_AUTORESET_PF)
     int quad = -1;               // one-step auto-reset launches with four cooperating wavefronts per tile (env_quad_kernel): -1 = where it pays
                                  // (<= 512 tiles), 0 / 1 = never / wherever it can run (CAVOID_QUAD)

@@ -30,6 +30,10 @@
 //                      cavoid_quad.hpp -- all three are idle once the last step is settled, and the launch's tail is one
 //                      observation latency behind that moment (relay_coop_last).
 //
+// One workgroup per tile (TPW = 1), or -- where two tiles share every CU anyway -- one workgroup of up to 16 wavefronts for TWO tiles (TPW = 2,
+// relay_duo_slot below): the roles dealt by SIMD, four consumers per tile, each tile with its own LDS region and nothing shared but the
+// prologue's barrier (profiles/relay_duo_timing.txt: -8.7 % per step at 4 x 8192).
+//
 // Same arithmetic per value, in the same operation order, as env_kernel: outputs and state are bit-identical
 // (tests/test_gpu_packed.py, test_gpu_parity.py run through this kernel by default).  Synchronisation: sequence counters in
 // LDS, polled (s_sleep); an LDS write of a wavefront is visible to the workgroup in issue order, so "data, then counter" on
@@ -135,6 +139,36 @@ __host__ __device__ constexpr size_t relay_lds_fixed_bytes() {
     return (size_t)lds_floats_block() * sizeof(float) + sizeof(RelaySeq) + kRelayActRing * 64 + relay_ring<N>() * (sizeof(RelayTent) + sizeof(RelayRes)) +
            sizeof(RelayNxt) + kRelayEvq * sizeof(unsigned long long) + relay_coop_bytes<N>();
 }
+
+// ---- two tiles per workgroup (TPW = 2) ---------------------------------------------------------------------------------------------------
+// Two independent workgroups per CU land where the hardware puts them (the second starts where the first ended in 197 of 256 CUs only,
+// profiles/relay_trim_timing.txt table 4), and three consumers per tile cannot be dealt evenly over four SIMDs.  ONE workgroup that owns the
+// tiles 2 b and 2 b + 1 (a and b below) is alone on its CU, and inside a workgroup placement is a rule -- wavefront w runs on SIMD
+// (first + w) % 4 -- so the roles are dealt by SIMD: the four chain wavefronts first, one per SIMD and never a D beside a P; then the
+// consumers, round-robin over the SIMDs; then the loaders and, LAST, the top-up wavefronts:
+//      wavefront  0 Da  1 Db  2 Pa  3 Pb | 4 .. 3 + 2 NC  consumers | 4 + 2 NC La, Lb | 6 + 2 NC Ta, Tb
+// With four consumers that is SIMD 0: Da C C La, 1: Db C C Lb, 2: Pa C C Ta, 3: Pb C C Tb.  A launch without the top-up does not LAUNCH the
+// two T wavefronts (they are the last two: every other wavefront keeps its SIMD), and a launch with fewer consumers leaves their wavefronts
+// out the same way: the workgroup is 2 * (3 + NC + top-up) wavefronts and the table is compact, so NC follows from the block size as it does
+// for TPW = 1.  Which tile's consumers sit beside which chain wavefront is CAVOID_RELAY_DUO_MATE: 0 -- each chain wavefront beside its OWN
+// tile's consumers; 1 -- beside the other tile's.
+// The tiles share nothing but the prologue's workgroup barrier: each has its own LDS region (counters, rings, tiles), one behind the other.
+#ifndef CAVOID_RELAY_DUO_MATE
+#define CAVOID_RELAY_DUO_MATE 0
+#endif
+constexpr int kRelayDuoMaxN = 5;          // (N = 6: 144 vector registers, and its LDS does not fit twice)
+__host__ __device__ constexpr int relay_duo_waves(int NC, int topup) { return 2 * (3 + NC + (topup ? 1 : 0)); }
+// wavefront wv of a TPW = 2 workgroup: (tile << 4) | role, the role numbered as for TPW = 1 (0 D, 1 P, 2 .. 1 + NC consumers, 2 + NC L, 3 + NC T)
+__host__ __device__ constexpr int relay_duo_slot(int wv, int NC, int mate = CAVOID_RELAY_DUO_MATE) {
+    if (wv < 4) return ((wv & 1) << 4) | (wv >> 1);
+    const int k = wv - 4;
+    if (k < 2 * NC) return ((((k & 1) ^ mate) & 1) << 4) | (2 + (k >> 1));
+    return (((k - 2 * NC) & 1) << 4) | (2 + NC + ((k - 2 * NC) >> 1));
+}
+// a tile's LDS region, the workgroup's dynamic LDS and where the region of the workgroup's tile `tsel` begins
+__host__ __device__ constexpr size_t relay_region_bytes(size_t fixed, int nc, int tile_floats) { return fixed + (size_t)nc * tile_floats * sizeof(float); }
+__host__ __device__ constexpr size_t relay_lds_bytes(int tpw, size_t fixed, int nc, int tile_floats) { return tpw * relay_region_bytes(fixed, nc, tile_floats); }
+__host__ __device__ constexpr size_t relay_region_offset(int tsel, size_t fixed, int nc, int tile_floats) { return tsel * relay_region_bytes(fixed, nc, tile_floats); }
 
 // development build: lane 0 of a role stamps the shader clock of step n_steps/2 into g_trace[tile*32 + k] (tools/trace_relay.py)
 #ifdef CAVOID_TRACE
@@ -429,7 +463,7 @@ typedef const __attribute__((address_space(4))) RelayArgs *RelayArgP;
     [[maybe_unused]] const int ostride = io.obs_stride;                                                \
     [[maybe_unused]] const int tile_floats = (c.tile_rows * ostride + 3) & ~3;                         \
     const int wpw = c.wpw, lanes_used = wpw * N;                                                       \
-    [[maybe_unused]] const int64_t wave = blockIdx.x;      /* one tile per workgroup */                \
+    [[maybe_unused]] const int64_t wave = tile_index;      /* the workgroup's tile (TPW = 2: this wavefront's of its two) */ \
     const int64_t w0 = wave * wpw;                                                                     \
     const int lw = lane0 / N;                                                                          \
     [[maybe_unused]] const int i0 = lane0 - lw * N;                                                    \
@@ -442,8 +476,8 @@ typedef const __attribute__((address_space(4))) RelayArgs *RelayArgP;
     if (worlds_here > wpw) worlds_here = wpw;                                                          \
     if (worlds_here < 0) worlds_here = 0;                                                              \
     [[maybe_unused]] const int n_steps = io.n_steps
-template <int N>
-__device__ __forceinline__ void relay_coop_last(unsigned char *smem) {
+template <int N, int TPW>
+__device__ __forceinline__ void relay_coop_last(unsigned char *smem) {      // smem: the tile's LDS region
     unsigned char *sp = smem + lds_floats_block() * sizeof(float);
     RelaySeq *seq = reinterpret_cast<RelaySeq *>(sp); sp += sizeof(RelaySeq) + kRelayEvq * sizeof(unsigned long long);
     const unsigned long long kp = (unsigned long long)(uint32_t)relay_peek(&seq->kernarg[0]) | ((unsigned long long)(uint32_t)relay_peek(&seq->kernarg[1]) << 32);
@@ -460,8 +494,14 @@ __device__ __forceinline__ void relay_coop_last(unsigned char *smem) {
     const int lane0 = threadIdx.x & 63;
     const int tile_nc = relay_peek(&seq->tile_id);          // the tile and, above bit 16, the consumer count (a launch with the top-up has one
     const int NC = tile_nc >> 16;                           // wavefront more than 3 + NC: not derived from the block size here)
-    const int role = relay_role_of(threadIdx.x >> 6, NC);
-    const int pw = role < 2 ? role : 2;                     // D 0, P 1, L 2
+    int pw;                                                 // D 0, P 1, L 2
+    if constexpr (TPW == 2) {
+        const int wv = (int)(threadIdx.x >> 6);             // (relay_duo_slot: D on wavefronts 0 1, P on 2 3, the loaders behind the consumers)
+        pw = wv < 2 ? 0 : (wv < 4 ? 1 : 2);
+    } else {
+        const int role = relay_role_of(threadIdx.x >> 6, NC);
+        pw = role < 2 ? role : 2;
+    }
     const int ostride = io.obs_stride;
     const int tile_floats = (c.tile_rows * ostride + 3) & ~3;
     const int wpw = c.wpw, lanes_used = wpw * N;
@@ -550,7 +590,7 @@ __device__ __forceinline__ void relay_coop_last(unsigned char *smem) {
 
 // ---- T: the top-up of the look-ahead rings (the role's comment in env_relay_kernel) ------------------------------------------------------
 template <int N>
-__device__ __forceinline__ void relay_topup() {
+__device__ __forceinline__ void relay_topup(const unsigned tile_index) {
     __builtin_amdgcn_s_setprio(CAVOID_RELAY_PRIO_T);
     unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kp));                            // (its own loads of the arguments, not the kernel's)
@@ -566,7 +606,7 @@ __device__ __forceinline__ void relay_topup() {
     const int lane0 = threadIdx.x & 63;
     const int wpw = c.wpw, lanes_used = wpw * N;
     const int lw = lane0 / N, i0 = lane0 - lw * N;
-    const int64_t w = (int64_t)blockIdx.x * wpw + lw;
+    const int64_t w = (int64_t)tile_index * wpw + lw;
     const bool active = lane0 < lanes_used && w < c.num_worlds;
     const int base0 = lane0 < lanes_used ? lw * N : 0;
     uint32_t ep = 0u, fh = 0u;
@@ -579,9 +619,35 @@ __device__ __forceinline__ void relay_topup() {
     ahead_fill_range<N, true>(c, ep, fh, active, w, i0, base0, lane0, hi, const_cast<PoolRec *>(ring), c.ahead, 0, 1, nullptr, nullptr);
 }
 
-template <int N>
-__global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopupMaxN ? 4 : 1) env_relay_kernel(const KCfg c_, const KState s_, const PoolRec *pool_, const KIO io_) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// TPW: tiles per workgroup.  1: one workgroup of 3 + NC (+ 1) wavefronts per tile, two of them per CU beyond 256 tiles.  2: one workgroup of
+// 2 * (3 + NC (+ 1)) wavefronts, up to 16, owns two tiles (relay_duo_slot): four wavefronts per SIMD, 128 vector registers each.
+template <int N, int TPW = 1>
+__global__ void __launch_bounds__(TPW == 2 ? 1024 : 64 * (4 + kRelayMaxConsumers), TPW == 2 ? 1 : (N <= kRelayTopupMaxN ? 4 : 1)) env_relay_kernel(const KCfg c_, const KState s_, const PoolRec *pool_, const KIO io_) {
+    static_assert(TPW == 1 || TPW == 2, "one or two tiles per workgroup");
+    static_assert(relay_lds_fixed_bytes<N>() % 16 == 0, "a tile's region begins on a 16-byte boundary (TPW = 2: the second one behind the first)");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_wg[];
+    // In front of the role branch: only what decides the role (block size, thread id, whether the launch carries the top-up) and what D
+    // zeroes.  Everything else -- the arguments a role uses and the tile geometry made from them -- each role loads and derives for itself
+    // (RELAY_ROLE_ARGS), so that no wavefront loads, keeps or spills what only another role reads.
+    const int NC = (blockDim.x >> (TPW == 2 ? 7 : 6)) - 3 - (io_.ahead_hi ? 1 : 0);   // (a launch with the top-up has one wavefront more per tile)
+    int role;                                               // 0 D, 1 P, 2 .. 1+NC consumers, 2+NC L, 3+NC T
+    unsigned tile_index;                                    // the tile this wavefront works for
+    unsigned char *smem = smem_wg;                          // ... and that tile's LDS region
+    if constexpr (TPW == 2) {
+        const int slot = relay_duo_slot(__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), NC);
+        role = slot & 15;
+        tile_index = 2u * blockIdx.x + (unsigned)(slot >> 4);
+        smem += relay_region_offset(slot >> 4, relay_lds_fixed_bytes<N>(), NC, (c_.tile_rows * io_.obs_stride + 3) & ~3);
+        // an odd number of tiles: the last workgroup's second tile does not exist.  Its wavefronts take part in the one barrier every role
+        // reaches and leave: they touch no memory and no counter (nobody of the other tile reads this region)
+        if ((int64_t)tile_index * c_.wpw >= c_.num_worlds) {
+            __syncthreads();
+            return;
+        }
+    } else {
+        role = relay_role_of(threadIdx.x >> 6, NC);
+        tile_index = blockIdx.x;
+    }
     unsigned char *sp = smem;
     double *lds_tab = reinterpret_cast<double *>(sp); sp += lds_floats_block() * sizeof(float);
     RelaySeq *seq = reinterpret_cast<RelaySeq *>(sp); sp += sizeof(RelaySeq);
@@ -593,11 +659,6 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
     RelayCoop<N> *coopb = reinterpret_cast<RelayCoop<N> *>(sp); sp += relay_coop_bytes<N>();   // (N < kRelayCoopFromN: nothing, never touched)
     float *tiles = reinterpret_cast<float *>(sp);
 
-    // In front of the role branch: only what decides the role (block size, thread id, whether the launch carries the top-up) and what D
-    // zeroes.  Everything else -- the arguments a role uses and the tile geometry made from them -- each role loads and derives for itself
-    // (RELAY_ROLE_ARGS), so that no wavefront loads, keeps or spills what only another role reads.
-    const int NC = (blockDim.x >> 6) - 3 - (io_.ahead_hi ? 1 : 0);   // (a launch with the top-up has one wavefront more)
-    const int role = relay_role_of(threadIdx.x >> 6, NC);   // 0 D, 1 P, 2 .. 1+NC consumers, 2+NC L, 3+NC T
     const int lane0 = threadIdx.x & 63;
     constexpr bool kCoop = N >= kRelayCoopFromN;            // the last step's observation: D, P and L together (below the roles)
     const bool coop_role = role < 2 || role == 2 + NC;      // (the consumers are still at their own steps when the last one is settled)
@@ -607,7 +668,7 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
         if (role == 0 && lane0 == 0) {                      // (behind the zeroes: the same wavefront's LDS writes, in order)
             const unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
             seq->kernarg[0] = (int)(uint32_t)kp; seq->kernarg[1] = (int)(uint32_t)(kp >> 32);
-            seq->tile_id = (int)blockIdx.x | (NC << 16);    // (at most 512 tiles: cavoid_launch_relay)
+            seq->tile_id = (int)tile_index | (NC << 16);       // (at most 512 tiles: cavoid_launch_relay)
         }
     }
 
@@ -974,7 +1035,7 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
         // ahead_hi then).  No LDS counters, no waits, no part in relay_coop_last.
         // Like relay_coop_last it derives what it needs from the kernel-argument segment on its own: none of it is live in scalar
         // registers across the other roles' loops (written against the kernel's parameters it added 44 scalar spills at N = 4).
-        relay_topup<N>();
+        relay_topup<N>(tile_index);
     } else {
         // ================================================ C: observation of every NC-th step ===================================
         __builtin_amdgcn_s_setprio(CAVOID_RELAY_PRIO_C);
@@ -1040,7 +1101,7 @@ __global__ void __launch_bounds__(64 * (4 + kRelayMaxConsumers), N <= kRelayTopu
     }
     // ================================================ D, P, L: the LAST step's observation, together =======================================
     if constexpr (kCoop) {
-        if (coop_role) relay_coop_last<N>(smem);
+        if (coop_role) relay_coop_last<N, TPW>(smem);
     }
 }
 static_assert(std::is_same<decltype(&env_relay_kernel<4>), void (*)(const KCfg, const KState, const PoolRec *, const KIO)>::value,

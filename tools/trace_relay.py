@@ -51,11 +51,22 @@ def main():
         print("rep %d: %d tiles stamped (step %d of %d)" % (rep, len(t), K // 2, K))
         for k in sorted(NAMES):
             d = t[:, k] - t[:, 0]
-            print("   %-26s median %6d  p10 %6d  p90 %6d" % (NAMES[k], np.median(d), np.percentile(d, 10), np.percentile(d, 90)))
+            d = d[(t[:, k] > 0) & (np.abs(d) < (1 << 20))]   # (a stamp the build does not make, or one that is not of this launch)
+            if len(d) == 0:
+                continue
+            print("   %-26s median %6d  p10 %6d  p90 %6d  (%d tiles)" % (NAMES[k], np.median(d), np.percentile(d, 10), np.percentile(d, 90), len(d)))
     if "--launch" in sys.argv:                             # launch-level marks: where a K-step launch's fixed cost goes
         marks = {20: "D kernel entry", 25: "L kernel entry", 26: "L first action batch in LDS", 21: "D prologue done (state, table, first actions)", 22: "D step 0 posted",
                  27: "L first pool records posted", 28: "C step 0's rows flushed", 23: "D last step settled", 29: "C last step's rows flushed", 30: "C0 stores completed",
                  24: "D write-back issued"}
+        # A tile whose row misses a mark (a zero) or holds one that is not of this launch puts a difference of the size of the clock itself
+        # into the upper percentiles and the maximum: a launch is 1e5 .. 4e5 cycles, so only the tiles whose marks all lie within 2^20 cycles of
+        # the tile's first kernel entry are reported, and the others are counted.
+        entry = np.minimum(t[:, 20], t[:, 25])
+        rel = t[:, sorted(marks)] - entry[:, None]
+        good = ((rel >= 0) & (rel < (1 << 20))).all(axis=1)
+        print("launch-level marks: %d of %d tiles with a complete set of marks of this launch (%d dropped)" % (good.sum(), len(t), len(t) - good.sum()))
+        t = t[good]
         t0 = np.minimum(t[:, 20], t[:, 25])                # (per tile: the shader clock is per XCD, tiles do not share a time base)
         print("launch-level marks, cycles after the tile's own first kernel entry: median / p10 / p90 / max")
         for k in marks:
