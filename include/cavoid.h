@@ -482,6 +482,27 @@ int cavoid_eval_run(cavoid_env *env, cavoid_policy *policy, cavoid_policy *froze
                     float *obs, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps,
                     int32_t greedy, void *stream);
 
+/* cavoid_eval_run for the WEIGHT-SHARING network (cavoid_policy_create_ws; cavoid_eval_run refuses such a handle): the same evaluation loop,
+ * up to n_steps steps in one launch that finished tiles leave early -- per tile of floor(64/N) worlds a workgroup runs the weight-sharing
+ * pass (cavoid_policy_forward's arithmetic on a weight-sharing handle: float32 MFMA) on the tile's rows that still need an action, takes
+ * the argmax (or the Philox draw), steps the tile's worlds without auto-reset and records the outcome.  Arguments, buffers, records, the
+ * definition of "over", the step counter, the ORCA / in-step box routing and CAVOID_ACTOR_QUAD exactly as cavoid_eval_run; in particular
+ * the same definition of the return: An agent's return sums the rewards up to and including the step at which its world is over.
+ * Trajectories are bit-identical to calling cavoid_policy_forward (+ cavoid_policy_forward_rows on `frozen` for the
+ * CAVOID_POLICY_FROZEN_NET rows) and cavoid_step per step.
+ *   policy: a loaded cavoid_policy_create_ws handle whose max_other (1..19) is the env's.
+ *   frozen (may be NULL): a loaded cavoid_policy_create_ws handle of the same max_other, input size and action count; it drives the
+ *   frozen-network agents by its argmax.  values[] of those rows then holds the frozen network's value (nothing reads it).
+ * CAVOID_EINVAL: cavoid_eval_run's cases -- null handles, buffers or record pointers, a wrong struct_size, n_steps < 0, handles that do not
+ * describe the same batch, a handle that is not loaded.  CAVOID_EUNSUPPORTED (evaluate step by step): an LSTM handle (cavoid_eval_run carries
+ * it), a cavoid_policy_create_ws_crowd handle (the ring form, 20..64 observed agents), an env of more than 16 agents per world, holonomic
+ * dynamics, a `frozen` handle that is not a matching whole-row weight-sharing handle, an env whose generator makes frozen-network agents
+ * when `frozen` is NULL (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0), and an env step whose LDS (with rvo_enabled: the ORCA
+ * lines) does not fit the 66 560 bytes of activation rows the pass lends it.  n_steps == 0: CAVOID_OK, nothing is launched or written. */
+int cavoid_eval_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_policy *frozen /* or NULL */, const cavoid_eval_buffers *buffers,
+                       float *obs, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps,
+                       int32_t greedy, void *stream);
+
 /* cavoid_step_autoreset + cavoid_rollout_push as ONE launch: the env step of every world and the Experience bookkeeping of its slots
  * (ProcessAgent.py:149-211) -- the fused actor's env phase for actors whose policy is a launch of its own (frozen-network agents,
  * a caller-supplied policy).  obs_cur [W,N,1+D]: the observation `actions` / `values` (V(s_t)) were computed on; the step writes the

@@ -65,7 +65,12 @@ extern "C" int cavoid_eval_run(cavoid_env *e, cavoid_policy *h, cavoid_policy *f
     const int rc_launch = frozen ? cavoid_launch_eval_frozen(e, sa, fz, io, s)
                                  : (rvo_form ? cavoid_launch_eval_rvo(e, sa, io, s) : launch_eval_any<false>(e, sa, sa, io, s));
     if (rc_launch != CAVOID_OK) return rc_launch;
-    hipLaunchKernelGGL(eval_finish_kernel, dim3(1), dim3(1), 0, s, h->step_counter, n_steps);
+    return cavoid_launch_eval_finish(h->step_counter, n_steps, s);
+}
+
+// eval_finish_kernel for the evaluation launches of other translation units too (cavoid_eval_ws.hip)
+int cavoid_launch_eval_finish(int32_t *policy_step, int32_t n_steps, hipStream_t s) {
+    hipLaunchKernelGGL(eval_finish_kernel, dim3(1), dim3(1), 0, s, policy_step, n_steps);
     HIP_TRY(hipGetLastError());
     return CAVOID_OK;
 }

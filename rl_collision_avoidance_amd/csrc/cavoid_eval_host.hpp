@@ -39,3 +39,5 @@ static int launch_eval_any(cavoid_env *e, const SplitArgs &sa, const SplitArgs &
 int cavoid_launch_eval_rvo(cavoid_env *e, const cavoid::SplitArgs &sa, const cavoid::EvalIO &io, hipStream_t s);
 // cavoid_eval_frozen.hip: eval_kernel<N, true, true> -- the 'everything' env step + a second, frozen network for the policy-4 agents
 int cavoid_launch_eval_frozen(cavoid_env *e, const cavoid::SplitArgs &sa, const cavoid::SplitArgs &fz, const cavoid::EvalIO &io, hipStream_t s);
+// cavoid_eval.hip: eval_finish_kernel behind an evaluation launch, for both entry points (cavoid_eval_run, cavoid_eval_run_ws)
+int cavoid_launch_eval_finish(int32_t *policy_step, int32_t n_steps, hipStream_t s);

@@ -5,7 +5,8 @@ report: reached the goal / collided / ran out of time, and the extra time to goa
 
 Two paths produce the same numbers: the step-by-step loop (policy launch, ``env.step`` and a look at the world buffer per env
 step, one host synchronisation each) and, with ``fused=True``, ``cavoid_eval_run`` -- the whole loop per tile of worlds inside
-one launch of ``steps_per_launch`` steps that finished tiles leave early, the outcome recorded on the device."""
+one launch of ``steps_per_launch`` steps that finished tiles leave early, the outcome recorded on the device (``fused_ws=True``:
+``cavoid_eval_run_ws``, the same for the ``weight_sharing`` network)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -123,6 +124,42 @@ def evaluate_fused_unavailable_reason(env, policy, frozen_policy=None) -> Option
     return None
 
 
+def evaluate_fused_ws_unavailable_reason(env, policy, frozen_policy=None) -> Optional[str]:
+    """Why ``evaluate(fused_ws=True)`` (``cavoid_eval_run_ws``: the evaluation loop of the weight_sharing network inside one launch) does
+    not apply to this env and policy -- None when it does.  Host values only (no launch, no GPU), the refusals of the C entry point one
+    for one: a ``FusedPolicy`` of the ``weight_sharing`` network on the whole-row kernels (up to ``MAX_OTHERS_WS`` observed neighbours, not
+    the ring handle of ``ws_crowd=True``) whose neighbour count is the env's, tile worlds (up to 16 agents), table actions, a frozen
+    policy of the same kind for the frozen-network agents, and an env step whose LDS fits the rows the pass lends it."""
+    from .policy_kernel import MAX_OTHERS_WS
+    from .rollout import WS_ACTOR_LENT_BYTES, env_step_lds_bytes
+    n = int(env.max_agents)
+    if not hasattr(policy, "act") or not hasattr(policy, "inference_form") or getattr(policy, "_h", None) is None:
+        return "the policy is not a FusedPolicy (a plain callable is evaluated step by step)"
+    if not getattr(policy, "ws", False):
+        return "the policy is the %s network (use fused=True: cavoid_eval_run embeds the LSTM pass)" % (getattr(policy, "arch", "rnn"),)
+    if getattr(policy, "crowd", False) or int(policy.max_others) > MAX_OTHERS_WS:
+        return ("the policy observes %d neighbours on the ring kernels (the weight_sharing evaluation kernel parks the whole row: up to %d; "
+                "the ring form is evaluated step by step)" % (int(policy.max_others), MAX_OTHERS_WS))
+    if int(policy.max_others) != int(env.max_other):
+        return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy.max_others), int(env.max_other))
+    if n > _lib.TILE_MAX_AGENTS:
+        return "%d agents per world: crowd worlds (more than %d) are evaluated step by step" % (n, _lib.TILE_MAX_AGENTS)
+    if int(env.cfg.dynamics) == 2:
+        return "holonomic (velocity) actions"
+    if frozen_policy is not None:
+        fz = frozen_policy
+        same_kind = getattr(fz, "_h", None) is not None and getattr(fz, "ws", False) and not getattr(fz, "crowd", False)
+        if not same_kind or int(fz.max_others) != int(policy.max_others) or int(getattr(fz, "num_actions", 0)) != int(getattr(policy, "num_actions", 0)):
+            return ("the frozen policy is not a weight_sharing FusedPolicy of the policy's shape (%s, %d neighbours; the policy: %d)"
+                    % (getattr(fz, "arch", "no FusedPolicy"), int(getattr(fz, "max_others", -1)), int(policy.max_others)))
+    elif float(env.cfg.gen_frozen_fraction) > 0.0 and float(env.cfg.gen_nonlearning_fraction) > 0.0:
+        return "frozen-network agents without a frozen_policy (they act by their own network)"
+    need = env_step_lds_bytes(n, 6 + 7 * int(env.max_other), bool(env.cfg.rvo_enabled))
+    if need > WS_ACTOR_LENT_BYTES:
+        return "the env step's LDS (%d bytes) does not fit the %d bytes the weight_sharing pass lends it" % (need, WS_ACTOR_LENT_BYTES)
+    return None
+
+
 class _EvalRecords(object):
     """The device-side records of ``cavoid_eval_run`` for one env, and the per-step outputs it writes (``cavoid_eval_buffers``)."""
 
@@ -152,6 +189,31 @@ def eval_run(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _Eva
                                           int(n_steps), 1 if greedy else 0, env._stream()), "cavoid_eval_run")
 
 
+def eval_run_ws(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
+    """One ``cavoid_eval_run_ws`` launch (the weight_sharing network's evaluation kernel): ``eval_run``'s arguments and buffers."""
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(_lib.lib().cavoid_eval_run_ws(env._h, policy._h, frozen_policy._h if frozen_policy is not None else None, C.byref(rec.c),
+                                             ptr(env.obs), ptr(env.rewards), ptr(env.done), ptr(env.game_over), ptr(rec.actions), ptr(rec.values),
+                                             int(n_steps), 1 if greedy else 0, env._stream()), "cavoid_eval_run_ws")
+
+
+def _fused_round(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, launch: Callable, steps_per_launch: int, limit: int,
+                 greedy: bool) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One round (the env has just been reset) as launches of ``launch`` (``eval_run`` or ``eval_run_ws``): the round's step count, the
+    flags it ends with, the returns and the goal steps."""
+    rec.zero()
+    steps = 0
+    while steps < limit:                                   # the last launch is cut so that no world takes more than `limit` steps
+        n = min(steps_per_launch, limit - steps)
+        launch(env, policy, frozen_policy, rec, n, greedy)
+        steps += n
+        if int(rec.worlds_running.item()) == 0:            # ONE 4-byte read per launch
+            break
+    step = int(rec.world_steps.max())                      # = the step-by-step loop's count: the slowest world's
+    fl = _settle_finished(env, rec.world_steps, step)
+    return step, fl, rec.ret.clone(), rec.goal_step.clone()
+
+
 def _settle_finished(env: BatchedCollisionAvoidanceEnv, world_steps: torch.Tensor, env_steps: int) -> torch.Tensor:
     """The world buffer the step-by-step loop would have left, and its flags.  That loop goes on stepping worlds that are over until the
     slowest one is, and the first such step leaves a trace in a finished world (``cavoid_step`` latches CAVOID_F_WAS_AT_GOAL /
@@ -175,7 +237,7 @@ def _settle_finished(env: BatchedCollisionAvoidanceEnv, world_steps: torch.Tenso
 @torch.no_grad()
 def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 1, greedy: bool = True,
              max_steps: Optional[int] = None, frozen_policy=None, fused: bool = False, steps_per_launch: int = 16,
-             details: bool = False) -> Dict[str, float]:
+             details: bool = False, fused_ws: bool = False) -> Dict[str, float]:
     """Run ``rounds`` batches of ``env.num_worlds`` episodes.  ``policy``: a ``FusedPolicy`` (its ``act`` is used) or any
     callable ``x [B, NN_INPUT_SIZE] -> (p [B, A], v [B])``.  Returns rates over the learning agents that took part.
 
@@ -184,15 +246,20 @@ def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 
     one difference in ``mean_reward`` / ``per_agent["ret"]``: the kernel's return stops at the step at which the agent's world is
     over, the loop's goes on summing what ``cavoid_step`` pays finished worlds until the slowest world ends (``reward_time_step``
     where one is set; at the default rewards the getting-close penalty of an agent that ran out of time beside another).
+    ``fused_ws=True`` is the same for a ``FusedPolicy`` of the ``weight_sharing`` network: ``cavoid_eval_run_ws``, the same launch loop
+    and the same numbers (raises with ``evaluate_fused_ws_unavailable_reason``).  The two exclude each other; both are opt-in.
     ``details=True`` adds ``extra_time_p75`` / ``_p90`` and ``per_agent`` (``reduce_outcomes``)."""
-    rec = None
-    if fused:
-        why = evaluate_fused_unavailable_reason(env, policy, frozen_policy)
+    rec, launch = None, None
+    if fused and fused_ws:
+        raise ValueError("evaluate: fused=True (cavoid_eval_run, the rnn network) and fused_ws=True (cavoid_eval_run_ws, weight_sharing) exclude each other")
+    if fused or fused_ws:
+        why = (evaluate_fused_ws_unavailable_reason if fused_ws else evaluate_fused_unavailable_reason)(env, policy, frozen_policy)
         if why is not None:
-            raise ValueError("evaluate(fused=True) does not apply: " + why)
+            raise ValueError("evaluate(%s=True) does not apply: " % ("fused_ws" if fused_ws else "fused") + why)
         if int(steps_per_launch) < 1:
             raise ValueError("steps_per_launch must be >= 1")
         rec = _EvalRecords(env)
+        launch = eval_run_ws if fused_ws else eval_run
     W, N = env.num_worlds, env.max_agents
     dt = float(env.cfg.dt)
     limit = max_steps if max_steps is not None else 100000
@@ -200,18 +267,8 @@ def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 
     for _ in range(rounds):
         obs = env.reset()
         state0 = env.get_state()
-        if fused:
-            rec.zero()
-            steps = 0
-            while steps < limit:                           # the last launch is cut so that no world takes more than `limit` steps
-                n = min(int(steps_per_launch), limit - steps)
-                eval_run(env, policy, frozen_policy, rec, n, greedy)
-                steps += n
-                if int(rec.worlds_running.item()) == 0:    # ONE 4-byte read per launch
-                    break
-            step = int(rec.world_steps.max())              # = the step-by-step loop's count: the slowest world's
-            fl = _settle_finished(env, rec.world_steps, step)
-            ret, goal_step = rec.ret.clone(), rec.goal_step.clone()
+        if launch is not None:
+            step, fl, ret, goal_step = _fused_round(env, policy, frozen_policy, rec, launch, int(steps_per_launch), limit, greedy)
         else:
             goal_step = torch.zeros(W * N, dtype=torch.int32, device=env.device)
             ret = torch.zeros(W * N, dtype=torch.float64, device=env.device)

@@ -114,6 +114,12 @@ def main(argv=None) -> None:
                          "one policy launch, one env launch and one host synchronisation per env step; same numbers.  The run ends if the "
                          "configuration is one the kernel does not carry (crowd worlds, the weight_sharing network, more than 19 observed "
                          "neighbours, the PyTorch policy).  Opt-in (profiles/eval_fused_timing.txt: tools/evalbench.py)")
+    ap.add_argument("--fused-ws-evaluate", action="store_true",
+                    help="with --evaluate and --arch weight_sharing: the same for the weight_sharing network (up to 16 agents per world and 19 "
+                         "observed neighbours) -- launches of --steps-per-graph env steps of cavoid_eval_run_ws (the weight_sharing pass, argmax, "
+                         "env.step without auto-reset and the outcome record per tile of worlds); same numbers.  The run ends if the "
+                         "configuration is one the kernel does not carry (the rnn network, the ring form above 19 neighbours, crowd worlds, "
+                         "the PyTorch policy).  Opt-in (profiles/eval_ws_fused_timing.txt: tools/evalbench.py --arch weight_sharing)")
     ap.add_argument("--pretrain-steps", type=int, default=0,
                     help="supervised initialisation before RL (the role of Regression.py): Adam steps on teacher-driven rollouts")
     ap.add_argument("--fused-regression", action="store_true",
@@ -315,6 +321,17 @@ def main(argv=None) -> None:
             if rank == 0:
                 print("[Evaluate] fused evaluation kernel (cavoid_eval_run), %d env steps per launch" % args.steps_per_graph, flush=True)
             res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused=True, steps_per_launch=args.steps_per_graph)
+        elif args.fused_ws_evaluate:
+            from .evaluate import evaluate_fused_ws_unavailable_reason
+            why = evaluate_fused_ws_unavailable_reason(env, eval_policy, frozen)
+            if why is not None:
+                raise SystemExit("--fused-ws-evaluate: the fused weight_sharing evaluation kernel (cavoid_eval_run_ws) does not apply: " + why)
+            if args.steps_per_graph < 1:
+                raise SystemExit("--steps-per-graph must be >= 1")
+            if rank == 0:
+                print("[Evaluate] fused weight_sharing evaluation kernel (cavoid_eval_run_ws), %d env steps per launch" % args.steps_per_graph,
+                      flush=True)
+            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused_ws=True, steps_per_launch=args.steps_per_graph)
         else:
             res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen)
         if rank == 0:
