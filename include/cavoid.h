@@ -342,8 +342,10 @@ int cavoid_policy_rows(cavoid_env *env, int32_t policy_id, int32_t only_running,
  *   actions int32 [W,N], values float [W,N] (V(s_t)), rewards/done/game_over = what the step returned.
  *   dup_* : append buffer for the rows only the reference's post-done re-flush quirk produces
  *   (reflush_done = 1: a done agent that is still reported learning re-emits its kept experience with
- *   every later step); dup_count int32 [2] = (appended, dropped), reset by the caller.
- *   ep_out float [ep_capacity,3] (world, total_reward, total_length), ep_count int32 [2].
+ *   every later step); dup_count int32 [2] = (rows OFFERED: stored plus dropped, rows dropped for lack
+ *   of capacity), reset by the caller.  The rows stored are the first min(dup_count[0], dup_capacity) of dup_*: read no further.
+ *   ep_out float [ep_capacity,3] (world, total_reward, total_length), ep_count int32 [2] = (records offered, records dropped) in
+ *   the same sense: min(ep_count[0], ep_capacity) records are stored.  Nothing is written behind either capacity.
  *   step < 0: use (and advance) the handle's device-side step counter (hipGraph replays). */
 int cavoid_rollout_create(int64_t num_worlds, int32_t max_agents, int32_t obs_width, int32_t time_max, double discount,
                           int32_t reflush_done, int32_t ring_len, int device, cavoid_rollout **out);
@@ -518,8 +520,9 @@ int cavoid_step_push(cavoid_env *env, cavoid_rollout *rollout, const cavoid_roll
 /* hand-over to the trainer (`training_q.put((x_, r_, a_))`, ProcessAgent.py:238): append the training rows (emit_t >= 0) of
  * the step blocks [step_lo, step_hi) to one batch -- out_x float [capacity, D], out_r float [capacity] (n-step returns),
  * out_a int32 [capacity], out_src int32 [capacity, 4] (world, agent, recorded-at, emitted-at; may be NULL),
- * out_count int32 [2] = (rows appended, rows dropped for lack of capacity), zeroed by the call.  Row order is unspecified.
- * mark_taken != 0 stamps the rows emit_t = -2 (they are not handed out again).  Rows of every width the env makes are carried
+ * out_count int32 [2] = (rows OFFERED: stored plus dropped, rows dropped for lack of capacity), zeroed by the call: the batch holds
+ * min(out_count[0], capacity) rows and nothing is written behind `capacity` (0 is allowed).  Row order is unspecified.
+ * mark_taken != 0 stamps the STORED rows emit_t = -2 (they are not handed out again; a dropped row stays for a later call).  Rows of every width the env makes are carried
  * (D up to 453 = 5 + 7 * 64); CAVOID_EUNSUPPORTED only from D = 4096 up, where the copy loop's multiply-shift e / D is no longer exact. */
 int cavoid_rollout_compact(cavoid_rollout *r, int32_t step_lo, int32_t step_hi, int32_t mark_taken, const float *x, const float *ret,
                            const uint8_t *act, int32_t *emit_t, float *out_x, float *out_r, int32_t *out_a, int32_t *out_src,

@@ -67,9 +67,9 @@ struct RolloutIO {
     float *dup_r;            // [dup_capacity]
     int32_t *dup_a;          // [dup_capacity]
     int32_t *dup_src;        // [dup_capacity][4]  world, agent, recorded-at step, emitted-at step
-    int32_t *dup_count;      // [2]  rows appended, rows dropped for lack of capacity
+    int32_t *dup_count;      // [2]  rows offered (stored + dropped), rows dropped for lack of capacity
     float *ep_out;           // [ep_capacity][3]  world, total_reward, total_length
-    int32_t *ep_count;       // [2]  records appended, dropped
+    int32_t *ep_count;       // [2]  records offered (stored + dropped), dropped
 };
 
 constexpr int kMaxRing = 32;   // T_max + 1 <= 32: the backward pass runs in registers (else a serial fallback)
@@ -338,7 +338,7 @@ struct CompactArgs {
     float *out_r;            // [capacity]
     int32_t *out_a;          // [capacity]
     int32_t *out_src;        // [capacity][4] (world, agent, recorded-at step, emitted-at step) or nullptr
-    int32_t *out_count;      // [2] rows appended, rows dropped for lack of capacity
+    int32_t *out_count;      // [2] rows offered (stored + dropped), rows dropped for lack of capacity
     int64_t capacity;
 };
 

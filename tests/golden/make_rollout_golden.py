@@ -6,6 +6,7 @@ values it returned are stored.  Needs /root/reference; not runnable on the GPU b
 
     python tests/golden/make_rollout_golden.py            # rollout_golden.npz
     python tests/golden/make_rollout_golden.py --seed7    # rollout_seed7_golden.npz
+    python tests/golden/make_rollout_golden.py --limits   # rollout_limits_golden.npz
 
 Stubs: the env package the reference imports (absent submodule) resolves to this repo's compat
 shim; NumPy 2 dropped ``np.product`` (used at Config.py:69), aliased here; ``Environment`` is
@@ -190,8 +191,54 @@ def main_seed7():
     print("wrote", out, os.path.getsize(out), "bytes")
 
 
+# (TIME_MAX, DISCOUNT) the limits fixture records; test_rollout_oracle.test_limits_against_live_reference adds (254, 0.97) live
+LIMIT_CASES = ((1, 0.97), (2, 0.97), (31, 0.97), (32, 0.97), (33, 1.0), (40, 0.97))
+LIMIT_EPISODES = 5
+
+
+def limit_scripts(time_max, n_episodes=LIMIT_EPISODES):
+    """The scripted episodes of one limits case: a pure function of ``time_max`` (rng 1000 + time_max), TrainPhase1 shapes."""
+    rng = np.random.default_rng(1000 + time_max)
+    out = []
+    for _ in range(n_episodes):
+        n_present = int(rng.integers(1, 5))
+        out.append(make_script(rng, 4, 26, n_present, 2 * time_max + 12, time_max))
+    return out
+
+
+def run_limit_case(time_max, discount, n_episodes=LIMIT_EPISODES):
+    """``n_episodes`` scripted episodes through the reference's run_episode with Config.TIME_MAX / Config.DISCOUNT set before the
+    agent is built (ProcessAgent reads both at run time).  Returns [(script, yields)]."""
+    Config, PA, EX = load_reference("TrainPhase1")
+    assert (Config.MAX_NUM_AGENTS_IN_ENVIRONMENT, Config.NN_INPUT_SIZE) == (4, 26)
+    Config.TIME_MAX, Config.DISCOUNT = int(time_max), float(discount)
+    return [(script, run_reference_episode(Config, PA, script)) for script in limit_scripts(time_max, n_episodes)]
+
+
+def main_limits():
+    """tests/golden/rollout_limits_golden.npz: the reference's yields off its default TIME_MAX -- the smallest buffers (1, 2), the
+    last register form of the device's backward pass (31), the first serial ones (32, 33; 33 undiscounted) and the TIME_MAX a run at
+    DT = 0.1 trains on (40).  Stored per case like the episodes of rollout_golden.npz."""
+    store = {"cases": np.array(LIMIT_CASES, dtype=np.float64), "num_episodes": LIMIT_EPISODES}
+    for c, (time_max, discount) in enumerate(LIMIT_CASES):
+        for e, (script, yields) in enumerate(run_limit_case(time_max, discount)):
+            pre = "c%d_ep_%d_" % (c, e)
+            for key in ("obs", "rewards", "done", "learning", "n", "actions", "values"):
+                store[pre + key] = np.asarray(script[key])
+            store[pre + "rows"] = np.array([len(y[1]) for y in yields], dtype=np.int64)
+            store[pre + "x"] = np.concatenate([y[0].reshape(-1, 26) for y in yields])
+            store[pre + "r"] = np.concatenate([y[1] for y in yields])
+            store[pre + "a"] = np.concatenate([y[2] for y in yields])
+            store[pre + "score"] = np.array([y[3] for y in yields])
+    out = os.path.join(ROOT, "tests", "golden", "rollout_limits_golden.npz")
+    np.savez_compressed(out, **store)
+    print("wrote", out, os.path.getsize(out), "bytes")
+
+
 if __name__ == "__main__":
-    if "--seed7" in sys.argv:
+    if "--limits" in sys.argv:
+        main_limits()
+    elif "--seed7" in sys.argv:
         main_seed7()
     else:
         main()

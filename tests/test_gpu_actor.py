@@ -12,10 +12,12 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import rollout_scripts as rs
+
 pytestmark = pytest.mark.gpu
 
 
-def _make(W, N, seed, reflush, greedy=False, skip_finished=None, M=None, **over):
+def _make(W, N, seed, reflush, greedy=False, skip_finished=None, M=None, time_max=5, **over):
     from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
     from rl_collision_avoidance_amd.config import EnvConfig
     from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
@@ -44,7 +46,7 @@ def _make(W, N, seed, reflush, greedy=False, skip_finished=None, M=None, **over)
         skip_finished = (not reflush) and not (over.get("gen_frozen_fraction", 0.0) > 0.0)
     # short chunks: many flushes; room for every duplicate row of the re-flush quirk (a full buffer drops rows in arrival order,
     # which legitimately differs between the two forms)
-    roll = BatchedRollout(env, pol, reflush_done=reflush, greedy=greedy, time_max=5, dup_capacity=600000 if reflush else None,
+    roll = BatchedRollout(env, pol, reflush_done=reflush, greedy=greedy, time_max=time_max, dup_capacity=600000 if reflush else None,
                           skip_finished=skip_finished, frozen_policy=frozen)
     roll.reset()
     return env, net, pol, roll
@@ -84,6 +86,10 @@ def _same(a, b, what):
     # unicycle_max_turn_rate, with turns the clamp cuts (the default table's widest, pi/6, is below max_turn_rate * dt)
     (4, 500, False, False, dict(dynamics=1, gen_min_agents=2, actions=[[1.0, 0.3], [1.0, -0.3], [1.0, 0.0], [1.0, 0.9], [1.0, -0.9], [0.5, 1.2],
                                                                       [0.5, -1.2], [0.0, 0.7], [0.0, -0.7], [1.0, 1.5], [1.0, -1.5]])),
+    # the backward pass past its 32 registers (time_max + 1 > 32: the serial form) and with all 32 live (time_max = 31), 8 tiles
+    (4, 128, False, False, dict(time_max=33)),
+    (4, 128, True, False, dict(time_max=33, gen_min_agents=2, gen_nonlearning_fraction=0.3)),
+    (4, 128, False, False, dict(time_max=31)),
 ])
 def test_fused_actor_equals_step_by_step(N, W, reflush, greedy, over):
     seed = 21
@@ -115,6 +121,8 @@ def test_fused_actor_equals_step_by_step(N, W, reflush, greedy, over):
     # what reaches the trainer and the stats process
     ba, bb = a.drain(flush_all=True), b.drain(flush_all=True)
     assert len(ba) == len(bb) > 0 and ba.dropped == bb.dropped == 0
+    if over.get("time_max", 5) > 5:
+        rs.require_deep_flushes(bb.src.cpu().numpy(), over["time_max"], "fused actor N=%d W=%d reflush=%s" % (N, W, reflush))
     ka = np.lexsort(ba.src.cpu().numpy().T[::-1])
     kb = np.lexsort(bb.src.cpu().numpy().T[::-1])
     assert np.array_equal(ba.src.cpu().numpy()[ka], bb.src.cpu().numpy()[kb])
@@ -246,6 +254,9 @@ def test_pipelined_hand_over_equals_drain():
     (10, 300, False, dict(gen_min_agents=2, gen_nonlearning_fraction=0.2)),
     (4, 500, False, dict(rvo_enabled=1, gen_rvo_fraction=0.5, gen_nonlearning_fraction=0.5, gen_mode=1, gen_pool_size=0)),
     (1, 200, False, dict()),
+    (4, 300, True, dict(time_max=33, gen_min_agents=2, gen_nonlearning_fraction=0.3)),      # the serial backward pass
+    (4, 300, False, dict(time_max=33)),
+    (4, 300, False, dict(time_max=31)),                                                      # all 32 registers live
 ])
 def test_step_push_equals_step_then_push(N, W, reflush, over):
     """`cavoid_step_push` (env.step + Experience bookkeeping in ONE launch, BatchedRollout.step's default) against the three launches
@@ -259,13 +270,15 @@ def test_step_push_equals_step_then_push(N, W, reflush, over):
         def __init__(self):
             self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
             EnvConfig.__init__(self)
+    over = dict(over)
+    time_max = over.pop("time_max", 5)
     rolls = []
     for fuse in (True, False):
         if N > 1:
-            env, _, _, roll = _make(W, N, 17, reflush, False, **over)
+            env, _, _, roll = _make(W, N, 17, reflush, False, time_max=time_max, **over)
         else:
             env = BatchedCollisionAvoidanceEnv(W, Cfg(), device="cuda:0", seed=17, **over)
-            roll = BatchedRollout(env, None, reflush_done=reflush, time_max=5)
+            roll = BatchedRollout(env, None, reflush_done=reflush, time_max=time_max)
             roll.reset()
         roll.fuse_env_push = fuse
         rolls.append((env, roll))
@@ -288,6 +301,8 @@ def test_step_push_equals_step_then_push(N, W, reflush, over):
                 _same(getattr(a, name), getattr(b, name), (name, t))
     ba, bb = a.drain(flush_all=True), b.drain(flush_all=True)
     assert len(ba) == len(bb) > 0 and ba.dropped == bb.dropped == 0
+    if time_max > 5:
+        rs.require_deep_flushes(bb.src.cpu().numpy(), time_max, "step_push N=%d W=%d reflush=%s" % (N, W, reflush))
     ka, kb = np.lexsort(ba.src.cpu().numpy().T[::-1]), np.lexsort(bb.src.cpu().numpy().T[::-1])
     for name in ("src", "x", "r", "a_index"):
         assert np.array_equal(getattr(ba, name).cpu().numpy()[ka], getattr(bb, name).cpu().numpy()[kb]), name

@@ -17,6 +17,8 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import rollout_scripts as rs
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +26,7 @@ KS = (2, 1, 7, 16, 4) + (16,) * 14 + (3,)                    # odd counts too: t
 OK, EINVAL, EUNSUPPORTED = 0, -1, -4
 
 
-def _make(W, N, M, seed, reflush=False, greedy=False, arch="weight_sharing", net_M=None, ws_crowd=False, **over):
+def _make(W, N, M, seed, reflush=False, greedy=False, arch="weight_sharing", net_M=None, ws_crowd=False, time_max=5, **over):
     from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
     from rl_collision_avoidance_amd.config import EnvConfig
     from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
@@ -44,7 +46,7 @@ def _make(W, N, M, seed, reflush=False, greedy=False, arch="weight_sharing", net
     # skip_finished = not reflush: the fused kernel hands a result only to the rows that still need an action (with the re-flush quirk: to
     # every row), exactly the rows the step-by-step path lists with skip_finished -- like is compared with like.  Short chunks: many
     # flushes; room for every duplicate row of the re-flush quirk (a full buffer drops rows in arrival order, which legitimately differs).
-    roll = BatchedRollout(env, pol, reflush_done=reflush, greedy=greedy, time_max=5, dup_capacity=600000 if reflush else None,
+    roll = BatchedRollout(env, pol, reflush_done=reflush, greedy=greedy, time_max=time_max, dup_capacity=600000 if reflush else None,
                           skip_finished=not reflush)
     roll.reset()
     return env, net, pol, roll
@@ -90,6 +92,10 @@ def _close(*pairs):
     (4, 500, 7, dict(sort_method=1, gen_min_agents=3)),
     # 512 tiles: two workgroups per CU, one tile's env step under another's matrix phase
     (4, 8192, 7, dict()),
+    # WS-8 at 4 agents with the backward pass past its 32 registers (the serial form), and with all 32 live
+    (4, 130, 7, dict(time_max=33)),
+    (4, 130, 7, dict(time_max=33, reflush=True, gen_min_agents=2, gen_nonlearning_fraction=0.3)),
+    (4, 130, 7, dict(time_max=31)),
 ])
 def test_fused_ws_actor_equals_step_by_step(N, W, M, over):
     over = dict(over)
@@ -116,6 +122,8 @@ def test_fused_ws_actor_equals_step_by_step(N, W, M, over):
     # what reaches the trainer and the stats process
     ba, bb = a.drain(flush_all=True), b.drain(flush_all=True)
     assert len(ba) == len(bb) > 0 and ba.dropped == bb.dropped == 0
+    if over.get("time_max", 5) > 5:
+        rs.require_deep_flushes(bb.src.cpu().numpy(), over["time_max"], "ws actor N=%d W=%d reflush=%s" % (N, W, reflush))
     ka = np.lexsort(ba.src.cpu().numpy().T[::-1])
     kb = np.lexsort(bb.src.cpu().numpy().T[::-1])
     for name in ("src", "x", "r", "a_index"):

@@ -19,6 +19,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import rollout_scripts as rs
 from tests.test_gpu_parity import _env
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +30,7 @@ FAST = dict(max_time_ratio=0.1)
 ORCA = dict(rvo_enabled=2, gen_rvo_fraction=0.5, gen_nonlearning_fraction=0.5)
 
 
-def _make(W, N, M, seed, reflush, greedy=False, net_M=None, arch="rnn", frozen=False, **over):
+def _make(W, N, M, seed, reflush, greedy=False, net_M=None, arch="rnn", frozen=False, time_max=5, **over):
     from rl_collision_avoidance_amd.config import EnvConfig
     from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
     from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
@@ -54,7 +55,7 @@ def _make(W, N, M, seed, reflush, greedy=False, net_M=None, arch="rnn", frozen=F
     # skip_finished = not reflush: the fused kernel hands a result only to the rows that still need an action (with the re-flush quirk: to
     # every row), exactly the rows the step-by-step path lists with skip_finished -- like is compared with like.  Room for every duplicate
     # row of the re-flush quirk (at most one per slot and step): a full buffer drops rows in arrival order, which legitimately differs.
-    roll = BatchedRollout(env, pol, reflush_done=reflush, greedy=greedy, time_max=5, dup_capacity=W * N * 160 if reflush else None,
+    roll = BatchedRollout(env, pol, reflush_done=reflush, greedy=greedy, time_max=time_max, dup_capacity=W * N * 160 if reflush else None,
                           skip_finished=not reflush, frozen_policy=fz)
     roll.reset()
     return env, net, pol, roll
@@ -89,6 +90,10 @@ def _compare(env_a, a, env_b, b, total):
     (20, 30, 19, False, False, dict(**ORCA, **FAST)),                          # ORCA agents (crowd_actor_kernel<32, true>)
     (40, 12, 39, False, False, dict(**ORCA, **FAST)),                          # ... <64, true>
     (33, 520, 32, False, False, dict(**FAST)),                                 # 520 workgroups: two per CU on every CU
+    # the backward pass past its 32 registers (the serial form) and with all 32 live; the default time ratio: episodes outlast a chunk
+    (20, 32, 19, False, False, dict(time_max=33, gen_min_agents=2, gen_nonlearning_fraction=0.3)),
+    (20, 32, 19, True, False, dict(time_max=33, gen_min_agents=2, gen_nonlearning_fraction=0.3)),
+    (20, 32, 19, False, False, dict(time_max=31, gen_min_agents=2, gen_nonlearning_fraction=0.3)),
 ])
 def test_fused_crowd_actor_equals_step_by_step(N, W, M, reflush, greedy, over):
     seed = 21
@@ -118,6 +123,8 @@ def test_fused_crowd_actor_equals_step_by_step(N, W, M, reflush, greedy, over):
     assert env_b.episode.max().item() >= 1
     assert len(bb) > 0 and len(eb) > 0
     assert dup_b[1] == 0 and (dup_b[0] > 0 if reflush else dup_b[0] == 0)
+    if over.get("time_max", 5) > 5:
+        rs.require_deep_flushes(bb.src.cpu().numpy(), over["time_max"], "crowd actor N=%d W=%d reflush=%s" % (N, W, reflush))
     # what reaches the trainer and the stats process
     assert len(ba) == len(bb) and ba.dropped == bb.dropped == 0
     ka = np.lexsort(ba.src.cpu().numpy().T[::-1])

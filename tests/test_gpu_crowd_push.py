@@ -12,6 +12,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from oracle import rollout_oracle as ro
+from tests import rollout_scripts as rs
 from tests.test_gpu_parity import _env
 
 pytestmark = pytest.mark.gpu
@@ -53,16 +54,22 @@ def _rollout(env, reflush, steps, fuse, **kw):
     (32, 40, 31, True, dict(gen_pool_size=200), 280, 10),
     (33, 20, 19, False, dict(gen_min_agents=2), 150, 0),
     (64, 12, 63, True, dict(gen_min_agents=2, gen_nonlearning_fraction=0.2), 200, 6),
+    # the backward pass past its 32 registers (time_max + 1 > 32: the serial form) and with all 32 live, on a ring of 2 time_max + 12 blocks
+    (20, 24, 19, True, dict(time_max=33, gen_min_agents=2, gen_nonlearning_fraction=0.3), 150, 0),
+    (20, 24, 19, False, dict(time_max=33, gen_min_agents=2), 150, 0),
+    (20, 24, 19, False, dict(time_max=31, gen_min_agents=2), 150, 0),
 ])
 def test_crowd_step_push_equals_step_then_push(N, W, M, reflush, over, steps, straight):
     """One launch against the three it replaces, bitwise, with scripted actions / values from one generator; time_max = 5 and a ring
-    of 12 blocks that wraps a dozen times and more.  Actions are biased to 'full speed straight ahead' so that agents reach goals
+    of 12 blocks that wraps a dozen times and more (the time_max = 33 / 31 cases: a ring of 2 time_max + 12 blocks that wraps once).  Actions are biased to 'full speed straight ahead' so that agents reach goals
     and worlds finish (tests/test_gpu_parity.py's _goal_seeking_actions)."""
-    STEPS, RING = steps, 12
+    over = dict(over)
+    time_max = over.pop("time_max", 5)
+    STEPS, RING = steps, 12 if time_max == 5 else 2 * time_max + 12
     rolls = []
     for fuse in (True, False):
         env = _env(W, N, M, seed=17, **over)
-        rolls.append((env, _rollout(env, reflush, STEPS, fuse, time_max=5, ring_len=RING)))
+        rolls.append((env, _rollout(env, reflush, STEPS, fuse, time_max=time_max, ring_len=RING)))
     (ea, a), (eb, b) = rolls
     assert a.step_path == ONE and b.step_path == THREE
     g = torch.Generator(device="cuda").manual_seed(3)
@@ -92,6 +99,8 @@ def test_crowd_step_push_equals_step_then_push(N, W, M, reflush, over, steps, st
     # the three-launch side (the code of before) did what the case is about: nothing below passes on nothing
     assert emitted_b > 0 and len(bb) > 0 and len(epb) > 0
     assert dup_b[1] == 0 and (dup_b[0] > 0 if reflush else dup_b[0] == 0)
+    if time_max > 5:
+        rs.require_deep_flushes(bb.src.cpu().numpy(), time_max, "crowd step_push N=%d W=%d reflush=%s" % (N, W, reflush))
     assert len(ba) == len(bb) and ba.dropped == bb.dropped == 0
     ka, kb = np.lexsort(ba.src.cpu().numpy().T[::-1]), np.lexsort(bb.src.cpu().numpy().T[::-1])
     for name in ("src", "x", "r", "a_index"):
@@ -104,12 +113,13 @@ def test_crowd_step_push_equals_step_then_push(N, W, M, reflush, over, steps, st
         r.close(); e.close()
 
 
-@pytest.mark.parametrize("reflush", [True, False])
-def test_crowd_step_push_matches_the_rollout_oracle(reflush):
+@pytest.mark.parametrize("reflush,T_MAX", [pytest.param(True, 20, id="True"), pytest.param(False, 20, id="False"),
+                                            pytest.param(True, 33, id="True-tmax33")])       # 33: the serial backward pass
+def test_crowd_step_push_matches_the_rollout_oracle(reflush, T_MAX):
     """The one-launch path on a crowd env against oracle/rollout_oracle.run_episode, world by world and episode by episode, the way
     tests/test_gpu_rollout.py::test_rollout_matches_oracle holds the tile forms: rows and actions exact, returns to R_TOL, episode
     lengths exact, episode totals to its atol = 1e-4."""
-    N, W, steps, seed, T_MAX, GAMMA = 20, 24, 160, 3, 20, 0.97
+    N, W, steps, seed, GAMMA = 20, 24, 160, 3, 0.97
     env = _env(W, N, seed=seed, gen_min_agents=2, gen_nonlearning_fraction=0.3)
     roll = _rollout(env, reflush, steps, True, time_max=T_MAX, discount=GAMMA, ring_len=steps + 8)
     assert roll.step_path == ONE
@@ -127,6 +137,8 @@ def test_crowd_step_push_matches_the_rollout_oracle(reflush):
     episodes = roll.drain_episodes().cpu().numpy()
     assert batch.dropped == 0 and len(batch) > 0
     x, r, a, src = [v.cpu().numpy() for v in (batch.x, batch.r, batch.a_index, batch.src)]
+    if T_MAX > 20:
+        rs.require_deep_flushes(src, T_MAX, "crowd step_push vs oracle")
     got = {}
     for k in range(len(r)):
         got.setdefault(tuple(src[k]), []).append(k)          # (world, agent, recorded-at, emitted-at)

@@ -8,6 +8,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from oracle import rollout_oracle as ro
+from tests import rollout_scripts as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +27,14 @@ def _make(W, N, seed, **over):
 
 
 @pytest.mark.parametrize("fuse_env_push", ["1", "0"])      # env.step + bookkeeping as ONE launch (cavoid_step_push, the default) / as three
-@pytest.mark.parametrize("N,gen_min,nonl,reflush", [(4, 2, 0.3, True), (4, 4, 0.0, False), (10, 2, 0.2, True)])
-def test_rollout_matches_oracle(N, gen_min, nonl, reflush, fuse_env_push, monkeypatch):
+@pytest.mark.parametrize("N,gen_min,nonl,reflush,T_MAX", [
+    pytest.param(4, 2, 0.3, True, 20, id="4-2-0.3-True"), pytest.param(4, 4, 0.0, False, 20, id="4-4-0.0-False"),
+    pytest.param(10, 2, 0.2, True, 20, id="10-2-0.2-True"),
+    pytest.param(4, 2, 0.3, True, 33, id="4-2-0.3-True-tmax33")])       # 33: the serial backward pass (time_max + 1 > 32)
+def test_rollout_matches_oracle(N, gen_min, nonl, reflush, T_MAX, fuse_env_push, monkeypatch):
     monkeypatch.setenv("CAVOID_FUSE_ENV_PUSH", fuse_env_push)
     from rl_collision_avoidance_amd.ga3c.rollout import BatchedRollout
-    W, steps, seed, T_MAX, GAMMA = 96, 260, 3, 20, 0.97
+    W, steps, seed, GAMMA = 96, 260, 3, 0.97
     env = _make(W, N, seed, gen_min_agents=gen_min, gen_nonlearning_fraction=nonl)
     roll = BatchedRollout(env, policy=None, time_max=T_MAX, discount=GAMMA, reflush_done=reflush, ring_len=steps + 8,
                           dup_capacity=1000000)
@@ -48,6 +52,8 @@ def test_rollout_matches_oracle(N, gen_min, nonl, reflush, fuse_env_push, monkey
     episodes = roll.drain_episodes().cpu().numpy()
     assert batch.dropped == 0 and len(batch) > W * 20
     x, r, a, src = [v.cpu().numpy() for v in (batch.x, batch.r, batch.a_index, batch.src)]
+    if T_MAX > 20:
+        rs.require_deep_flushes(src, T_MAX, "rollout vs oracle, fuse_env_push=%s" % fuse_env_push)
     got = {}
     for k in range(len(r)):
         got.setdefault(tuple(src[k]), []).append(k)          # (world, agent, recorded-at, emitted-at)
