@@ -505,6 +505,28 @@ int cavoid_eval_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_policy *fr
                        float *obs, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps,
                        int32_t greedy, void *stream);
 
+/* cavoid_eval_run for CROWD worlds (17..64 agents per world; cavoid_eval_run refuses them): the same evaluation loop, up to n_steps steps in
+ * one launch that finished tiles leave early, over the crowd step form -- per tile of floor(64/N) worlds (at most 64 rows: one policy tile) a
+ * workgroup runs cavoid_policy_forward's arithmetic on the tile's rows with the input slots used as a ring (rows of up to 63 observed agents;
+ * the pass runs while one row of the tile still needs an action, and only those rows take its result: the others are handed action 0 /
+ * value 0), takes the argmax (or the Philox draw), steps the tile's worlds without auto-reset (cavoid_step's crowd launch) and records the
+ * outcome.  There is no `frozen` argument; `buffers` is cavoid_eval_run's struct, unchanged.  The records, the definition of "over", the
+ * return, the worlds_running protocol (zeroed on the stream by the call) and the step counter are exactly cavoid_eval_run's.  The return,
+ * once more, as the two blocks above define it: An agent's return sums the rewards up to and including the step
+ * at which its world is over.
+ * Trajectories are bit-identical to calling cavoid_policy_forward and cavoid_step per step.  With rvo_enabled = CAVOID_RVO_WAVE the launch
+ * runs over the ORCA-carrying env step; afterwards cavoid_last_step_form reports CAVOID_FORM_CROWD / CAVOID_FORM_CROWD_RVO, as after
+ * cavoid_step on such an env.  `policy`: a loaded LSTM handle (cavoid_policy_create) of the default inference form whose max_other is the
+ * env's, 1..63.
+ * CAVOID_EINVAL: cavoid_eval_run's cases -- null handles, buffers or record pointers, a wrong struct_size, n_steps < 0, a handle that is not
+ * loaded, handles that do not describe the same batch.  CAVOID_EUNSUPPORTED (evaluate step by step): what cavoid_crowd_actor_run refuses -- an
+ * env of <= 16 agents per world (cavoid_eval_run carries those), a weight-sharing handle, holonomic dynamics, CAVOID_POLICY_F32 / a
+ * non-default CAVOID_POLICY_PRODUCTS (the bf16 product form included), an env whose generator makes frozen-network agents
+ * (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0: one network per launch, there is no frozen form of this launch), and an env
+ * step whose LDS exceeds what cavoid_crowd_actor_run's launch allows.  n_steps == 0: CAVOID_OK, nothing is launched or written. */
+int cavoid_crowd_eval_run(cavoid_env *env, cavoid_policy *policy, const cavoid_eval_buffers *buffers, float *obs, float *rewards,
+                          uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps, int32_t greedy, void *stream);
+
 /* cavoid_step_autoreset + cavoid_rollout_push as ONE launch: the env step of every world and the Experience bookkeeping of its slots
  * (ProcessAgent.py:149-211) -- the fused actor's env phase for actors whose policy is a launch of its own (frozen-network agents,
  * a caller-supplied policy).  obs_cur [W,N,1+D]: the observation `actions` / `values` (V(s_t)) were computed on; the step writes the

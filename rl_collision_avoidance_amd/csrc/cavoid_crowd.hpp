@@ -372,7 +372,7 @@ __device__ __forceinline__ void crowd_tile(const KCfg &c, const KState &s, const
         const bool game_over = (running & wmask) == 0ull;
         rew_f = (float)r;
         done_f = done ? 1.0f : 0.0f;
-        if (out) { out->reward = rew_f; out->done = done; out->game_over = game_over; }
+        if (out) { out->reward = rew_f; out->done = done; out->game_over = game_over; out->flags = a.flags; }
         if (active) {
             if (!packed) {
                 io.rew[slot_w * n + a_idx] = rew_f;

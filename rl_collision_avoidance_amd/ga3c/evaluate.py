@@ -6,7 +6,8 @@ report: reached the goal / collided / ran out of time, and the extra time to goa
 Two paths produce the same numbers: the step-by-step loop (policy launch, ``env.step`` and a look at the world buffer per env
 step, one host synchronisation each) and, with ``fused=True``, ``cavoid_eval_run`` -- the whole loop per tile of worlds inside
 one launch of ``steps_per_launch`` steps that finished tiles leave early, the outcome recorded on the device (``fused_ws=True``:
-``cavoid_eval_run_ws``, the same for the ``weight_sharing`` network)."""
+``cavoid_eval_run_ws``, the same for the ``weight_sharing`` network; ``fused_crowd=True``: ``cavoid_crowd_eval_run``, the same for
+crowd worlds of 17 to 64 agents and the ``rnn`` network)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -160,6 +161,35 @@ def evaluate_fused_ws_unavailable_reason(env, policy, frozen_policy=None) -> Opt
     return None
 
 
+def evaluate_fused_crowd_unavailable_reason(env, policy, frozen_policy=None) -> Optional[str]:
+    """Why ``evaluate(fused_crowd=True)`` (``cavoid_crowd_eval_run``: the evaluation loop of crowd worlds inside one launch) does not apply
+    to this env and policy -- None when it does.  Host values only (no launch, no GPU), the refusals of the C entry point one for one
+    (what ``cavoid_crowd_actor_run`` refuses): worlds of 17..64 agents (tile worlds have ``fused=True``), a ``FusedPolicy`` of the ``rnn``
+    network on the default inference form whose neighbour count is the env's, table actions, and no frozen-network agents (the launch
+    carries one network).  The entry point's last refusal, an env step whose LDS exceeds what the policy pass lends it, has no case here:
+    ``cavoid_create`` admits no crowd env whose step takes more than that."""
+    n = int(env.max_agents)
+    if not hasattr(policy, "act") or not hasattr(policy, "inference_form") or getattr(policy, "_h", None) is None:
+        return "the policy is not a FusedPolicy (a plain callable is evaluated step by step)"
+    if n <= _lib.TILE_MAX_AGENTS:
+        return "%d agents per world: up to %d run the tile forms' evaluation kernel (fused=True / cavoid_eval_run)" % (n, _lib.TILE_MAX_AGENTS)
+    if getattr(policy, "ws", False) or getattr(policy, "arch", "rnn") != "rnn":
+        return ("the policy is the %s network (the crowd evaluation kernel embeds the LSTM pass; the weight_sharing ring form is evaluated "
+                "step by step)" % (getattr(policy, "arch", "weight_sharing"),))
+    if int(env.cfg.dynamics) == 2:
+        return "holonomic (velocity) actions"
+    if tuple(policy.inference_form) != ("split", 16):
+        return "the policy runs a non-default inference form %r (CAVOID_POLICY_F32 / CAVOID_POLICY_PRODUCTS at its creation)" % (
+            tuple(policy.inference_form),)
+    if int(policy.max_others) != int(env.max_other):
+        return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy.max_others), int(env.max_other))
+    if frozen_policy is not None:
+        return "a frozen_policy (the crowd evaluation kernel carries one network: there is no frozen form of this launch)"
+    if float(env.cfg.gen_frozen_fraction) > 0.0 and float(env.cfg.gen_nonlearning_fraction) > 0.0:
+        return "frozen-network agents (the crowd evaluation kernel carries one network; they act by their own)"
+    return None
+
+
 class _EvalRecords(object):
     """The device-side records of ``cavoid_eval_run`` for one env, and the per-step outputs it writes (``cavoid_eval_buffers``)."""
 
@@ -195,6 +225,17 @@ def eval_run_ws(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _
     _lib.check(_lib.lib().cavoid_eval_run_ws(env._h, policy._h, frozen_policy._h if frozen_policy is not None else None, C.byref(rec.c),
                                              ptr(env.obs), ptr(env.rewards), ptr(env.done), ptr(env.game_over), ptr(rec.actions), ptr(rec.values),
                                              int(n_steps), 1 if greedy else 0, env._stream()), "cavoid_eval_run_ws")
+
+
+def eval_run_crowd(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
+    """One ``cavoid_crowd_eval_run`` launch (the evaluation kernel of crowd worlds): ``eval_run``'s arguments and buffers; the launch
+    carries one network, so ``frozen_policy`` must be None."""
+    if frozen_policy is not None:
+        raise ValueError("cavoid_crowd_eval_run carries one network: no frozen_policy")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(_lib.lib().cavoid_crowd_eval_run(env._h, policy._h, C.byref(rec.c), ptr(env.obs), ptr(env.rewards), ptr(env.done),
+                                                ptr(env.game_over), ptr(rec.actions), ptr(rec.values), int(n_steps), 1 if greedy else 0,
+                                                env._stream()), "cavoid_crowd_eval_run")
 
 
 def _fused_round(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, launch: Callable, steps_per_launch: int, limit: int,
@@ -237,7 +278,7 @@ def _settle_finished(env: BatchedCollisionAvoidanceEnv, world_steps: torch.Tenso
 @torch.no_grad()
 def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 1, greedy: bool = True,
              max_steps: Optional[int] = None, frozen_policy=None, fused: bool = False, steps_per_launch: int = 16,
-             details: bool = False, fused_ws: bool = False) -> Dict[str, float]:
+             details: bool = False, fused_ws: bool = False, fused_crowd: bool = False) -> Dict[str, float]:
     """Run ``rounds`` batches of ``env.num_worlds`` episodes.  ``policy``: a ``FusedPolicy`` (its ``act`` is used) or any
     callable ``x [B, NN_INPUT_SIZE] -> (p [B, A], v [B])``.  Returns rates over the learning agents that took part.
 
@@ -247,19 +288,26 @@ def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 
     over, the loop's goes on summing what ``cavoid_step`` pays finished worlds until the slowest world ends (``reward_time_step``
     where one is set; at the default rewards the getting-close penalty of an agent that ran out of time beside another).
     ``fused_ws=True`` is the same for a ``FusedPolicy`` of the ``weight_sharing`` network: ``cavoid_eval_run_ws``, the same launch loop
-    and the same numbers (raises with ``evaluate_fused_ws_unavailable_reason``).  The two exclude each other; both are opt-in.
+    and the same numbers (raises with ``evaluate_fused_ws_unavailable_reason``).  ``fused_crowd=True`` is the same for crowd worlds
+    (17 to 64 agents per world) and the ``rnn`` network: ``cavoid_crowd_eval_run``, the ring form of the policy pass and the crowd env step
+    per tile (raises with ``evaluate_fused_crowd_unavailable_reason``; no ``frozen_policy``).  The three exclude each other; all are opt-in.
     ``details=True`` adds ``extra_time_p75`` / ``_p90`` and ``per_agent`` (``reduce_outcomes``)."""
     rec, launch = None, None
     if fused and fused_ws:
         raise ValueError("evaluate: fused=True (cavoid_eval_run, the rnn network) and fused_ws=True (cavoid_eval_run_ws, weight_sharing) exclude each other")
-    if fused or fused_ws:
-        why = (evaluate_fused_ws_unavailable_reason if fused_ws else evaluate_fused_unavailable_reason)(env, policy, frozen_policy)
+    if fused_crowd and (fused or fused_ws):
+        raise ValueError("evaluate: fused_crowd=True (cavoid_crowd_eval_run, crowd worlds) excludes fused=True and fused_ws=True (tile worlds)")
+    if fused or fused_ws or fused_crowd:
+        which = "fused_crowd" if fused_crowd else ("fused_ws" if fused_ws else "fused")
+        reason = {"fused": evaluate_fused_unavailable_reason, "fused_ws": evaluate_fused_ws_unavailable_reason,
+                  "fused_crowd": evaluate_fused_crowd_unavailable_reason}[which]
+        why = reason(env, policy, frozen_policy)
         if why is not None:
-            raise ValueError("evaluate(%s=True) does not apply: " % ("fused_ws" if fused_ws else "fused") + why)
+            raise ValueError("evaluate(%s=True) does not apply: " % which + why)
         if int(steps_per_launch) < 1:
             raise ValueError("steps_per_launch must be >= 1")
         rec = _EvalRecords(env)
-        launch = eval_run_ws if fused_ws else eval_run
+        launch = {"fused": eval_run, "fused_ws": eval_run_ws, "fused_crowd": eval_run_crowd}[which]
     W, N = env.num_worlds, env.max_agents
     dt = float(env.cfg.dt)
     limit = max_steps if max_steps is not None else 100000

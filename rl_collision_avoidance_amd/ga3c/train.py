@@ -120,6 +120,12 @@ def main(argv=None) -> None:
                          "env.step without auto-reset and the outcome record per tile of worlds); same numbers.  The run ends if the "
                          "configuration is one the kernel does not carry (the rnn network, the ring form above 19 neighbours, crowd worlds, "
                          "the PyTorch policy).  Opt-in (profiles/eval_ws_fused_timing.txt: tools/evalbench.py --arch weight_sharing)")
+    ap.add_argument("--fused-crowd-evaluate", action="store_true",
+                    help="with --evaluate and --agents 17..64: the same for crowd worlds and the rnn network -- launches of --steps-per-graph env "
+                         "steps of cavoid_crowd_eval_run (the ring form of the policy pass, argmax, the crowd env.step without auto-reset and the "
+                         "outcome record per tile of floor(64/N) worlds); same numbers.  The run ends if the configuration is one the kernel "
+                         "does not carry (up to 16 agents per world, the weight_sharing network, frozen-network agents, holonomic dynamics, the "
+                         "PyTorch policy).  Opt-in (profiles/crowd_eval_fused_timing.txt: tools/crowdevalbench.py)")
     ap.add_argument("--pretrain-steps", type=int, default=0,
                     help="supervised initialisation before RL (the role of Regression.py): Adam steps on teacher-driven rollouts")
     ap.add_argument("--fused-regression", action="store_true",
@@ -332,6 +338,16 @@ def main(argv=None) -> None:
                 print("[Evaluate] fused weight_sharing evaluation kernel (cavoid_eval_run_ws), %d env steps per launch" % args.steps_per_graph,
                       flush=True)
             res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused_ws=True, steps_per_launch=args.steps_per_graph)
+        elif args.fused_crowd_evaluate:
+            from .evaluate import evaluate_fused_crowd_unavailable_reason
+            why = evaluate_fused_crowd_unavailable_reason(env, eval_policy, frozen)
+            if why is not None:
+                raise SystemExit("--fused-crowd-evaluate: the fused crowd evaluation kernel (cavoid_crowd_eval_run) does not apply: " + why)
+            if args.steps_per_graph < 1:
+                raise SystemExit("--steps-per-graph must be >= 1")
+            if rank == 0:
+                print("[Evaluate] fused crowd evaluation kernel (cavoid_crowd_eval_run), %d env steps per launch" % args.steps_per_graph, flush=True)
+            res = evaluate(env, eval_policy, rounds=args.evaluate, fused_crowd=True, steps_per_launch=args.steps_per_graph)
         else:
             res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen)
         if rank == 0:
