@@ -417,7 +417,7 @@ int cavoid_actor_run_mix(cavoid_env *env, cavoid_policy *policy, cavoid_policy *
  * the launch runs over the ORCA-carrying env step; afterwards cavoid_last_step_form reports CAVOID_FORM_CROWD / CAVOID_FORM_CROWD_RVO as after
  * cavoid_step_push.  `policy`: an LSTM handle (cavoid_policy_create) of the default inference form whose max_other is the env's, 1..63.
  * CAVOID_EINVAL: null or mismatching handles and buffers (cavoid_actor_run's checks).  CAVOID_EUNSUPPORTED (use the step-by-step entry
- * points): an env of <= 16 agents per world (cavoid_actor_run carries those), a weight-sharing handle, holonomic dynamics,
+ * points): an env of <= 16 agents per world (cavoid_actor_run carries those), a weight-sharing handle (cavoid_crowd_actor_run_ws carries it), holonomic dynamics,
  * CAVOID_POLICY_F32 / a non-default CAVOID_POLICY_PRODUCTS (the bf16 product form included), and an env whose generator makes frozen-network
  * agents (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0: there is no _mix form of this launch; the refusal looks at the generator's
  * fractions only, as cavoid_actor_run's).  n_steps == 0: CAVOID_OK, nothing is launched. */
@@ -433,13 +433,32 @@ int cavoid_crowd_actor_run(cavoid_env *env, cavoid_policy *policy, cavoid_rollou
  * cavoid_step_push).  `policy`: a loaded cavoid_policy_create_ws handle whose max_other (1..19) is the env's.
  * CAVOID_EINVAL: null or mismatching handles and buffers (cavoid_actor_run's checks).  CAVOID_EUNSUPPORTED (use the step-by-step entry
  * points): an LSTM handle (cavoid_actor_run carries it), a cavoid_policy_create_ws_crowd handle (the ring form, 20..64 observed agents), an env of
- * more than 16 agents per world, holonomic dynamics, an env whose generator makes frozen-network agents (gen_frozen_fraction > 0 with
+ * more than 16 agents per world (cavoid_crowd_actor_run_ws carries crowd worlds, with either weight-sharing handle), holonomic dynamics, an env whose generator makes frozen-network agents (gen_frozen_fraction > 0 with
  * gen_nonlearning_fraction > 0: one network per launch, no _mix form; the refusal looks at the generator's fractions only, as
  * cavoid_actor_run's), and an env step whose LDS (with rvo_enabled: the ORCA lines) does not fit the 66 560 bytes of activation rows the pass
  * lends it.  n_steps == 0: CAVOID_OK, nothing is launched. */
 int cavoid_actor_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_rollout *rollout, const cavoid_rollout_buffers *buffers,
                         float *obs_cur, float *obs_next, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values,
                         int32_t n_steps, int32_t greedy, void *stream);
+
+/* cavoid_actor_run_ws for CROWD worlds (17..64 agents per world): the same closed loop, K steps in one launch, over the crowd step form -- per
+ * tile of floor(64/N) worlds (at most 64 rows: one policy tile) a workgroup runs the weight-sharing pass on the tile's rows that need an action
+ * with the input slots used as a ring (rows of up to 63 observed agents; with 19 or fewer no slot is refilled), draws the actions, steps the
+ * tile's worlds (cavoid_step_push's crowd launch: env step + Experience bookkeeping + episode log) and copies the step's state rows into the
+ * experience store.  Arguments, buffers, counters and the rule for the rows that need an action exactly as cavoid_actor_run; results are
+ * bit-identical to the step-by-step entry points (cavoid_rollout_active_rows, cavoid_policy_forward[_rows], cavoid_step_push).  With rvo_enabled =
+ * CAVOID_RVO_WAVE the launch runs over the ORCA-carrying env step; afterwards cavoid_last_step_form reports CAVOID_FORM_CROWD /
+ * CAVOID_FORM_CROWD_RVO as after cavoid_step_push.  `policy`: a loaded weight-sharing handle whose max_other is the env's -- cavoid_policy_create_ws
+ * (1..19) or cavoid_policy_create_ws_crowd (20..64): one kernel serves both.
+ * CAVOID_EINVAL: null or mismatching handles and buffers (cavoid_crowd_actor_run's checks).  CAVOID_EUNSUPPORTED (use the step-by-step entry
+ * points): an env of <= 16 agents per world (cavoid_actor_run_ws carries those), an LSTM handle (cavoid_crowd_actor_run carries it), holonomic
+ * dynamics (velocity actions), an env whose generator makes frozen-network agents (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0:
+ * one network per launch, no _mix form; the refusal looks at the generator's fractions only, as cavoid_actor_run's), an env with scenario
+ * look-ahead rings, and a crowd env step whose LDS exceeds 64 KiB or the 66 560 bytes of activation rows the pass lends it.
+ * n_steps == 0: CAVOID_OK, nothing is launched. */
+int cavoid_crowd_actor_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_rollout *rollout, const cavoid_rollout_buffers *buffers,
+                              float *obs_cur, float *obs_next, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values,
+                              int32_t n_steps, int32_t greedy, void *stream);
 
 /* ---- evaluation: K greedy (or sampled) steps of every world in ONE launch, with outcome records ------------------------------------
  * The EVALUATE_MODE loop (argmax actions, ga3c/GA3C/ProcessAgent.py:98-103; every agent of a world must finish) without the host in it:
@@ -670,7 +689,7 @@ int cavoid_policy_train(cavoid_policy *p, const float *x, int64_t rows, int64_t 
  *   cavoid_policy_forward / _forward_rows / _seed / _info / _destroy take either kind of handle (same arguments, same action draw;
  *       _info reports use_split = 0, split_products = 0).  cavoid_policy_load / _train on a weight-sharing handle, and _load_ws /
  *       _train_ws on an LSTM handle, are CAVOID_EINVAL; cavoid_actor_run / _run_mix with one (as policy or frozen) are
- *       CAVOID_EUNSUPPORTED (cavoid_actor_run_ws is this network's closed actor loop).  CAVOID_POLICY_F32 / _PRODUCTS / _FORM do not apply.
+ *       CAVOID_EUNSUPPORTED (cavoid_actor_run_ws is this network's closed actor loop, cavoid_crowd_actor_run_ws the one of crowd worlds).  CAVOID_POLICY_F32 / _PRODUCTS / _FORM do not apply.
  *   cavoid_policy_train_ws : the trainer pass of cavoid_policy_train for this network (load with with_backward = 1).  The contractions it
  *       leaves the operands of (cavoid_policy_weight_grads_ws forms them, or the caller's own GEMM library):
  *       d fullyconnected1 = z2^T g3,  d layer2 = z1^T g2,  d [logits_p | logits_v] = z3^T gh,

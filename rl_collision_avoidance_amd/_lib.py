@@ -163,6 +163,7 @@ SYMBOLS = [
     ("cavoid_actor_run_mix", C.c_int, [_P, _P, _P, _P, C.POINTER(CavoidRolloutBuffers)] + [_P] * 7 + [C.c_int32, C.c_int32, _P]),
     ("cavoid_crowd_actor_run", C.c_int, [_P, _P, _P, C.POINTER(CavoidRolloutBuffers)] + [_P] * 7 + [C.c_int32, C.c_int32, _P]),
     ("cavoid_actor_run_ws", C.c_int, [_P, _P, _P, C.POINTER(CavoidRolloutBuffers)] + [_P] * 7 + [C.c_int32, C.c_int32, _P]),
+    ("cavoid_crowd_actor_run_ws", C.c_int, [_P, _P, _P, C.POINTER(CavoidRolloutBuffers)] + [_P] * 7 + [C.c_int32, C.c_int32, _P]),
     ("cavoid_eval_run", C.c_int, [_P, _P, _P, C.POINTER(CavoidEvalBuffers)] + [_P] * 6 + [C.c_int32, C.c_int32, _P]),
     ("cavoid_eval_run_ws", C.c_int, [_P, _P, _P, C.POINTER(CavoidEvalBuffers)] + [_P] * 6 + [C.c_int32, C.c_int32, _P]),
     ("cavoid_crowd_eval_run", C.c_int, [_P, _P, C.POINTER(CavoidEvalBuffers)] + [_P] * 6 + [C.c_int32, C.c_int32, _P]),

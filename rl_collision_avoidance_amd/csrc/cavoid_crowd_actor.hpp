@@ -38,6 +38,66 @@ __device__ __forceinline__ int crowd_actor_lane_id() {
     return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z));
 }
 
+// The env half of a crowd actor step, shared by crowd_actor_kernel and crowd_ws_rollout_kernel (cavoid_crowd_actor_ws.hpp): wavefront 0 runs env.step
+// of the tile (its LDS at lds_tab / wbase, inside the policy's idle activation memory), then the Experience bookkeeping of the tile's slots
+// and the episode log -- the statements of crowd_push_kernel's wavefront 0 -- and leaves the mask of the rows that need an action at the
+// NEXT step in live_next[0..1] (LDS the env step does not reach); wavefronts 1..3 meanwhile copy the step's state rows into the time-major
+// experience ring (they touch no LDS).  Between the caller's two workgroup barriers.
+template <int NB, bool RVO>
+__device__ __forceinline__ void crowd_actor_env_phase(const KCfg &c, const KState &s, const PoolRec *pool, const RolloutCfg &rc, const RolloutState &rs,
+                                                      const RolloutIO &rio_arg, const ActorIO &io, const float *obs_t, float *obs_n, double *lds_tab,
+                                                      float *wbase, int *live_next, const int n, const int wave_in_block, const int lane,
+                                                      const int64_t tile, const int64_t w0, const int64_t a0, const int rows, const int32_t step,
+                                                      const int blk) {
+    const int wpw = c.wpw, ow = c.width;
+    if (wave_in_block == 0) {
+        // ---- env.step of the tile, then the Experience bookkeeping of its slots: crowd_push_kernel's wavefront 0 ----------------
+        KIO k{};
+        k.actions = io.actions; k.obs = obs_n; k.rew = io.rewards; k.done = io.done; k.game_over = io.game_over;
+        k.obs_stride = ow; k.n_steps = 1;                    /* (out_step_stride = 0: the one step's outputs in slot 0) */
+        StepOut so{0.0f, true, false, false};
+        const int lw = lane / n, i = lane - lw * n;
+        const int64_t w = w0 + lw, a = w * n + i;
+        const bool in_range = lane < wpw * n && w < c.num_worlds;
+        // the bookkeeping's first trip to memory, issued in front of the env step (see actor_env_push_tile)
+        const RolloutSlot slot_in = rollout_slot_load(rs, a, in_range);
+        float learn_f = 0.0f, value = 0.0f;                  // is_learning of the state acted on (ProcessAgent.py:130)
+        int action = 0;
+        if (in_range) { learn_f = obs_t[a * ow]; value = io.values[a]; action = io.actions[a]; }
+        if constexpr (RVO) {
+            // The ORCA solve divides by c.dt (1.0 / c.dt, cavoid_crowd_rvo.hpp).  c is a kernel argument, so the quotient is invariant
+            // and was hoisted out of the STEP loop into a vector register pair live across the policy pass: 8 bytes of scratch per lane.
+            // A copy of the configuration whose dt the compiler cannot see through keeps the division inside the env phase -- the
+            // same operation on the same value; every other field is still read from the kernel arguments where it is used.
+            KCfg cc = c;
+            asm volatile("" : "+s"(cc.dt));
+            crowd_tile<NB, MODE_STEP_AUTORESET_N, RVO>(cc, s, pool, k, n, lds_tab, wbase, lane, tile, &so);
+        } else {
+            crowd_tile<NB, MODE_STEP_AUTORESET_N, RVO>(c, s, pool, k, n, lds_tab, wbase, lane, tile, &so);
+        }
+        {   // the rows that need an action at the NEXT step, for the next policy pass: in LDS (behind the lent memory)
+            const unsigned long long m = __ballot(in_range && so.learning_next && (so.game_over || !so.done));
+            if (lane == 0) { live_next[0] = (int)(uint32_t)m; live_next[1] = (int)(uint32_t)(m >> 32); }
+        }
+        const bool learning = in_range && learn_f > 0.5f;
+        const int base = lane < wpw * n ? lw * n : 0;
+        const uint64_t wbits = n >= 64 ? ~0ull : ((1ull << n) - 1ull);       // (crowd_tile's form: a shift by 64 is undefined)
+        const int n_learning = __popcll(__ballot(learning) & (wbits << base));
+        RolloutIO rio = rio_arg;
+        rollout_push_slot(rc, rs, rio, a, in_range ? w : 0, i, in_range, learning, n_learning, so.done, so.game_over, so.reward, value, action,
+                          step, blk, slot_in);
+        // episode_log_q.put: the totals above were accumulated with atomics by this wavefront's own lanes -- drain them;
+        // rollout_close_episode reads the sums at the cache the atomics went to
+        if (__ballot(in_range && so.game_over) != 0ull) {
+            __builtin_amdgcn_s_waitcnt(0);                   // (vmcnt 0: the atomics have been performed at the L2)
+            if (in_range && i == 0 && so.game_over) rollout_close_episode(rc, rs, rio, w);
+        }
+    } else {
+        // ---- meanwhile: the step's state rows -> the time-major experience store -----------------------------------------
+        rollout_copy_rows(rc, obs_t, rio_arg.x, a0, rows, blk, (wave_in_block - 1) * 64 + lane, 192);
+    }
+}
+
 template <int NB, bool RVO>
 __global__ void __launch_bounds__(256, 2) crowd_actor_kernel(const KCfg c, const KState s, const PoolRec *pool, const SplitArgs sa, const RolloutCfg rc,
                                                              const RolloutState rs, const RolloutIO rio_arg, const ActorIO io, const int n) {
@@ -111,52 +171,10 @@ __global__ void __launch_bounds__(256, 2) crowd_actor_kernel(const KCfg c, const
         __syncthreads();                                     // the tile's actions / values are in memory; the planes are idle
         lane = crowd_actor_lane_id();                        // (made again: not carried across the pass)
 
-        if (wave_in_block == 0) {
-            // ---- env.step of the tile, then the Experience bookkeeping of its slots: crowd_push_kernel's wavefront 0 ----------------
-            KIO k{};
-            k.actions = io.actions; k.obs = obs_n; k.rew = io.rewards; k.done = io.done; k.game_over = io.game_over;
-            k.obs_stride = ow; k.n_steps = 1;                    /* (out_step_stride = 0: the one step's outputs in slot 0) */
-            StepOut so{0.0f, true, false, false};
-            const int lw = lane / n, i = lane - lw * n;
-            const int64_t w = w0 + lw, a = w * n + i;
-            const bool in_range = lane < wpw * n && w < c.num_worlds;
-            // the bookkeeping's first trip to memory, issued in front of the env step (see actor_env_push_tile)
-            const RolloutSlot slot_in = rollout_slot_load(rs, a, in_range);
-            float learn_f = 0.0f, value = 0.0f;                  // is_learning of the state acted on (ProcessAgent.py:130)
-            int action = 0;
-            if (in_range) { learn_f = obs_t[a * ow]; value = io.values[a]; action = io.actions[a]; }
-            if constexpr (RVO) {
-                // The ORCA solve divides by c.dt (1.0 / c.dt, cavoid_crowd_rvo.hpp).  c is a kernel argument, so the quotient is invariant
-                // and was hoisted out of the STEP loop into a vector register pair live across the policy pass: 8 bytes of scratch per lane.
-                // A copy of the configuration whose dt the compiler cannot see through keeps the division inside the env phase -- the
-                // same operation on the same value; every other field is still read from the kernel arguments where it is used.
-                KCfg cc = c;
-                asm volatile("" : "+s"(cc.dt));
-                crowd_tile<NB, MODE_STEP_AUTORESET_N, RVO>(cc, s, pool, k, n, lds_tab, wbase, lane, tile, &so);
-            } else {
-                crowd_tile<NB, MODE_STEP_AUTORESET_N, RVO>(c, s, pool, k, n, lds_tab, wbase, lane, tile, &so);
-            }
-            {   // the rows that need an action at the NEXT step, for the next policy pass: in LDS (behind the planes)
-                const unsigned long long m = __ballot(in_range && so.learning_next && (so.game_over || !so.done));
-                if (lane == 0) { wave_max[12] = (int)(uint32_t)m; wave_max[13] = (int)(uint32_t)(m >> 32); }
-            }
-            const bool learning = in_range && learn_f > 0.5f;
-            const int base = lane < wpw * n ? lw * n : 0;
-            const uint64_t wbits = n >= 64 ? ~0ull : ((1ull << n) - 1ull);       // (crowd_tile's form: a shift by 64 is undefined)
-            const int n_learning = __popcll(__ballot(learning) & (wbits << base));
-            RolloutIO rio = rio_arg;
-            rollout_push_slot(rc, rs, rio, a, in_range ? w : 0, i, in_range, learning, n_learning, so.done, so.game_over, so.reward, value, action,
-                              step, blk, slot_in);
-            // episode_log_q.put: the totals above were accumulated with atomics by this wavefront's own lanes -- drain them;
-            // rollout_close_episode reads the sums at the cache the atomics went to
-            if (__ballot(in_range && so.game_over) != 0ull) {
-                __builtin_amdgcn_s_waitcnt(0);                   // (vmcnt 0: the atomics have been performed at the L2)
-                if (in_range && i == 0 && so.game_over) rollout_close_episode(rc, rs, rio, w);
-            }
-        } else {
-            // ---- meanwhile: the step's state rows -> the time-major experience store -----------------------------------------
-            rollout_copy_rows(rc, obs_t, rio_arg.x, a0, rows, blk, (wave_in_block - 1) * 64 + lane, 192);
-        }
+        // ---- env.step of the tile + the Experience bookkeeping of its slots on wavefront 0, the step's state rows -> the experience store
+        //      on wavefronts 1..3; the next step's live mask at wave_max[12], [13]
+        crowd_actor_env_phase<NB, RVO>(c, s, pool, rc, rs, rio_arg, io, obs_t, obs_n, lds_tab, wbase, wave_max + 12, n, wave_in_block, lane, tile, w0, a0,
+                                       rows, step, blk);
         __syncthreads();                                     // obs(t+1), the world state and the slot state are in memory
     }
 }

@@ -131,7 +131,8 @@ struct PolicyWsArgs {
 // slots hold the whole row (M <= kWsMaxOthers) or are a ring of R slots refilled while the slot loop runs (the kernels and the
 // protocol of cavoid_policy_wsring.hpp).
 //
-// FUSED = true: the pass as ONE PHASE of a kernel that goes on (actor_ws_kernel, cavoid_actor_ws.hpp) instead of a whole launch.  The
+// FUSED = true: the pass as ONE PHASE of a kernel that goes on (actor_ws_kernel, cavoid_actor_ws.hpp; with the ring crowd_ws_rollout_kernel,
+// cavoid_crowd_actor_ws.hpp: the ring's refills go through the caller's row list like the staging) instead of a whole launch.  The
 // caller hands over what the launch forms derive from the grid and the device-side counters: the thread id (`tid_in`; its step loop
 // re-materialises it), the tile's rows as a list it has written to the LDS row list (ws_tile_row(): `rows_in` GLOBAL rows, the row-list
 // form's gather from p.x and its scatter of the outputs) and the step that keys the action draw (`step_in`).  The CU ticket is the
@@ -139,7 +140,7 @@ struct PolicyWsArgs {
 // row's outputs is the launch forms': the results are theirs bit for bit.
 template <bool TRAIN, int LOSS, class Ring = PolNoRing, bool FUSED = false>
 __device__ __forceinline__ void policy_ws_forward_tile(const PolicyWsArgs &wa, int tid_in = 0, int rows_in = 0, int step_in = 0) {
-    static_assert(!FUSED || (!TRAIN && !Ring::on), "the fused phase is the actors' whole-row pass");
+    static_assert(!FUSED || !TRAIN, "the fused phase is the actors' pass (whole-row, or with the ring: crowd_ws_rollout_kernel)");
     constexpr int RT = 4, kRows = 64;
     const PolicyArgs &p = wa.a;
     // LDS: rows [kRows][kPolStride], the packed biases, 8 ints, the tile's row list.  While the slots run, a row is

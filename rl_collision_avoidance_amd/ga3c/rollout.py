@@ -112,6 +112,53 @@ def ws_actor_unavailable_reason(agents_per_world: int, dynamics: int, arch: str,
     return None
 
 
+def crowd_env_step_lds_bytes(agents_per_world: int, obs_width: int) -> int:
+    """The LDS the crowd env step of one tile takes inside an actor launch (``crowd_actor_env_lds_bytes``, csrc/cavoid_crowd_actor.hpp): the
+    action table, the wavefront's arrays (``crowd_lds_fixed_floats``, csrc/cavoid_crowd.hpp: staged records, velocities, generator scratch,
+    gaps, ranks) and the key region that later holds the observation tile, at the tile ``cavoid_create`` chooses for a crowd env -- as many
+    rows as fit the key region, in fours, at least 4, at most the tile's ``floor(64/n) * n``."""
+    n, width = int(agents_per_world), int(obs_width)
+    fixed = 64 * 8 + 64 * 2 * 2 + (64 * 2 * 4 + 64) + (n - 1) * 64 + (n - 1) * 16
+    keys = (n - 1) * 64 * 2
+    rows = min(max((keys // (width + 2)) & ~3, 4), (64 // n) * n)
+    return 4 * (128 + fixed + max((rows * width + 3) & ~3, keys))
+
+
+def crowd_ws_actor_unavailable_reason(agents_per_world: int, dynamics: int, arch: str, policy_max_others: int, env_max_other: int,
+                                      frozen_agents: bool, env_step_lds: int = 0, fused_policy: bool = True) -> Optional[str]:
+    """Why ``BatchedRollout.run_fused_crowd_ws`` (``cavoid_crowd_actor_run_ws``: the closed actor loop of crowd worlds with the
+    weight_sharing network, K steps in one launch) does not apply -- None when it does.  A pure function of host values, the refusals of the
+    C entry point one for one: worlds of 17..64 agents (tile worlds have ``run_fused_ws``), a ``FusedPolicy`` of the ``weight_sharing``
+    network -- on the whole-row handle up to ``MAX_OTHERS_WS`` observed neighbours, on the ring handle (``ws_crowd=True``; ``ga3c.train
+    --fused-crowd-ws``) above: a network of more neighbours has no ``FusedPolicy`` without it -- whose neighbour count is the env's, table
+    actions, no frozen-network agents (the launch carries one network), and an env step whose LDS (``env_step_lds`` bytes) fits the rows
+    the pass lends it."""
+    n = int(agents_per_world)
+    if not 1 <= n <= _lib.MAX_AGENTS:
+        raise ValueError("agents per world must be 1..%d" % _lib.MAX_AGENTS)
+    if n <= _lib.TILE_MAX_AGENTS:
+        return ("%d agents per world: up to %d run the tile forms' weight_sharing actor kernel (run_fused_ws / cavoid_actor_run_ws)"
+                % (n, _lib.TILE_MAX_AGENTS))
+    if not fused_policy:
+        if int(env_max_other) > MAX_OTHERS_WS:
+            return ("the policy is not a FusedPolicy (a weight_sharing network of %d observed neighbours, more than %d, has one on the ring "
+                    "kernels only: FusedPolicy(net, ws_crowd=True), ga3c.train --fused-crowd-ws)" % (int(env_max_other), MAX_OTHERS_WS))
+        return "the policy is not a FusedPolicy"
+    if arch != "weight_sharing":
+        return ("the policy is the %s network (the crowd weight_sharing actor kernel embeds the weight_sharing pass; run_fused_crowd / "
+                "cavoid_crowd_actor_run carries rnn)" % (arch,))
+    if int(dynamics) == 2:
+        return "holonomic (velocity) actions"
+    if int(policy_max_others) != int(env_max_other):
+        return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy_max_others), int(env_max_other))
+    if frozen_agents:
+        return "frozen-network agents (the crowd weight_sharing actor kernel carries one network: no _mix form)"
+    if int(env_step_lds) > min(65536, WS_ACTOR_LENT_BYTES):
+        return ("the crowd env step's LDS (%d bytes) does not fit the %d bytes the weight_sharing pass lends it"
+                % (int(env_step_lds), min(65536, WS_ACTOR_LENT_BYTES)))
+    return None
+
+
 class TrainingBatch(object):
     """Rows that became final since the last drain: ``x`` f32 [n, D], ``r`` f32 [n] (n-step returns),
     ``a_index`` int32 [n], ``src`` int32 [n, 4] (world, agent, recorded-at step, emitted-at step)."""
@@ -497,6 +544,59 @@ class BatchedRollout(object):
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             self.run_fused_ws(steps_per_graph)
+        self.step_index -= steps_per_graph                # capture records, it does not execute
+        self._graph_steps = steps_per_graph
+
+    # -- the fused actor of crowd worlds with the weight_sharing network: opt-in, beside the step-by-step path ----------------------
+    @property
+    def crowd_ws_fused_unavailable_reason(self) -> Optional[str]:
+        """Why ``run_fused_crowd_ws`` does not apply to this rollout (None: it does) -- ``crowd_ws_actor_unavailable_reason`` on its values."""
+        cfg, pol = self.env.cfg, self.policy
+        return crowd_ws_actor_unavailable_reason(
+            self.env.max_agents, cfg.dynamics, getattr(pol, "arch", "rnn"), getattr(pol, "max_others", -1), cfg.max_other,
+            self.frozen_policy is not None or (cfg.gen_frozen_fraction > 0.0 and cfg.gen_nonlearning_fraction > 0.0),
+            env_step_lds=(crowd_env_step_lds_bytes(self.env.max_agents, self.env.obs_width)
+                          if self.env.max_agents > _lib.TILE_MAX_AGENTS else 0),
+            fused_policy=bool(getattr(pol, "accepts_strided_obs", False)))
+
+    @property
+    def crowd_ws_fused_available(self) -> bool:
+        """``run_fused_crowd_ws`` applies (``fused_available``, ``crowd_fused_available`` and ``ws_fused_available`` stay False for the
+        weight_sharing network on crowd worlds: the default paths do not change)."""
+        return self.crowd_ws_fused_unavailable_reason is None
+
+    def run_fused_crowd_ws(self, n_steps: int) -> None:
+        """``run_fused_ws`` for crowd worlds: ``n_steps`` closed-loop steps of every world in ONE launch (``cavoid_crowd_actor_run_ws``) --
+        per tile of floor(64/N) worlds a workgroup runs the weight_sharing pass (float32 MFMA, the input slots as a ring: up to 63
+        observed neighbours) on its own rows that need an action, steps its worlds and records the step.  Bit-identical to ``n_steps``
+        calls of ``step()``; capturable into a hipGraph."""
+        why = self.crowd_ws_fused_unavailable_reason
+        if why is not None:
+            raise RuntimeError("run_fused_crowd_ws does not apply: " + why)
+        env, pol = self.env, self.policy
+        b = self._actor_buffers()
+        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
+        p = BatchedCollisionAvoidanceEnv._ptr
+        _lib.check(self._lib.cavoid_crowd_actor_run_ws(env._h, pol._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done),
+                                                       p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps),
+                                                       1 if self.greedy else 0, env._stream()), "cavoid_crowd_actor_run_ws")
+        self._cur = (self._cur + int(n_steps)) & 1
+        self.step_index += int(n_steps)
+
+    def capture_fused_crowd_ws(self, steps_per_graph: int = 4) -> None:
+        """``run_fused_crowd_ws(steps_per_graph)`` as a one-node hipGraph, as ``capture_fused_crowd``: an even step count (the two
+        observation buffers alternate), two warm-up steps outside the capture; ``replay`` serves it."""
+        if steps_per_graph < 2 or steps_per_graph % 2:
+            raise ValueError("steps_per_graph must be a positive even number")
+        side = torch.cuda.Stream(device=self.env.device)
+        side.wait_stream(torch.cuda.current_stream(self.env.device))
+        with torch.cuda.stream(side):
+            self.run_fused_crowd_ws(2)
+        torch.cuda.current_stream(self.env.device).wait_stream(side)
+        torch.cuda.synchronize(self.env.device)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self.run_fused_crowd_ws(steps_per_graph)
         self.step_index -= steps_per_graph                # capture records, it does not execute
         self._graph_steps = steps_per_graph
 

@@ -185,6 +185,14 @@ def main(argv=None) -> None:
                          "hipGraph; the run ends if the configuration is one the kernel does not carry (the rnn network, the ring form above 19 "
                          "neighbours, crowd worlds, frozen-network agents, the PyTorch policy).  Opt-in until a whole training run has been "
                          "timed with and without it (profiles/ws_actor_timing.txt holds the actor loop alone: tools/wsactorbench.py)")
+    ap.add_argument("--fused-crowd-ws-actor", action="store_true",
+                    help="run the actors of crowd worlds with the weight_sharing network (--agents 17..64 --arch weight_sharing) as ONE launch "
+                         "per --steps-per-graph env steps (cavoid_crowd_actor_run_ws: the weight_sharing pass on the rows that need an action, "
+                         "action draw, crowd env.step and Experience bookkeeping per tile of worlds inside one kernel) instead of one launch per "
+                         "phase in a hipGraph; above 19 observed neighbours it needs --fused-crowd-ws (the policy must be a FusedPolicy on the "
+                         "ring kernels); the run ends if the configuration is one the kernel does not carry (the rnn network, tile worlds, "
+                         "frozen-network agents, the PyTorch policy).  Opt-in until a whole training run has been timed with and without it "
+                         "(profiles/crowd_ws_actor_timing.txt holds the actor loop alone: tools/crowdwsactorbench.py)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--print-every", type=int, default=2000, help="stats line every n episodes (rank 0)")
     ap.add_argument("--faithful-reflush", action="store_true", help="keep the reference's post-done re-flush quirk")
@@ -404,6 +412,12 @@ def main(argv=None) -> None:
             raise SystemExit("--fused-ws-actor: the weight_sharing actor kernel (cavoid_actor_run_ws) does not apply: " + why)
         roll.capture_fused_ws(steps_per_graph=args.steps_per_graph)
         actors = "fused weight_sharing actor kernel (cavoid_actor_run_ws), %d env steps per launch" % args.steps_per_graph
+    elif args.fused_crowd_ws_actor:
+        why = roll.crowd_ws_fused_unavailable_reason
+        if why is not None:
+            raise SystemExit("--fused-crowd-ws-actor: the crowd weight_sharing actor kernel (cavoid_crowd_actor_run_ws) does not apply: " + why)
+        roll.capture_fused_crowd_ws(steps_per_graph=args.steps_per_graph)
+        actors = "fused crowd weight_sharing actor kernel (cavoid_crowd_actor_run_ws), %d env steps per launch" % args.steps_per_graph
     elif roll.fused_available and not args.no_actor_kernel:
         roll.capture_fused(steps_per_graph=args.steps_per_graph)       # K closed-loop steps per launch (cavoid_actor_run)
         actors = "%s, %d env steps per launch" % (roll.actor_path, args.steps_per_graph)
