@@ -546,6 +546,35 @@ int cavoid_eval_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_policy *fr
 int cavoid_crowd_eval_run(cavoid_env *env, cavoid_policy *policy, const cavoid_eval_buffers *buffers, float *obs, float *rewards,
                           uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps, int32_t greedy, void *stream);
 
+/* cavoid_eval_run_ws for CROWD worlds (17..64 agents per world; cavoid_eval_run_ws refuses them): the evaluation loop of the WEIGHT-SHARING
+ * network over the crowd step form, up to n_steps steps in one launch that finished tiles leave early -- per tile of floor(64/N) worlds (at
+ * most 64 rows: one policy tile) a workgroup lists the tile's rows that still need an action, runs the weight-sharing pass on them
+ * (cavoid_policy_forward's arithmetic on a weight-sharing handle: float32 MFMA, the input slots used as a ring: rows of up to 63 observed
+ * agents), takes the argmax (or the Philox draw), steps the tile's worlds without auto-reset (cavoid_step's crowd launch) and records the
+ * outcome.  Rows that need no action (a finished agent, a scripted agent, an absent slot) are handed action 0 / value 0.  The argument list
+ * is cavoid_eval_run_ws's; `buffers` is cavoid_eval_run's struct, unchanged.  The records, the definition of "over", the return, the
+ * worlds_running protocol (zeroed on the stream by the call) and the step counter are exactly cavoid_eval_run's.  The return, as the
+ * blocks above define it: An agent's return sums the rewards up to and including the step
+ * at which its world is over.
+ * Trajectories are bit-identical to calling cavoid_policy_forward (+ cavoid_policy_forward_rows on `frozen` for the
+ * CAVOID_POLICY_FROZEN_NET rows) and cavoid_step per step.  With rvo_enabled = CAVOID_RVO_WAVE the launch runs over the ORCA-carrying env
+ * step; afterwards cavoid_last_step_form reports CAVOID_FORM_CROWD / CAVOID_FORM_CROWD_RVO, as after cavoid_step on such an env.  The
+ * scenario look-ahead is not touched: nothing restarts.
+ *   policy: a loaded weight-sharing handle whose max_other is the env's -- cavoid_policy_create_ws (1..19 observed agents) or
+ *   cavoid_policy_create_ws_crowd (20..64): one kernel serves both.
+ *   frozen (may be NULL): a loaded weight-sharing handle of either kind with the same max_other, input size and action count; it drives
+ *   the frozen-network agents by its argmax in a second pass on their rows (the first crowd launch that carries them).  values[] of those
+ *   rows then holds the frozen network's value (nothing reads it).
+ * CAVOID_EINVAL: cavoid_eval_run's cases -- null handles, buffers or record pointers, a wrong struct_size, n_steps < 0, a handle that is not
+ * loaded, handles that do not describe the same batch.  CAVOID_EUNSUPPORTED (evaluate step by step): an LSTM handle (cavoid_crowd_eval_run
+ * carries it), a handle of more than 64 observed agents, an env of <= 16 agents per world (cavoid_eval_run_ws carries those), holonomic
+ * dynamics, a `frozen` handle that is not a matching weight-sharing handle, an env whose generator makes frozen-network agents when `frozen`
+ * is NULL (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0), and a crowd env step whose LDS exceeds 65 536 bytes or the 66 560
+ * bytes of activation rows the pass lends it.  n_steps == 0: CAVOID_OK, nothing is launched or written. */
+int cavoid_crowd_eval_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_policy *frozen /* or NULL */, const cavoid_eval_buffers *buffers,
+                             float *obs, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps,
+                             int32_t greedy, void *stream);
+
 /* cavoid_step_autoreset + cavoid_rollout_push as ONE launch: the env step of every world and the Experience bookkeeping of its slots
  * (ProcessAgent.py:149-211) -- the fused actor's env phase for actors whose policy is a launch of its own (frozen-network agents,
  * a caller-supplied policy).  obs_cur [W,N,1+D]: the observation `actions` / `values` (V(s_t)) were computed on; the step writes the

@@ -7,7 +7,8 @@ Two paths produce the same numbers: the step-by-step loop (policy launch, ``env.
 step, one host synchronisation each) and, with ``fused=True``, ``cavoid_eval_run`` -- the whole loop per tile of worlds inside
 one launch of ``steps_per_launch`` steps that finished tiles leave early, the outcome recorded on the device (``fused_ws=True``:
 ``cavoid_eval_run_ws``, the same for the ``weight_sharing`` network; ``fused_crowd=True``: ``cavoid_crowd_eval_run``, the same for
-crowd worlds of 17 to 64 agents and the ``rnn`` network)."""
+crowd worlds of 17 to 64 agents and the ``rnn`` network; ``fused_crowd_ws=True``: ``cavoid_crowd_eval_run_ws``, crowd worlds and the
+``weight_sharing`` network)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -190,6 +191,42 @@ def evaluate_fused_crowd_unavailable_reason(env, policy, frozen_policy=None) -> 
     return None
 
 
+def evaluate_fused_crowd_ws_unavailable_reason(env, policy, frozen_policy=None) -> Optional[str]:
+    """Why ``evaluate(fused_crowd_ws=True)`` (``cavoid_crowd_eval_run_ws``: the evaluation loop of crowd worlds with the weight_sharing
+    network inside one launch) does not apply to this env and policy -- None when it does.  Host values only (no launch, no GPU), the
+    refusals of the C entry point one for one: a ``FusedPolicy`` of the ``weight_sharing`` network -- on the whole-row handle (up to
+    ``MAX_OTHERS_WS`` observed neighbours) or the ring handle (``ws_crowd=True``) alike -- worlds of 17..64 agents (tile worlds have
+    ``fused_ws=True``), table actions, a neighbour count that is the env's, a frozen policy that is a weight_sharing ``FusedPolicy`` of
+    the policy's shape for the frozen-network agents, and a crowd env step whose LDS fits the rows the pass lends it.  That last refusal
+    has no case here: ``cavoid_create`` admits no crowd env whose step takes more than that; the check stands for a library that does."""
+    from .rollout import WS_ACTOR_LENT_BYTES, crowd_env_step_lds_bytes
+    n = int(env.max_agents)
+    if not hasattr(policy, "act") or not hasattr(policy, "inference_form") or getattr(policy, "_h", None) is None:
+        return "the policy is not a FusedPolicy (a plain callable is evaluated step by step)"
+    if not getattr(policy, "ws", False):
+        return ("the policy is the %s network (use fused_crowd=True: cavoid_crowd_eval_run embeds the LSTM pass)" % (getattr(policy, "arch", "rnn"),))
+    if n <= _lib.TILE_MAX_AGENTS:
+        return ("%d agents per world: up to %d run the tile forms' weight_sharing evaluation kernel (fused_ws=True / cavoid_eval_run_ws)"
+                % (n, _lib.TILE_MAX_AGENTS))
+    if int(env.cfg.dynamics) == 2:
+        return "holonomic (velocity) actions"
+    if int(policy.max_others) != int(env.max_other):
+        return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy.max_others), int(env.max_other))
+    if frozen_policy is not None:
+        fz = frozen_policy
+        same_kind = getattr(fz, "_h", None) is not None and getattr(fz, "ws", False)
+        if not same_kind or int(fz.max_others) != int(policy.max_others) or int(getattr(fz, "num_actions", 0)) != int(getattr(policy, "num_actions", 0)):
+            return ("the frozen policy is not a weight_sharing FusedPolicy of the policy's shape (%s, %d neighbours; the policy: %d)"
+                    % (getattr(fz, "arch", "no FusedPolicy"), int(getattr(fz, "max_others", -1)), int(policy.max_others)))
+    elif float(env.cfg.gen_frozen_fraction) > 0.0 and float(env.cfg.gen_nonlearning_fraction) > 0.0:
+        return "frozen-network agents without a frozen_policy (they act by their own network)"
+    need = crowd_env_step_lds_bytes(n, 6 + 7 * int(env.max_other))
+    if need > min(65536, WS_ACTOR_LENT_BYTES):
+        return ("the crowd env step's LDS (%d bytes) does not fit the %d bytes the weight_sharing pass lends it"
+                % (need, min(65536, WS_ACTOR_LENT_BYTES)))
+    return None
+
+
 class _EvalRecords(object):
     """The device-side records of ``cavoid_eval_run`` for one env, and the per-step outputs it writes (``cavoid_eval_buffers``)."""
 
@@ -238,6 +275,15 @@ def eval_run_crowd(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec
                                                 env._stream()), "cavoid_crowd_eval_run")
 
 
+def eval_run_crowd_ws(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
+    """One ``cavoid_crowd_eval_run_ws`` launch (the evaluation kernel of crowd worlds with the weight_sharing network): ``eval_run_ws``'s
+    arguments and buffers."""
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(_lib.lib().cavoid_crowd_eval_run_ws(env._h, policy._h, frozen_policy._h if frozen_policy is not None else None, C.byref(rec.c),
+                                                   ptr(env.obs), ptr(env.rewards), ptr(env.done), ptr(env.game_over), ptr(rec.actions),
+                                                   ptr(rec.values), int(n_steps), 1 if greedy else 0, env._stream()), "cavoid_crowd_eval_run_ws")
+
+
 def _fused_round(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, launch: Callable, steps_per_launch: int, limit: int,
                  greedy: bool) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor]:
     """One round (the env has just been reset) as launches of ``launch`` (``eval_run`` or ``eval_run_ws``): the round's step count, the
@@ -278,7 +324,7 @@ def _settle_finished(env: BatchedCollisionAvoidanceEnv, world_steps: torch.Tenso
 @torch.no_grad()
 def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 1, greedy: bool = True,
              max_steps: Optional[int] = None, frozen_policy=None, fused: bool = False, steps_per_launch: int = 16,
-             details: bool = False, fused_ws: bool = False, fused_crowd: bool = False) -> Dict[str, float]:
+             details: bool = False, fused_ws: bool = False, fused_crowd: bool = False, fused_crowd_ws: bool = False) -> Dict[str, float]:
     """Run ``rounds`` batches of ``env.num_worlds`` episodes.  ``policy``: a ``FusedPolicy`` (its ``act`` is used) or any
     callable ``x [B, NN_INPUT_SIZE] -> (p [B, A], v [B])``.  Returns rates over the learning agents that took part.
 
@@ -290,24 +336,33 @@ def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 
     ``fused_ws=True`` is the same for a ``FusedPolicy`` of the ``weight_sharing`` network: ``cavoid_eval_run_ws``, the same launch loop
     and the same numbers (raises with ``evaluate_fused_ws_unavailable_reason``).  ``fused_crowd=True`` is the same for crowd worlds
     (17 to 64 agents per world) and the ``rnn`` network: ``cavoid_crowd_eval_run``, the ring form of the policy pass and the crowd env step
-    per tile (raises with ``evaluate_fused_crowd_unavailable_reason``; no ``frozen_policy``).  The three exclude each other; all are opt-in.
+    per tile (raises with ``evaluate_fused_crowd_unavailable_reason``; no ``frozen_policy``).  ``fused_crowd_ws=True`` is the same for crowd
+    worlds and a ``FusedPolicy`` of the ``weight_sharing`` network on either handle (1 to 63 observed neighbours): ``cavoid_crowd_eval_run_ws``,
+    the ring form of the weight_sharing pass on the tile's rows that still need an action and the crowd env step per tile, with a
+    ``frozen_policy`` of the same kind for frozen-network agents (raises with ``evaluate_fused_crowd_ws_unavailable_reason``).  The four
+    exclude each other; all are opt-in.  A sampled evaluation (``greedy=False``) of SEVERAL rounds on a fused path draws other numbers than
+    the step-by-step path from the second round on (every launch advances the policy's step counter, which keys the draw, by its whole
+    ``steps_per_launch``, the loop by the steps the round took), as on the other fused paths; one round draws the same.
     ``details=True`` adds ``extra_time_p75`` / ``_p90`` and ``per_agent`` (``reduce_outcomes``)."""
     rec, launch = None, None
     if fused and fused_ws:
         raise ValueError("evaluate: fused=True (cavoid_eval_run, the rnn network) and fused_ws=True (cavoid_eval_run_ws, weight_sharing) exclude each other")
     if fused_crowd and (fused or fused_ws):
         raise ValueError("evaluate: fused_crowd=True (cavoid_crowd_eval_run, crowd worlds) excludes fused=True and fused_ws=True (tile worlds)")
-    if fused or fused_ws or fused_crowd:
-        which = "fused_crowd" if fused_crowd else ("fused_ws" if fused_ws else "fused")
+    if fused_crowd_ws and (fused or fused_ws or fused_crowd):
+        raise ValueError("evaluate: fused_crowd_ws=True (cavoid_crowd_eval_run_ws, crowd worlds, weight_sharing) excludes fused=True, fused_ws=True "
+                         "and fused_crowd=True")
+    if fused or fused_ws or fused_crowd or fused_crowd_ws:
+        which = "fused_crowd_ws" if fused_crowd_ws else ("fused_crowd" if fused_crowd else ("fused_ws" if fused_ws else "fused"))
         reason = {"fused": evaluate_fused_unavailable_reason, "fused_ws": evaluate_fused_ws_unavailable_reason,
-                  "fused_crowd": evaluate_fused_crowd_unavailable_reason}[which]
+                  "fused_crowd": evaluate_fused_crowd_unavailable_reason, "fused_crowd_ws": evaluate_fused_crowd_ws_unavailable_reason}[which]
         why = reason(env, policy, frozen_policy)
         if why is not None:
             raise ValueError("evaluate(%s=True) does not apply: " % which + why)
         if int(steps_per_launch) < 1:
             raise ValueError("steps_per_launch must be >= 1")
         rec = _EvalRecords(env)
-        launch = {"fused": eval_run, "fused_ws": eval_run_ws, "fused_crowd": eval_run_crowd}[which]
+        launch = {"fused": eval_run, "fused_ws": eval_run_ws, "fused_crowd": eval_run_crowd, "fused_crowd_ws": eval_run_crowd_ws}[which]
     W, N = env.num_worlds, env.max_agents
     dt = float(env.cfg.dt)
     limit = max_steps if max_steps is not None else 100000

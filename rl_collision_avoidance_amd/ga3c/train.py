@@ -126,6 +126,14 @@ def main(argv=None) -> None:
                          "outcome record per tile of floor(64/N) worlds); same numbers.  The run ends if the configuration is one the kernel "
                          "does not carry (up to 16 agents per world, the weight_sharing network, frozen-network agents, holonomic dynamics, the "
                          "PyTorch policy).  Opt-in (profiles/crowd_eval_fused_timing.txt: tools/crowdevalbench.py)")
+    ap.add_argument("--fused-crowd-ws-evaluate", action="store_true",
+                    help="with --evaluate, --agents 17..64 and --arch weight_sharing: the same for crowd worlds and the weight_sharing network "
+                         "(1 to 63 observed neighbours; above 19 with --fused-crowd-ws) -- launches of --steps-per-graph env steps of "
+                         "cavoid_crowd_eval_run_ws (the ring form of the weight_sharing pass on the tile's rows that still need an action, argmax, "
+                         "the crowd env.step without auto-reset and the outcome record per tile of floor(64/N) worlds; --frozen-policy drives "
+                         "frozen-network agents in a second pass); same numbers.  The run ends if the configuration is one the kernel does not "
+                         "carry (up to 16 agents per world, the rnn network, holonomic dynamics, the PyTorch policy).  Opt-in "
+                         "(profiles/crowd_ws_eval_fused_timing.txt: tools/crowdwsevalbench.py)")
     ap.add_argument("--pretrain-steps", type=int, default=0,
                     help="supervised initialisation before RL (the role of Regression.py): Adam steps on teacher-driven rollouts")
     ap.add_argument("--fused-regression", action="store_true",
@@ -356,6 +364,19 @@ def main(argv=None) -> None:
             if rank == 0:
                 print("[Evaluate] fused crowd evaluation kernel (cavoid_crowd_eval_run), %d env steps per launch" % args.steps_per_graph, flush=True)
             res = evaluate(env, eval_policy, rounds=args.evaluate, fused_crowd=True, steps_per_launch=args.steps_per_graph)
+        elif args.fused_crowd_ws_evaluate:
+            from .evaluate import evaluate_fused_crowd_ws_unavailable_reason
+            why = evaluate_fused_crowd_ws_unavailable_reason(env, eval_policy, frozen)
+            if why is not None:
+                raise SystemExit("--fused-crowd-ws-evaluate: the fused crowd weight_sharing evaluation kernel (cavoid_crowd_eval_run_ws) does not "
+                                 "apply: " + why)
+            if args.steps_per_graph < 1:
+                raise SystemExit("--steps-per-graph must be >= 1")
+            if rank == 0:
+                print("[Evaluate] fused crowd weight_sharing evaluation kernel (cavoid_crowd_eval_run_ws), %d env steps per launch"
+                      % args.steps_per_graph, flush=True)
+            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused_crowd_ws=True,
+                           steps_per_launch=args.steps_per_graph)
         else:
             res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen)
         if rank == 0:
