@@ -419,11 +419,31 @@ int cavoid_actor_run_mix(cavoid_env *env, cavoid_policy *policy, cavoid_policy *
  * CAVOID_EINVAL: null or mismatching handles and buffers (cavoid_actor_run's checks).  CAVOID_EUNSUPPORTED (use the step-by-step entry
  * points): an env of <= 16 agents per world (cavoid_actor_run carries those), a weight-sharing handle (cavoid_crowd_actor_run_ws carries it), holonomic dynamics,
  * CAVOID_POLICY_F32 / a non-default CAVOID_POLICY_PRODUCTS (the bf16 product form included), and an env whose generator makes frozen-network
- * agents (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0: there is no _mix form of this launch; the refusal looks at the generator's
- * fractions only, as cavoid_actor_run's).  n_steps == 0: CAVOID_OK, nothing is launched. */
+ * agents (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0: this launch carries one network, cavoid_crowd_actor_run_mix carries the
+ * second; the refusal looks at the generator's fractions only, as cavoid_actor_run's).  n_steps == 0: CAVOID_OK, nothing is launched. */
 int cavoid_crowd_actor_run(cavoid_env *env, cavoid_policy *policy, cavoid_rollout *rollout, const cavoid_rollout_buffers *buffers,
                            float *obs_cur, float *obs_next, float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values,
                            int32_t n_steps, int32_t greedy, void *stream);
+
+/* cavoid_actor_run_mix for CROWD worlds (17..64 agents per world; cavoid_actor_run_mix refuses them, cavoid_crowd_actor_run refuses an env whose
+ * generator makes frozen-network agents): cavoid_crowd_actor_run's closed loop, K steps in one launch, with `frozen` = a second LSTM handle
+ * (same shapes, its own weights) that drives the CAVOID_POLICY_FROZEN_NET agents.  Per step, after the learner's pass, a tile that holds a
+ * RUNNING frozen-network agent (present, policy 4, no terminal flag in the state before this step -- what cavoid_policy_rows lists) runs the
+ * same ring pass once more on `frozen`'s weights and takes its ARGMAX for exactly those rows; values[] of those rows stays what the learner's
+ * pass left (0 for a row that needs no action).  Other tiles skip the second pass, and a tile without a row that needs the learner's action
+ * skips the first.  The argument list is cavoid_actor_run_mix's; buffers, counters, the rule for the rows that need an action, the ORCA
+ * routing and cavoid_last_step_form exactly as cavoid_crowd_actor_run.  Bit-identical to the step-by-step entry points
+ * (cavoid_rollout_active_rows, cavoid_policy_forward[_rows], cavoid_policy_rows + cavoid_policy_forward_rows on `frozen`, cavoid_step_push).
+ * An env whose generator makes no frozen-network agents is accepted: the second pass then never runs.
+ * CAVOID_EINVAL: null handles (`frozen` included), buffers or pointers, a wrong struct_size, n_steps < 0 -- looked at before n_steps == 0 --, a
+ * handle that is not loaded, handles that do not describe the same batch.  CAVOID_EUNSUPPORTED (use the step-by-step entry points): an env of
+ * <= 16 agents per world (cavoid_actor_run_mix carries those), a weight-sharing handle as `policy` or as `frozen`, CAVOID_POLICY_F32 / a
+ * non-default CAVOID_POLICY_PRODUCTS on either handle (the bf16 product form included), a `frozen` handle whose max_other, input size or action
+ * count differ from the policy's, a policy whose max_other is not the env's, holonomic dynamics, an env with scenario look-ahead rings, and a
+ * crowd env step whose LDS exceeds what cavoid_crowd_actor_run's launch allows.  n_steps == 0: CAVOID_OK, nothing is launched. */
+int cavoid_crowd_actor_run_mix(cavoid_env *env, cavoid_policy *policy, cavoid_policy *frozen, cavoid_rollout *rollout,
+                               const cavoid_rollout_buffers *buffers, float *obs_cur, float *obs_next, float *rewards, uint8_t *done,
+                               uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps, int32_t greedy, void *stream);
 
 /* cavoid_actor_run for the WEIGHT-SHARING network (cavoid_policy_create_ws; cavoid_actor_run, _run_mix and cavoid_crowd_actor_run refuse such a
  * handle): the same closed loop, K steps in one launch -- per tile of floor(64/N) worlds a workgroup runs the weight-sharing pass
@@ -541,10 +561,34 @@ int cavoid_eval_run_ws(cavoid_env *env, cavoid_policy *policy, cavoid_policy *fr
  * loaded, handles that do not describe the same batch.  CAVOID_EUNSUPPORTED (evaluate step by step): what cavoid_crowd_actor_run refuses -- an
  * env of <= 16 agents per world (cavoid_eval_run carries those), a weight-sharing handle, holonomic dynamics, CAVOID_POLICY_F32 / a
  * non-default CAVOID_POLICY_PRODUCTS (the bf16 product form included), an env whose generator makes frozen-network agents
- * (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0: one network per launch, there is no frozen form of this launch), and an env
+ * (gen_frozen_fraction > 0 with gen_nonlearning_fraction > 0: one network per launch; cavoid_crowd_eval_run_mix carries the second), and an env
  * step whose LDS exceeds what cavoid_crowd_actor_run's launch allows.  n_steps == 0: CAVOID_OK, nothing is launched or written. */
 int cavoid_crowd_eval_run(cavoid_env *env, cavoid_policy *policy, const cavoid_eval_buffers *buffers, float *obs, float *rewards,
                           uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps, int32_t greedy, void *stream);
+
+/* cavoid_crowd_eval_run with a FROZEN network: cavoid_eval_run's `frozen` argument for CROWD worlds (17..64 agents per world) -- the same
+ * evaluation loop, up to n_steps steps in one launch that finished tiles leave early, and per step, after the learner's pass, a tile that
+ * holds a RUNNING frozen-network agent (CAVOID_POLICY_FROZEN_NET, present, no terminal flag in the state before this step -- what
+ * cavoid_policy_rows lists) runs the same ring pass once more on `frozen`'s weights and takes its ARGMAX for exactly those rows.  The learner's
+ * pass is skipped while no row of the tile needs its action; the frozen pass runs all the same (with evaluate_mode a frozen-network agent can
+ * outlive every learner of its tile).  values[] is not written by the frozen pass.  The argument list is cavoid_eval_run's with `frozen`
+ * REQUIRED; `buffers` is cavoid_eval_run's struct, unchanged.  The records, the definition of "over", the return, the worlds_running protocol
+ * (zeroed on the stream by the call) and the step counter are exactly cavoid_eval_run's.  The return, as the blocks above define it: An
+ * agent's return sums the rewards up to and including the step
+ * at which its world is over.
+ * Trajectories are bit-identical to calling cavoid_policy_forward, cavoid_policy_rows + cavoid_policy_forward_rows on `frozen`, and
+ * cavoid_step per step.  ORCA routing and cavoid_last_step_form as cavoid_crowd_eval_run.  An env whose generator makes no frozen-network
+ * agents is accepted: the second pass then never runs.
+ * CAVOID_EINVAL: null handles (`frozen` included), buffers or record pointers, a wrong struct_size, n_steps < 0 -- looked at before
+ * n_steps == 0 --, a handle that is not loaded, handles that do not describe the same batch.  CAVOID_EUNSUPPORTED (evaluate step by step): an
+ * env of <= 16 agents per world (cavoid_eval_run carries those), a weight-sharing handle as `policy` or as `frozen` (cavoid_crowd_eval_run_ws
+ * carries those), CAVOID_POLICY_F32 / a non-default CAVOID_POLICY_PRODUCTS on either handle (the bf16 product form included), a `frozen`
+ * handle whose max_other, input size or action count differ from the policy's, a policy whose max_other is not the env's, holonomic
+ * dynamics, an env with scenario look-ahead rings, and an env step whose LDS exceeds what cavoid_crowd_actor_run's launch allows.
+ * n_steps == 0: CAVOID_OK, nothing is launched or written. */
+int cavoid_crowd_eval_run_mix(cavoid_env *env, cavoid_policy *policy, cavoid_policy *frozen, const cavoid_eval_buffers *buffers, float *obs,
+                              float *rewards, uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps,
+                              int32_t greedy, void *stream);
 
 /* cavoid_eval_run_ws for CROWD worlds (17..64 agents per world; cavoid_eval_run_ws refuses them): the evaluation loop of the WEIGHT-SHARING
  * network over the crowd step form, up to n_steps steps in one launch that finished tiles leave early -- per tile of floor(64/N) worlds (at

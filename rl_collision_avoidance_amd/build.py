@@ -21,7 +21,8 @@ SOURCES = [os.path.join(CSRC, "cavoid_capi.hip"), os.path.join(CSRC, "cavoid_mul
            os.path.join(CSRC, "cavoid_eval_rvo.hip"), os.path.join(CSRC, "cavoid_eval_frozen.hip"), os.path.join(CSRC, "cavoid_eval_ws.hip"),
            os.path.join(CSRC, "cavoid_eval_ws_rvo.hip"), os.path.join(CSRC, "cavoid_eval_ws_frozen.hip"),
            os.path.join(CSRC, "cavoid_crowd_eval.hip"), os.path.join(CSRC, "cavoid_crowd_actor_ws.hip"),
-           os.path.join(CSRC, "cavoid_crowd_eval_ws.hip")]
+           os.path.join(CSRC, "cavoid_crowd_eval_ws.hip"), os.path.join(CSRC, "cavoid_crowd_actor_mix.hip"),
+           os.path.join(CSRC, "cavoid_crowd_eval_mix.hip")]
 HEADERS = {
     "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp"],
     "cavoid_multistep.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
@@ -85,6 +86,14 @@ HEADERS = {
                                  "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp", "cavoid_actor.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp",
                                  "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_pipe.hpp", "cavoid_policy_host.hpp",
                                  "cavoid_rollout.hpp", "cavoid_host.hpp"],
+    "cavoid_crowd_actor_mix.hip": ["cavoid_crowd_actor_mix.hpp", "cavoid_crowd_actor.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp",
+                                   "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
+                                   "cavoid_policy_split.hpp", "cavoid_policy_pipe.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp",
+                                   "cavoid_rollout_host.hpp", "cavoid_host.hpp"],
+    "cavoid_crowd_eval_mix.hip": ["cavoid_crowd_eval_mix.hpp", "cavoid_crowd_actor_mix.hpp", "cavoid_crowd_eval.hpp", "cavoid_crowd_actor.hpp", "cavoid_crowd.hpp",
+                                  "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp", "cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_actor.hpp",
+                                  "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp",
+                                  "cavoid_policy_pipe.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
 }
 # per-file extra flags.  The multi-step env kernels run their step loop inside the launch; MachineLICM would hoist every
 # constant materialisation of the body (float64 polynomial coefficients, config scalars) out of that loop into
@@ -119,7 +128,10 @@ EXTRA_FLAGS = {"cavoid_multistep.hip": ["-mllvm", "-disable-machine-licm"], "cav
                "cavoid_crowd_actor_ws.hip": ["-mllvm", "-disable-machine-licm"],
                # crowd_ws_evaluate_kernel (cavoid_crowd_eval_ws.hpp): the ring-form weight-sharing pass + crowd env step + outcome record inside one
                # step loop, as cavoid_crowd_eval.hip
-               "cavoid_crowd_eval_ws.hip": ["-mllvm", "-disable-machine-licm"]}
+               "cavoid_crowd_eval_ws.hip": ["-mllvm", "-disable-machine-licm"],
+               # crowd_mix_rollout_kernel / crowd_mix_evaluate_kernel (cavoid_crowd_actor_mix.hpp, cavoid_crowd_eval_mix.hpp): crowd_actor_kernel's and
+               # crowd_evaluate_kernel's step loops with the frozen network's second pass inside
+               "cavoid_crowd_actor_mix.hip": ["-mllvm", "-disable-machine-licm"], "cavoid_crowd_eval_mix.hip": ["-mllvm", "-disable-machine-licm"]}
 STAMP_PATH = os.path.join(PKG_DIR, "libcavoid_hip.so.stamp")
 DEPS = SOURCES + [os.path.join(CSRC, h) for hs in HEADERS.values() for h in hs] + [os.path.join(ROOT, "include", "cavoid.h")]
 OBJ_DIR = os.path.join(PKG_DIR, "build")

@@ -8,7 +8,8 @@ step, one host synchronisation each) and, with ``fused=True``, ``cavoid_eval_run
 one launch of ``steps_per_launch`` steps that finished tiles leave early, the outcome recorded on the device (``fused_ws=True``:
 ``cavoid_eval_run_ws``, the same for the ``weight_sharing`` network; ``fused_crowd=True``: ``cavoid_crowd_eval_run``, the same for
 crowd worlds of 17 to 64 agents and the ``rnn`` network; ``fused_crowd_ws=True``: ``cavoid_crowd_eval_run_ws``, crowd worlds and the
-``weight_sharing`` network)."""
+``weight_sharing`` network; ``fused_crowd_mix=True``: ``cavoid_crowd_eval_run_mix``, crowd worlds, the ``rnn`` network and a second,
+frozen ``rnn`` network for the frozen-network agents)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -227,6 +228,47 @@ def evaluate_fused_crowd_ws_unavailable_reason(env, policy, frozen_policy=None) 
     return None
 
 
+def evaluate_fused_crowd_mix_unavailable_reason(env, policy, frozen_policy=None) -> Optional[str]:
+    """Why ``evaluate(fused_crowd_mix=True)`` (``cavoid_crowd_eval_run_mix``: the evaluation loop of crowd worlds with a second, frozen
+    network for the frozen-network agents inside one launch) does not apply to this env and the two policies -- None when it does.  Host
+    values only (no launch, no GPU), the refusals of the C entry point one for one: what ``evaluate_fused_crowd_unavailable_reason``
+    asks of the env and the policy, and a ``frozen_policy`` that is a ``FusedPolicy`` of the ``rnn`` network on the default inference form
+    with the policy's neighbour count and action count.  Without a ``frozen_policy`` the launch has nothing to add: ``fused_crowd=True``
+    is the one-network form.  The entry point's last refusal, an env step whose LDS exceeds what the policy pass lends it, has no case
+    here: ``cavoid_create`` admits no crowd env whose step takes more than that."""
+    n = int(env.max_agents)
+    if not hasattr(policy, "act") or not hasattr(policy, "inference_form") or getattr(policy, "_h", None) is None:
+        return "the policy is not a FusedPolicy (a plain callable is evaluated step by step)"
+    if n <= _lib.TILE_MAX_AGENTS:
+        return ("%d agents per world: up to %d run the tile forms' evaluation kernel (fused=True / cavoid_eval_run, with its frozen_policy)"
+                % (n, _lib.TILE_MAX_AGENTS))
+    if getattr(policy, "ws", False) or getattr(policy, "arch", "rnn") != "rnn":
+        return ("the policy is the %s network (the crowd mix evaluation kernel embeds the LSTM pass; fused_crowd_ws=True / "
+                "cavoid_crowd_eval_run_ws carries weight_sharing and its frozen_policy)" % (getattr(policy, "arch", "weight_sharing"),))
+    if int(env.cfg.dynamics) == 2:
+        return "holonomic (velocity) actions"
+    if tuple(policy.inference_form) != ("split", 16):
+        return "the policy runs a non-default inference form %r (CAVOID_POLICY_F32 / CAVOID_POLICY_PRODUCTS at its creation)" % (
+            tuple(policy.inference_form),)
+    if int(policy.max_others) != int(env.max_other):
+        return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy.max_others), int(env.max_other))
+    if frozen_policy is None:
+        return "no frozen_policy (fused_crowd=True / cavoid_crowd_eval_run is the one-network form of this launch)"
+    fz = frozen_policy
+    if not hasattr(fz, "inference_form") or getattr(fz, "_h", None) is None:
+        return "the frozen policy is not a FusedPolicy"
+    if getattr(fz, "ws", False) or getattr(fz, "arch", "rnn") != "rnn":
+        return "the frozen policy is the %s network (the crowd mix evaluation kernel embeds the LSTM pass twice)" % (getattr(fz, "arch", "weight_sharing"),)
+    if tuple(fz.inference_form) != ("split", 16):
+        return "the frozen policy runs a non-default inference form %r (CAVOID_POLICY_F32 / CAVOID_POLICY_PRODUCTS at its creation)" % (
+            tuple(fz.inference_form),)
+    if int(fz.max_others) != int(policy.max_others):
+        return "the frozen policy observes %d neighbours, the policy %d" % (int(fz.max_others), int(policy.max_others))
+    if int(getattr(fz, "num_actions", 0)) != int(getattr(policy, "num_actions", 0)):
+        return "the frozen policy has %d actions, the policy %d" % (int(getattr(fz, "num_actions", 0)), int(getattr(policy, "num_actions", 0)))
+    return None
+
+
 class _EvalRecords(object):
     """The device-side records of ``cavoid_eval_run`` for one env, and the per-step outputs it writes (``cavoid_eval_buffers``)."""
 
@@ -284,6 +326,17 @@ def eval_run_crowd_ws(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, 
                                                    ptr(rec.values), int(n_steps), 1 if greedy else 0, env._stream()), "cavoid_crowd_eval_run_ws")
 
 
+def eval_run_crowd_mix(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
+    """One ``cavoid_crowd_eval_run_mix`` launch (the evaluation kernel of crowd worlds with a second, frozen ``rnn`` network): ``eval_run``'s
+    arguments and buffers; ``frozen_policy`` is required."""
+    if frozen_policy is None:
+        raise ValueError("cavoid_crowd_eval_run_mix carries two networks: it needs a frozen_policy")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(_lib.lib().cavoid_crowd_eval_run_mix(env._h, policy._h, frozen_policy._h, C.byref(rec.c), ptr(env.obs), ptr(env.rewards),
+                                                    ptr(env.done), ptr(env.game_over), ptr(rec.actions), ptr(rec.values), int(n_steps),
+                                                    1 if greedy else 0, env._stream()), "cavoid_crowd_eval_run_mix")
+
+
 def _fused_round(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, launch: Callable, steps_per_launch: int, limit: int,
                  greedy: bool) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor]:
     """One round (the env has just been reset) as launches of ``launch`` (``eval_run`` or ``eval_run_ws``): the round's step count, the
@@ -324,7 +377,8 @@ def _settle_finished(env: BatchedCollisionAvoidanceEnv, world_steps: torch.Tenso
 @torch.no_grad()
 def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 1, greedy: bool = True,
              max_steps: Optional[int] = None, frozen_policy=None, fused: bool = False, steps_per_launch: int = 16,
-             details: bool = False, fused_ws: bool = False, fused_crowd: bool = False, fused_crowd_ws: bool = False) -> Dict[str, float]:
+             details: bool = False, fused_ws: bool = False, fused_crowd: bool = False, fused_crowd_mix: bool = False,
+             fused_crowd_ws: bool = False) -> Dict[str, float]:
     """Run ``rounds`` batches of ``env.num_worlds`` episodes.  ``policy``: a ``FusedPolicy`` (its ``act`` is used) or any
     callable ``x [B, NN_INPUT_SIZE] -> (p [B, A], v [B])``.  Returns rates over the learning agents that took part.
 
@@ -339,7 +393,10 @@ def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 
     per tile (raises with ``evaluate_fused_crowd_unavailable_reason``; no ``frozen_policy``).  ``fused_crowd_ws=True`` is the same for crowd
     worlds and a ``FusedPolicy`` of the ``weight_sharing`` network on either handle (1 to 63 observed neighbours): ``cavoid_crowd_eval_run_ws``,
     the ring form of the weight_sharing pass on the tile's rows that still need an action and the crowd env step per tile, with a
-    ``frozen_policy`` of the same kind for frozen-network agents (raises with ``evaluate_fused_crowd_ws_unavailable_reason``).  The four
+    ``frozen_policy`` of the same kind for frozen-network agents (raises with ``evaluate_fused_crowd_ws_unavailable_reason``).
+    ``fused_crowd_mix=True`` is ``fused_crowd=True`` with a ``frozen_policy`` (a ``FusedPolicy`` of the ``rnn`` network, required):
+    ``cavoid_crowd_eval_run_mix``, which runs the ring pass once more on the frozen network for the tile's running frozen-network agents
+    (raises with ``evaluate_fused_crowd_mix_unavailable_reason``).  The five
     exclude each other; all are opt-in.  A sampled evaluation (``greedy=False``) of SEVERAL rounds on a fused path draws other numbers than
     the step-by-step path from the second round on (every launch advances the policy's step counter, which keys the draw, by its whole
     ``steps_per_launch``, the loop by the steps the round took), as on the other fused paths; one round draws the same.
@@ -352,17 +409,23 @@ def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 
     if fused_crowd_ws and (fused or fused_ws or fused_crowd):
         raise ValueError("evaluate: fused_crowd_ws=True (cavoid_crowd_eval_run_ws, crowd worlds, weight_sharing) excludes fused=True, fused_ws=True "
                          "and fused_crowd=True")
-    if fused or fused_ws or fused_crowd or fused_crowd_ws:
-        which = "fused_crowd_ws" if fused_crowd_ws else ("fused_crowd" if fused_crowd else ("fused_ws" if fused_ws else "fused"))
+    if fused_crowd_mix and (fused or fused_ws or fused_crowd or fused_crowd_ws):
+        raise ValueError("evaluate: fused_crowd_mix=True (cavoid_crowd_eval_run_mix, crowd worlds, the rnn network and a frozen rnn network) excludes "
+                         "fused=True, fused_ws=True, fused_crowd=True and fused_crowd_ws=True")
+    if fused or fused_ws or fused_crowd or fused_crowd_ws or fused_crowd_mix:
+        which = ("fused_crowd_mix" if fused_crowd_mix else
+                 "fused_crowd_ws" if fused_crowd_ws else ("fused_crowd" if fused_crowd else ("fused_ws" if fused_ws else "fused")))
         reason = {"fused": evaluate_fused_unavailable_reason, "fused_ws": evaluate_fused_ws_unavailable_reason,
-                  "fused_crowd": evaluate_fused_crowd_unavailable_reason, "fused_crowd_ws": evaluate_fused_crowd_ws_unavailable_reason}[which]
+                  "fused_crowd": evaluate_fused_crowd_unavailable_reason, "fused_crowd_ws": evaluate_fused_crowd_ws_unavailable_reason,
+                  "fused_crowd_mix": evaluate_fused_crowd_mix_unavailable_reason}[which]
         why = reason(env, policy, frozen_policy)
         if why is not None:
             raise ValueError("evaluate(%s=True) does not apply: " % which + why)
         if int(steps_per_launch) < 1:
             raise ValueError("steps_per_launch must be >= 1")
         rec = _EvalRecords(env)
-        launch = {"fused": eval_run, "fused_ws": eval_run_ws, "fused_crowd": eval_run_crowd, "fused_crowd_ws": eval_run_crowd_ws}[which]
+        launch = {"fused": eval_run, "fused_ws": eval_run_ws, "fused_crowd": eval_run_crowd, "fused_crowd_ws": eval_run_crowd_ws,
+                  "fused_crowd_mix": eval_run_crowd_mix}[which]
     W, N = env.num_worlds, env.max_agents
     dt = float(env.cfg.dt)
     limit = max_steps if max_steps is not None else 100000

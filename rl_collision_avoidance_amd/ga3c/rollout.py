@@ -63,6 +63,44 @@ def crowd_actor_unavailable_reason(agents_per_world: int, dynamics: int, arch: s
     return None
 
 
+def crowd_actor_mix_unavailable_reason(agents_per_world: int, dynamics: int, arch: str, inference_form, policy_max_others: int,
+                                       env_max_other: int, frozen_arch: Optional[str], frozen_inference_form=("split", 16),
+                                       frozen_max_others: int = -1, fused_policy: bool = True, frozen_fused_policy: bool = True) -> Optional[str]:
+    """Why ``BatchedRollout.run_fused_crowd_mix`` (``cavoid_crowd_actor_run_mix``: the closed actor loop of crowd worlds with a second,
+    frozen network for the frozen-network agents, K steps in one launch) does not apply -- None when it does.  A pure function of host
+    values, the refusals of the C entry point: what ``crowd_actor_unavailable_reason`` asks of the env and the policy, and a frozen policy
+    (``frozen_arch`` None: there is none) that is a ``FusedPolicy`` of the ``rnn`` network on the default inference form with the policy's
+    neighbour count.  Whether the env's generator makes frozen-network agents does not matter: without them the second pass never runs."""
+    n = int(agents_per_world)
+    if not 1 <= n <= _lib.MAX_AGENTS:
+        raise ValueError("agents per world must be 1..%d" % _lib.MAX_AGENTS)
+    if n <= _lib.TILE_MAX_AGENTS:
+        return ("%d agents per world: up to %d run the tile forms' fused actor kernel (run_fused / cavoid_actor_run_mix)"
+                % (n, _lib.TILE_MAX_AGENTS))
+    if not fused_policy:
+        return "the policy is not a FusedPolicy"
+    if arch != "rnn":
+        return "the policy is the %s network (the crowd mix actor kernel embeds the LSTM pass; its kernel acts step by step)" % (arch,)
+    if int(dynamics) == 2:
+        return "holonomic (velocity) actions"
+    if tuple(inference_form) != ("split", 16):
+        return "the policy runs a non-default inference form %r (CAVOID_POLICY_F32 / CAVOID_POLICY_PRODUCTS at its creation)" % (tuple(inference_form),)
+    if int(policy_max_others) != int(env_max_other):
+        return "the policy observes %d neighbours, the env's rows carry %d" % (int(policy_max_others), int(env_max_other))
+    if frozen_arch is None:
+        return "no frozen_policy (run_fused_crowd / cavoid_crowd_actor_run is the one-network form of this launch)"
+    if not frozen_fused_policy:
+        return "the frozen-network agents' policy is not a FusedPolicy"
+    if frozen_arch != "rnn":
+        return "the frozen policy is the %s network (the crowd mix actor kernel embeds the LSTM pass twice)" % (frozen_arch,)
+    if tuple(frozen_inference_form) != ("split", 16):
+        return ("the frozen policy runs a non-default inference form %r (CAVOID_POLICY_F32 / CAVOID_POLICY_PRODUCTS at its creation)"
+                % (tuple(frozen_inference_form),))
+    if int(frozen_max_others) != int(policy_max_others):
+        return "the frozen policy observes %d neighbours, the policy %d" % (int(frozen_max_others), int(policy_max_others))
+    return None
+
+
 # what the weight-sharing pass lends the env step inside actor_ws_kernel: its 64 activation rows of kPolStride floats
 # (actor_ws_lent_bytes(), csrc/cavoid_actor_ws.hpp)
 WS_ACTOR_LENT_BYTES = 64 * 260 * 4
@@ -492,6 +530,59 @@ class BatchedRollout(object):
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             self.run_fused_crowd(steps_per_graph)
+        self.step_index -= steps_per_graph                # capture records, it does not execute
+        self._graph_steps = steps_per_graph
+
+    # -- the fused actor of crowd worlds with frozen-network agents (the training mix): opt-in, beside the step-by-step path ----------
+    @property
+    def crowd_mix_fused_unavailable_reason(self) -> Optional[str]:
+        """Why ``run_fused_crowd_mix`` does not apply to this rollout (None: it does) -- ``crowd_actor_mix_unavailable_reason`` on its values."""
+        cfg, pol, fz = self.env.cfg, self.policy, self.frozen_policy
+        return crowd_actor_mix_unavailable_reason(
+            self.env.max_agents, cfg.dynamics, getattr(pol, "arch", "rnn"), getattr(pol, "inference_form", ("split", 16)),
+            getattr(pol, "max_others", -1), cfg.max_other,
+            None if fz is None else getattr(fz, "arch", "rnn"), getattr(fz, "inference_form", ("split", 16)), getattr(fz, "max_others", -1),
+            fused_policy=bool(getattr(pol, "accepts_strided_obs", False)),
+            frozen_fused_policy=bool(getattr(fz, "accepts_strided_obs", False)))
+
+    @property
+    def crowd_mix_fused_available(self) -> bool:
+        """``run_fused_crowd_mix`` applies (``fused_available`` and ``crowd_fused_available`` stay False for crowd worlds with a frozen
+        policy: the default paths do not change)."""
+        return self.crowd_mix_fused_unavailable_reason is None
+
+    def run_fused_crowd_mix(self, n_steps: int) -> None:
+        """``run_fused_crowd`` with the frozen network: ``n_steps`` closed-loop steps of every world in ONE launch
+        (``cavoid_crowd_actor_run_mix``) -- per tile of floor(64/N) worlds a workgroup runs the policy on its own rows (the ring form), runs
+        the same pass once more on ``frozen_policy``'s weights where the tile holds a running frozen-network agent and takes its argmax for
+        those rows, steps its worlds and records the step.  Bit-identical to ``n_steps`` calls of ``step()``; capturable into a hipGraph."""
+        why = self.crowd_mix_fused_unavailable_reason
+        if why is not None:
+            raise RuntimeError("run_fused_crowd_mix does not apply: " + why)
+        env, pol = self.env, self.policy
+        b = self._actor_buffers()
+        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
+        p = BatchedCollisionAvoidanceEnv._ptr
+        _lib.check(self._lib.cavoid_crowd_actor_run_mix(env._h, pol._h, self.frozen_policy._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards),
+                                                        p(env.done), p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps),
+                                                        1 if self.greedy else 0, env._stream()), "cavoid_crowd_actor_run_mix")
+        self._cur = (self._cur + int(n_steps)) & 1
+        self.step_index += int(n_steps)
+
+    def capture_fused_crowd_mix(self, steps_per_graph: int = 4) -> None:
+        """``run_fused_crowd_mix(steps_per_graph)`` as a one-node hipGraph, as ``capture_fused_crowd``: an even step count (the two
+        observation buffers alternate), two warm-up steps outside the capture; ``replay`` serves it."""
+        if steps_per_graph < 2 or steps_per_graph % 2:
+            raise ValueError("steps_per_graph must be a positive even number")
+        side = torch.cuda.Stream(device=self.env.device)
+        side.wait_stream(torch.cuda.current_stream(self.env.device))
+        with torch.cuda.stream(side):
+            self.run_fused_crowd_mix(2)
+        torch.cuda.current_stream(self.env.device).wait_stream(side)
+        torch.cuda.synchronize(self.env.device)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self.run_fused_crowd_mix(steps_per_graph)
         self.step_index -= steps_per_graph                # capture records, it does not execute
         self._graph_steps = steps_per_graph
 

@@ -134,6 +134,13 @@ def main(argv=None) -> None:
                          "frozen-network agents in a second pass); same numbers.  The run ends if the configuration is one the kernel does not "
                          "carry (up to 16 agents per world, the rnn network, holonomic dynamics, the PyTorch policy).  Opt-in "
                          "(profiles/crowd_ws_eval_fused_timing.txt: tools/crowdwsevalbench.py)")
+    ap.add_argument("--fused-crowd-mix-evaluate", action="store_true",
+                    help="with --evaluate, --agents 17..64 and --frozen-fraction: --fused-crowd-evaluate for worlds with frozen-network agents -- "
+                         "launches of --steps-per-graph env steps of cavoid_crowd_eval_run_mix (the ring form of the policy pass, once more on the "
+                         "frozen network for the tile's running frozen-network agents, argmax, the crowd env.step without auto-reset and the "
+                         "outcome record per tile of floor(64/N) worlds); same numbers.  The run ends if the configuration is one the kernel "
+                         "does not carry (up to 16 agents per world, the weight_sharing network, no frozen network, holonomic dynamics, the "
+                         "PyTorch policy).  Opt-in (profiles/crowd_mix_timing.txt: tools/crowdmixbench.py)")
     ap.add_argument("--pretrain-steps", type=int, default=0,
                     help="supervised initialisation before RL (the role of Regression.py): Adam steps on teacher-driven rollouts")
     ap.add_argument("--fused-regression", action="store_true",
@@ -186,6 +193,13 @@ def main(argv=None) -> None:
                          "per phase in a hipGraph; the run ends if the configuration is one the kernel does not carry (frozen-network agents, "
                          "the weight_sharing network, the PyTorch policy).  Opt-in until a whole training run has been timed with and without it "
                          "(profiles/crowd_actor_timing.txt holds the actor loop alone: tools/crowdactorbench.py)")
+    ap.add_argument("--fused-crowd-mix-actor", action="store_true",
+                    help="--fused-crowd-actor for the training mix with frozen-network agents (--agents 17..64 --scripted-fraction S "
+                         "--frozen-fraction F): ONE launch per --steps-per-graph env steps of cavoid_crowd_actor_run_mix, which runs the policy "
+                         "pass once more on the frozen network for the tile's running frozen-network agents; the run ends if the configuration "
+                         "is one the kernel does not carry (no frozen network, the weight_sharing network, the PyTorch policy).  Opt-in until a "
+                         "whole training run has been timed with and without it (profiles/crowd_mix_timing.txt holds the actor loop alone: "
+                         "tools/crowdmixbench.py)")
     ap.add_argument("--fused-ws-actor", action="store_true",
                     help="run the actors of the weight_sharing network (--arch weight_sharing, up to 16 agents per world and 19 observed "
                          "neighbours) as ONE launch per --steps-per-graph env steps (cavoid_actor_run_ws: the weight_sharing pass, action draw, "
@@ -377,6 +391,19 @@ def main(argv=None) -> None:
                       % args.steps_per_graph, flush=True)
             res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused_crowd_ws=True,
                            steps_per_launch=args.steps_per_graph)
+        elif args.fused_crowd_mix_evaluate:
+            from .evaluate import evaluate_fused_crowd_mix_unavailable_reason
+            why = evaluate_fused_crowd_mix_unavailable_reason(env, eval_policy, frozen)
+            if why is not None:
+                raise SystemExit("--fused-crowd-mix-evaluate: the fused crowd evaluation kernel with a frozen network (cavoid_crowd_eval_run_mix) "
+                                 "does not apply: " + why)
+            if args.steps_per_graph < 1:
+                raise SystemExit("--steps-per-graph must be >= 1")
+            if rank == 0:
+                print("[Evaluate] fused crowd evaluation kernel (cavoid_crowd_eval_run_mix), %d env steps per launch" % args.steps_per_graph,
+                      flush=True)
+            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused_crowd_mix=True,
+                           steps_per_launch=args.steps_per_graph)
         else:
             res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen)
         if rank == 0:
@@ -427,6 +454,13 @@ def main(argv=None) -> None:
             raise SystemExit("--fused-crowd-actor: the crowd actor kernel (cavoid_crowd_actor_run) does not apply: " + why)
         roll.capture_fused_crowd(steps_per_graph=args.steps_per_graph)
         actors = "fused crowd actor kernel (cavoid_crowd_actor_run), %d env steps per launch" % args.steps_per_graph
+    elif args.fused_crowd_mix_actor:
+        why = roll.crowd_mix_fused_unavailable_reason
+        if why is not None:
+            raise SystemExit("--fused-crowd-mix-actor: the crowd actor kernel with a frozen network (cavoid_crowd_actor_run_mix) does not apply: " + why)
+        roll.capture_fused_crowd_mix(steps_per_graph=args.steps_per_graph)
+        actors = ("fused crowd actor kernel (cavoid_crowd_actor_run_mix: learner + frozen network), %d env steps per launch"
+                  % args.steps_per_graph)
     elif args.fused_ws_actor:
         why = roll.ws_fused_unavailable_reason
         if why is not None:
