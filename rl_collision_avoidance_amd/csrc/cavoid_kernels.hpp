@@ -379,7 +379,10 @@ __device__ __forceinline__ Ego ego_from(const KCfg &c, double tx, double ty, dou
     e.tx = tx;
     e.ty = ty;
     const double ss = e.tx * e.tx + e.ty * e.ty;
-    const bool tiny = !(ss > 1e-16);                                  // dist <= 1e-8: axes stay un-normalised
+    // dist <= 1e-8: axes stay un-normalised.  The oracle and ego_frame_exact compare the correctly rounded sqrt(ss) with 1e-8; the
+    // same predicate without the square root: 0x1.cd2b297d889bdp-54 is the largest float64 whose rounded square root is not above
+    // 1e-8 -- one ulp above the float64 1e-16, which is the side (1e-8)^2 itself falls on (tests/tie_regimes.py, P9)
+    const bool tiny = !(ss > 0x1.cd2b297d889bdp-54);
     double y = (double)__builtin_amdgcn_rsqf((float)ss);              // ~1e-7 relative
     y = y * __builtin_fma(-0.5 * ss, y * y, 1.5);                     // -> ~1e-14
     y = y * __builtin_fma(-0.5 * ss, y * y, 1.5);

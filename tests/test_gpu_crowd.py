@@ -245,7 +245,9 @@ def test_crowd_switches_follow_the_oracle(over):
 
 @pytest.mark.parametrize("sort", [0, 1, 2])
 def test_crowd_exact_ties_take_the_generic_rank_path(sort):
-    """tests/test_gpu_parity.py's mirrored pair, in a world of 20 (the other 16 agents absent): equal keys, the exact rule"""
+    """tests/test_gpu_parity.py's mirrored pair, in a world of 20 (the other 16 agents absent): equal keys, the exact rule.
+    (Ties of three, inside the M cut, of the float32 lateral alone, of the exact-gap keys, over the steps of one launch, and the threshold
+    predicates at equality, through every launch form of 17, 33 and 64 agents: tests/tie_regimes.py, tests/test_gpu_tie_regimes.py.)"""
     W, N = 40, 20
     ocfg = co.default_cfg(N, N - 1, sort_method=sort)
     env = _env(W, N, sort_method=sort)

@@ -674,7 +674,10 @@ def test_baseline_config0_two_agent_single_world_1000_steps():
 def test_exact_sort_ties_take_the_generic_rank_path(sort):
     """Two neighbours mirrored about the host's goal axis have the SAME centimetre bucket and the SAME lateral offset
     (ry*tx - rx*ty, bit for bit): the 63-bit tournament keys coincide and the kernel must fall back to the exact rule
-    (float64 lateral, then agent index -- what the oracle's stable sort does).  Worlds without ties share the tile."""
+    (float64 lateral, then agent index -- what the oracle's stable sort does).  Worlds without ties share the tile.
+    This is one pair in the plain one-step kernel; tests/tie_regimes.py holds the hand-placed ties (of three, inside the M cut, of the
+    float32 lateral alone, of the exact-gap keys, persisting and appearing inside a launch) and the threshold predicates at equality, and
+    tests/test_gpu_tie_regimes.py takes them through every launch form."""
     W, N = 40, 4
     ocfg, _ = _oracle(N, sort_method=sort)
     env = _env(W, N, sort_method=sort)
