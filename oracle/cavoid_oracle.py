@@ -283,7 +283,15 @@ def _det(ax: float, ay: float, bx: float, by: float) -> float:
     return ax * by - ay * bx
 
 
-def orca_lines(hi: int, agents: List["Agent"], cfg: "OracleConfig") -> List[Tuple[float, float, float, float]]:
+def _br(hook, name, cond):
+    """Every decision of the ORCA programmes passes through here.  ``hook(name, cond) -> bool`` may record it (a trace) or
+    return the opposite (a flip: tests/orca_regimes.py); without a hook the decision is ``cond`` itself and nothing in
+    the arithmetic or its order changes.  The two programmes share their code, so _lp_on_line / _lp_plane prefix their
+    names with "lp" (closest to the preferred velocity) or "dir" (the direction-optimising one of least penetration)."""
+    return cond if hook is None else hook(name, cond)
+
+
+def orca_lines(hi: int, agents: List["Agent"], cfg: "OracleConfig", hook=None) -> List[Tuple[float, float, float, float]]:
     """One line (point_x, point_y, dir_x, dir_y) per OTHER agent: velocities to the left of the line are admissible."""
     host = agents[hi]
     inv_h = 1.0 / cfg.rvo_time_horizon
@@ -296,11 +304,12 @@ def orca_lines(hi: int, agents: List["Agent"], cfg: "OracleConfig") -> List[Tupl
         dist_sq = rpx * rpx + rpy * rpy
         comb = cfg.rvo_radius_scale * host.radius + cfg.rvo_radius_scale * other.radius
         comb_sq = comb * comb
-        if dist_sq > comb_sq:                              # not touching: velocity obstacle truncated at the horizon
+        if _br(hook, "line.apart", dist_sq > comb_sq):     # not touching: velocity obstacle truncated at the horizon
             wx, wy = rvx - inv_h * rpx, rvy - inv_h * rpy
             w_sq = wx * wx + wy * wy
             dot1 = wx * rpx + wy * rpy
-            if dot1 < 0.0 and dot1 * dot1 > comb_sq * w_sq:   # closest point is on the cut-off circle
+            # closest point is on the cut-off circle
+            if _br(hook, "line.dot1_neg", dot1 < 0.0) and _br(hook, "line.cutoff", dot1 * dot1 > comb_sq * w_sq):
                 w_len = math.sqrt(w_sq)
                 ux, uy = wx / w_len, wy / w_len
                 dx, dy = uy, -ux
@@ -308,7 +317,7 @@ def orca_lines(hi: int, agents: List["Agent"], cfg: "OracleConfig") -> List[Tupl
                 ucx, ucy = scale * ux, scale * uy
             else:                                           # ... on one of the two legs
                 leg = math.sqrt(dist_sq - comb_sq)
-                if _det(rpx, rpy, wx, wy) > 0.0:
+                if _br(hook, "line.left_leg", _det(rpx, rpy, wx, wy) > 0.0):
                     dx, dy = (rpx * leg - rpy * comb) / dist_sq, (rpx * comb + rpy * leg) / dist_sq
                 else:
                     dx, dy = -(rpx * leg + rpy * comb) / dist_sq, -(-rpx * comb + rpy * leg) / dist_sq
@@ -326,12 +335,13 @@ def orca_lines(hi: int, agents: List["Agent"], cfg: "OracleConfig") -> List[Tupl
     return lines
 
 
-def _lp_on_line(lines, k: int, radius: float, ox: float, oy: float, direction_opt: bool):
+def _lp_on_line(lines, k: int, radius: float, ox: float, oy: float, direction_opt: bool, hook=None):
     """Optimise along line k inside the disc and the half-planes 0..k-1.  -> (ok, x, y)"""
     px, py, dx, dy = lines[k]
     dot = px * dx + py * dy
     disc = dot * dot + radius * radius - (px * px + py * py)
-    if disc < 0.0:
+    pre = "dir" if direction_opt else "lp"
+    if _br(hook, pre + ".disc_neg", disc < 0.0):
         return False, 0.0, 0.0
     root = math.sqrt(disc)
     t_lo, t_hi = -dot - root, -dot + root
@@ -339,54 +349,56 @@ def _lp_on_line(lines, k: int, radius: float, ox: float, oy: float, direction_op
         qx, qy, ex, ey = lines[i]
         den = _det(dx, dy, ex, ey)
         num = _det(ex, ey, px - qx, py - qy)
-        if abs(den) <= RVO_EPSILON:                        # parallel lines
-            if num < 0.0:
+        if _br(hook, pre + ".parallel", abs(den) <= RVO_EPSILON):     # parallel lines
+            if _br(hook, pre + ".parallel_out", num < 0.0):
                 return False, 0.0, 0.0
             continue
         t = num / den
-        if den >= 0.0:
+        if _br(hook, pre + ".den_pos", den >= 0.0):
             t_hi = min(t_hi, t)
         else:
             t_lo = max(t_lo, t)
-        if t_lo > t_hi:
+        if _br(hook, pre + ".empty", t_lo > t_hi):
             return False, 0.0, 0.0
     if direction_opt:
-        t = t_hi if ox * dx + oy * dy > 0.0 else t_lo
+        t = t_hi if _br(hook, "dir.forward", ox * dx + oy * dy > 0.0) else t_lo
     else:
         t = dx * (ox - px) + dy * (oy - py)
-        t = t_lo if t < t_lo else (t_hi if t > t_hi else t)
+        t = t_lo if _br(hook, "lp.clamp_lo", t < t_lo) else (t_hi if _br(hook, "lp.clamp_hi", t > t_hi) else t)
     return True, px + t * dx, py + t * dy
 
 
-def _lp_plane(lines, radius: float, ox: float, oy: float, direction_opt: bool):
+def _lp_plane(lines, radius: float, ox: float, oy: float, direction_opt: bool, hook=None):
     """-> (index of the first line that cannot be satisfied, or len(lines); x; y)"""
+    pre = "dir" if direction_opt else "lp"
     if direction_opt:
         x, y = ox * radius, oy * radius
-    elif ox * ox + oy * oy > radius * radius:
+    elif _br(hook, "lp.pref_outside", ox * ox + oy * oy > radius * radius):
         n = math.sqrt(ox * ox + oy * oy)
         x, y = ox / n * radius, oy / n * radius
     else:
         x, y = ox, oy
     for k, (px, py, dx, dy) in enumerate(lines):
-        if _det(dx, dy, px - x, py - y) > 0.0:             # current optimum violates half-plane k
-            ok, nx, ny = _lp_on_line(lines, k, radius, ox, oy, direction_opt)
-            if not ok:
+        # current optimum violates half-plane k
+        if _br(hook, pre + ".violated", _det(dx, dy, px - x, py - y) > 0.0):
+            ok, nx, ny = _lp_on_line(lines, k, radius, ox, oy, direction_opt, hook)
+            if _br(hook, pre + ".no_point", not ok):
                 return k, x, y
             x, y = nx, ny
     return len(lines), x, y
 
 
-def _lp_least_penetration(lines, begin: int, radius: float, x: float, y: float):
+def _lp_least_penetration(lines, begin: int, radius: float, x: float, y: float, hook=None):
     distance = 0.0
     for k in range(begin, len(lines)):
         px, py, dx, dy = lines[k]
-        if _det(dx, dy, px - x, py - y) > distance:
+        if _br(hook, "pen.deeper", _det(dx, dy, px - x, py - y) > distance):
             proj = []
             for j in range(k):
                 qx, qy, ex, ey = lines[j]
                 den = _det(dx, dy, ex, ey)
-                if abs(den) <= RVO_EPSILON:
-                    if dx * ex + dy * ey > 0.0:             # same direction: line j adds nothing
+                if _br(hook, "pen.parallel", abs(den) <= RVO_EPSILON):
+                    if _br(hook, "pen.same_dir", dx * ex + dy * ey > 0.0):             # same direction: line j adds nothing
                         continue
                     nx, ny = 0.5 * (px + qx), 0.5 * (py + qy)
                 else:
@@ -395,28 +407,28 @@ def _lp_least_penetration(lines, begin: int, radius: float, x: float, y: float):
                 fx, fy = ex - dx, ey - dy
                 fn = math.sqrt(fx * fx + fy * fy)
                 proj.append((nx, ny, fx / fn, fy / fn))
-            fail, nx, ny = _lp_plane(proj, radius, -dy, dx, True)
-            if fail >= len(proj):
+            fail, nx, ny = _lp_plane(proj, radius, -dy, dx, True, hook)
+            if _br(hook, "pen.solved", fail >= len(proj)):
                 x, y = nx, ny
             distance = _det(dx, dy, px - x, py - y)
     return x, y
 
 
-def rvo_action(hi: int, agents: List["Agent"], cfg: "OracleConfig") -> np.ndarray:
+def rvo_action(hi: int, agents: List["Agent"], cfg: "OracleConfig", hook=None) -> np.ndarray:
     """[speed, delta_heading] of an RVO agent: the ORCA velocity for one DT, turned into the unicycle action the env
     integrates; a turn beyond rvo_max_delta_heading is clipped and taken standing still."""
     host = agents[hi]
     gx, gy = host.goal[0] - host.pos[0], host.goal[1] - host.pos[1]
     gn = math.sqrt(gx * gx + gy * gy)
-    scale = host.pref_speed / gn if gn > 0.0 else 0.0
+    scale = host.pref_speed / gn if _br(hook, "act.off_goal", gn > 0.0) else 0.0
     pvx, pvy = scale * gx, scale * gy
-    lines = orca_lines(hi, agents, cfg)
-    fail, vx, vy = _lp_plane(lines, host.pref_speed, pvx, pvy, False)
-    if fail < len(lines):
-        vx, vy = _lp_least_penetration(lines, fail, host.pref_speed, vx, vy)
+    lines = orca_lines(hi, agents, cfg, hook)
+    fail, vx, vy = _lp_plane(lines, host.pref_speed, pvx, pvy, False, hook)
+    if _br(hook, "act.infeasible", fail < len(lines)):
+        vx, vy = _lp_least_penetration(lines, fail, host.pref_speed, vx, vy, hook)
     speed = math.sqrt(vx * vx + vy * vy)
-    delta = wrap(math.atan2(vy, vx) - host.heading, cfg.wrap_closed_end) if speed > 0.0 else 0.0
-    if abs(delta) > cfg.rvo_max_delta_heading:
+    delta = wrap(math.atan2(vy, vx) - host.heading, cfg.wrap_closed_end) if _br(hook, "act.moving", speed > 0.0) else 0.0
+    if _br(hook, "act.turn_clipped", abs(delta) > cfg.rvo_max_delta_heading):
         delta = math.copysign(cfg.rvo_max_delta_heading, delta)
         speed = 0.0
     return np.array([speed, delta])

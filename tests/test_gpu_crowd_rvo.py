@@ -32,12 +32,17 @@ MIX = dict(rvo_enabled=2, gen_rvo_fraction=0.6, gen_nonlearning_fraction=0.6, ge
 _BITWISE_CHILD = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, sys.argv[2])
-from tests.test_gpu_parity import _env
+from tests.test_gpu_parity import _env, _push
+from oracle import c_oracle as co
+from tests import orca_regimes as R
 # box scenarios generated inside the step, the training mix; ring scenarios (head-on traffic through a crowded centre): the programmes
 # without a solution, least penetration
 CONFIGS = [
     ("box", dict(rvo_enabled=2, gen_rvo_fraction=0.6, gen_nonlearning_fraction=0.6, gen_static_fraction=0.2, gen_min_agents=2, gen_mode=1, gen_pool_size=0)),
     ("ring", dict(rvo_enabled=2, gen_rvo_fraction=1.0, gen_nonlearning_fraction=0.7, gen_static_fraction=0.2, gen_min_agents=2, gen_mode=0, gen_pool_size=0)),
+    # the placed worlds of tests/orca_regimes.py (default group, the batch twice side by side), pushed after the reset, their own actions
+    # for their first steps: the parallel-line, mid-point and failed-projection branches that generator scenarios hardly reach
+    ("placed", None),
 ]
 def cat(*ts):
     return np.concatenate([t.cpu().numpy().ravel().view(np.uint8) for t in ts])
@@ -45,19 +50,34 @@ out = {}
 for tag, over in CONFIGS:
     for N in (4, 10, 15):
         W, seed = 300, 21
+        run, kw = None, over
+        if over is None:
+            run = R.Run.of("default", N)
+            W, seed, kw = 2 * run.W, R.SEED, R.over_of(run.group, 2)
         key = lambda name: "%s_%s%d" % (tag, name, N)
         rng = np.random.default_rng(N)
         acts = lambda *shape: torch.from_numpy(np.where(rng.random(shape) < 0.8, 2, rng.integers(0, 11, size=shape)).astype(np.int32)).cuda()
-        e = _env(W, N, seed=seed, **over)
+        e = _env(W, N, seed=seed, **kw)
         out[key("reset")] = cat(e.reset())
+        if run is not None:
+            e.seed(seed, torch.zeros(W, dtype=torch.int32, device=e.device))        # (the episode counters at 0: their sum counts restarts)
+            _push(e, co.State(np.tile(run.start.f64, 2), np.tile(run.start.f32, 2), np.tile(run.start.flags, 2)))
         orca = ((e.get_state()[2].cpu().numpy().view(np.uint32) >> 8) & 7) == 3
         out[key("orca_agents")] = np.array([int(orca.sum())])
         for t in range(40):
-            out[key("step%02d_" % t)] = cat(*e.step(acts(W, N)))
+            a = acts(W, N)
+            if run is not None and t < R.STEPS:
+                a = torch.from_numpy(np.tile(run.acts[t], (2, 1))).cuda()
+            out[key("step%02d_" % t)] = cat(*e.step(a))
             if t == 0:
                 out[key("form")] = np.array([ord(ch) for ch in e.last_step_form[0]])
+        if run is not None:                                 # (pushed again: the placed worlds end, and are restarted, inside the auto-reset steps)
+            _push(e, co.State(np.tile(run.start.f64, 2), np.tile(run.start.f32, 2), np.tile(run.start.flags, 2)))
         for t in range(40):
-            out[key("auto%02d_" % t)] = cat(*e.step_autoreset(acts(W, N)))
+            a = acts(W, N)
+            if run is not None and t < R.STEPS:
+                a = torch.from_numpy(np.tile(run.acts[t], (2, 1))).cuda()
+            out[key("auto%02d_" % t)] = cat(*e.step_autoreset(a))
         K = 17
         out[key("kstep")] = cat(*e.step_autoreset_n(acts(K, W, N), slots=e.new_step_slots(K)))
         pk, go = e.step_autoreset_packed(acts(5, W, N), e.new_step_slots(5, packed=True))
