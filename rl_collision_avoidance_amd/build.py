@@ -23,6 +23,13 @@ SOURCES = [os.path.join(CSRC, "cavoid_capi.hip"), os.path.join(CSRC, "cavoid_mul
            os.path.join(CSRC, "cavoid_crowd_eval.hip"), os.path.join(CSRC, "cavoid_crowd_actor_ws.hip"),
            os.path.join(CSRC, "cavoid_crowd_eval_ws.hip"), os.path.join(CSRC, "cavoid_crowd_actor_mix.hip"),
            os.path.join(CSRC, "cavoid_crowd_eval_mix.hip")]
+# every header cavoid_loop_host.hpp reaches (the host path of a step-loop launch, tile and crowd forms alike): part of each unit that
+# launches a step loop or cavoid_step_push, whichever kernel it instantiates
+LOOP_HOST = ["cavoid_loop_host.hpp", "cavoid_crowd_actor.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp", "cavoid_policy_pipe.hpp",
+             "cavoid_actor.hpp", "cavoid_eval.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp",
+             "cavoid_policy_host.hpp", "cavoid_rollout.hpp", "cavoid_rollout_host.hpp", "cavoid_host.hpp"]
+ACTOR_HOST = ["cavoid_actor_host.hpp"] + LOOP_HOST
+EVAL_HOST = ["cavoid_eval_host.hpp"] + LOOP_HOST
 HEADERS = {
     "cavoid_capi.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp"],
     "cavoid_multistep.hip": ["cavoid_kernels.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
@@ -33,67 +40,34 @@ HEADERS = {
     "cavoid_policy_capi.hip": ["cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_split8.hpp", "cavoid_policy_crowd.hpp", "cavoid_policy_host.hpp",
                                "cavoid_host.hpp"],
     "cavoid_policy_train_ring.hip": ["cavoid_policy.hpp", "cavoid_policy_train_ring.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
-    "cavoid_actor.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
-                         "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp", "cavoid_rollout_host.hpp", "cavoid_host.hpp"],
-    "cavoid_actor_rvo.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
-                             "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_actor_frozen.hip": ["cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
-                                "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
+    "cavoid_actor.hip": ACTOR_HOST,
+    "cavoid_actor_rvo.hip": ACTOR_HOST,
+    "cavoid_actor_frozen.hip": ACTOR_HOST,
     "cavoid_comm_capi.hip": ["cavoid_host.hpp"],
     "cavoid_crowd.hip": ["cavoid_kernels.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_launch.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_push.hip": ["cavoid_crowd_push.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp",
-                              "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_rvo.hip": ["cavoid_crowd_push.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp",
-                             "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_actor.hip": ["cavoid_crowd_actor.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp",
-                               "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp",
-                               "cavoid_host.hpp"],
+    "cavoid_crowd_push.hip": ["cavoid_crowd_push.hpp"] + ACTOR_HOST,
+    "cavoid_crowd_rvo.hip": ["cavoid_crowd_push.hpp"] + ACTOR_HOST,
+    "cavoid_crowd_actor.hip": ACTOR_HOST,
     "cavoid_policy_wsring.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp",
                                  "cavoid_host.hpp"],
     "cavoid_policy_ws.hip": ["cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
-    "cavoid_actor_ws.hip": ["cavoid_actor_ws.hpp", "cavoid_actor_ws_host.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp",
-                            "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp",
-                            "cavoid_rollout_host.hpp", "cavoid_host.hpp"],
-    "cavoid_actor_ws_rvo.hip": ["cavoid_actor_ws.hpp", "cavoid_actor_ws_host.hpp", "cavoid_actor.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp",
-                                "cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
+    "cavoid_actor_ws.hip": ["cavoid_actor_ws.hpp", "cavoid_actor_ws_host.hpp", "cavoid_policy_ws.hpp"] + ACTOR_HOST,
+    "cavoid_actor_ws_rvo.hip": ["cavoid_actor_ws.hpp", "cavoid_actor_ws_host.hpp", "cavoid_policy_ws.hpp"] + LOOP_HOST,
     "cavoid_policy_step.hip": ["cavoid_policy_step.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
     "cavoid_policy_step_ws.hip": ["cavoid_policy_step_ws.hpp", "cavoid_policy_step.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp",
                                   "cavoid_host.hpp"],
-    "cavoid_eval.hip": ["cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
-                        "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_host.hpp"],
-    "cavoid_eval_rvo.hip": ["cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
-                            "cavoid_policy_split.hpp", "cavoid_host.hpp"],
-    "cavoid_eval_frozen.hip": ["cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
-                               "cavoid_policy_split.hpp", "cavoid_host.hpp"],
-    "cavoid_eval_ws.hip": ["cavoid_eval_ws.hpp", "cavoid_eval_ws_host.hpp", "cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_actor_ws.hpp", "cavoid_actor.hpp",
-                           "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp",
-                           "cavoid_policy_host.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_eval_ws_rvo.hip": ["cavoid_eval_ws.hpp", "cavoid_eval_ws_host.hpp", "cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_actor_ws.hpp", "cavoid_actor.hpp",
-                               "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp",
-                               "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_eval_ws_frozen.hip": ["cavoid_eval_ws.hpp", "cavoid_eval_ws_host.hpp", "cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_actor_ws.hpp", "cavoid_actor.hpp",
-                                  "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_split.hpp",
-                                  "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_eval.hip": ["cavoid_crowd_eval.hpp", "cavoid_crowd_actor.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp",
-                              "cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_actor.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp",
-                              "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_actor_ws.hip": ["cavoid_crowd_actor_ws.hpp", "cavoid_crowd_actor.hpp", "cavoid_actor_ws.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp",
-                                  "cavoid_policy_crowd.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp", "cavoid_actor.hpp", "cavoid_actor_host.hpp",
-                                  "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp",
-                                  "cavoid_policy_pipe.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp", "cavoid_rollout_host.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_eval_ws.hip": ["cavoid_crowd_eval_ws.hpp", "cavoid_crowd_actor_ws.hpp", "cavoid_eval_ws.hpp", "cavoid_crowd_actor.hpp", "cavoid_actor_ws.hpp",
-                                 "cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp",
-                                 "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp", "cavoid_actor.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp",
-                                 "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp", "cavoid_policy_pipe.hpp", "cavoid_policy_host.hpp",
-                                 "cavoid_rollout.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_actor_mix.hip": ["cavoid_crowd_actor_mix.hpp", "cavoid_crowd_actor.hpp", "cavoid_crowd.hpp", "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp",
-                                   "cavoid_actor.hpp", "cavoid_actor_host.hpp", "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp",
-                                   "cavoid_policy_split.hpp", "cavoid_policy_pipe.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp",
-                                   "cavoid_rollout_host.hpp", "cavoid_host.hpp"],
-    "cavoid_crowd_eval_mix.hip": ["cavoid_crowd_eval_mix.hpp", "cavoid_crowd_actor_mix.hpp", "cavoid_crowd_eval.hpp", "cavoid_crowd_actor.hpp", "cavoid_crowd.hpp",
-                                  "cavoid_crowd_rvo.hpp", "cavoid_policy_crowd.hpp", "cavoid_eval.hpp", "cavoid_eval_host.hpp", "cavoid_actor.hpp",
-                                  "cavoid_kernels.hpp", "cavoid_quad.hpp", "cavoid_launch.hpp", "cavoid_policy.hpp", "cavoid_policy_split.hpp",
-                                  "cavoid_policy_pipe.hpp", "cavoid_policy_host.hpp", "cavoid_rollout.hpp", "cavoid_host.hpp"],
+    "cavoid_eval.hip": EVAL_HOST,
+    "cavoid_eval_rvo.hip": EVAL_HOST,
+    "cavoid_eval_frozen.hip": EVAL_HOST,
+    "cavoid_eval_ws.hip": ["cavoid_eval_ws.hpp", "cavoid_eval_ws_host.hpp", "cavoid_actor_ws.hpp", "cavoid_policy_ws.hpp"] + EVAL_HOST,
+    "cavoid_eval_ws_rvo.hip": ["cavoid_eval_ws.hpp", "cavoid_eval_ws_host.hpp", "cavoid_actor_ws.hpp", "cavoid_policy_ws.hpp"] + EVAL_HOST,
+    "cavoid_eval_ws_frozen.hip": ["cavoid_eval_ws.hpp", "cavoid_eval_ws_host.hpp", "cavoid_actor_ws.hpp", "cavoid_policy_ws.hpp"] + EVAL_HOST,
+    "cavoid_crowd_eval.hip": ["cavoid_crowd_eval.hpp"] + EVAL_HOST,
+    "cavoid_crowd_actor_ws.hip": ["cavoid_crowd_actor_ws.hpp", "cavoid_actor_ws.hpp", "cavoid_policy_ws.hpp", "cavoid_policy_wsring.hpp"] + ACTOR_HOST,
+    "cavoid_crowd_eval_ws.hip": ["cavoid_crowd_eval_ws.hpp", "cavoid_crowd_actor_ws.hpp", "cavoid_eval_ws.hpp", "cavoid_actor_ws.hpp", "cavoid_policy_ws.hpp",
+                                 "cavoid_policy_wsring.hpp"] + EVAL_HOST,
+    "cavoid_crowd_actor_mix.hip": ["cavoid_crowd_actor_mix.hpp"] + ACTOR_HOST,
+    "cavoid_crowd_eval_mix.hip": ["cavoid_crowd_eval_mix.hpp", "cavoid_crowd_actor_mix.hpp", "cavoid_crowd_eval.hpp"] + EVAL_HOST,
 }
 # per-file extra flags.  The multi-step env kernels run their step loop inside the launch; MachineLICM would hoist every
 # constant materialisation of the body (float64 polynomial coefficients, config scalars) out of that loop into

@@ -7,27 +7,15 @@
 #include "cavoid_actor.hpp"
 #include "cavoid_host.hpp"
 #include "cavoid_launch.hpp"
+#include "cavoid_loop_host.hpp"
 
 namespace cavoid {
 
 template <int N, bool RVO, bool FROZEN = false>
 static int launch_actor(cavoid_env *e, const SplitArgs &sa, const SplitArgs &fz, const RolloutCfg &rc, const RolloutState &rs, const RolloutIO &rio, const ActorIO &io,
                         hipStream_t s) {
-    // > 64 KiB of dynamic LDS: opted into once per instantiation AND device (the attribute belongs to the function on the current
-    // device; a process may drive several).  The flags are only ever set, and setting the attribute twice is harmless: no lock.
-    static bool opted_in[64] = {};
-    const int dev = e->device;
-    if (dev < 0 || dev >= 64 || !opted_in[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(actor_kernel<N, RVO, FROZEN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)policy_split_lds_bytes()));
-        if (dev >= 0 && dev < 64) opted_in[dev] = true;
-    }
-    const int64_t tiles = (e->W + e->k.wpw - 1) / e->k.wpw;
-    KCfg k = e->k;
-    k.stream_obs = 0;                                        // (the tile's own policy phase reads the rows next: they stay in the L2)
-    hipLaunchKernelGGL((actor_kernel<N, RVO, FROZEN>), dim3((unsigned)tiles), dim3(256), policy_split_lds_bytes(), s, k, e->st, e->pool, sa, fz, rc, rs, rio, io);
-    HIP_TRY(hipGetLastError());
-    return CAVOID_OK;
+    return launch_big_lds<actor_kernel<N, RVO, FROZEN>>(e->device, policy_split_lds_bytes(), loop_tile_count(e), s, loop_kcfg(e, /*stream_obs=*/false), e->st,
+                                                        e->pool, sa, fz, rc, rs, rio, io);
 }
 
 template <bool RVO, bool FROZEN = false>
@@ -39,9 +27,7 @@ static int launch_actor_any(cavoid_env *e, const SplitArgs &sa, const SplitArgs 
 template <int N, bool RVO>
 static int launch_step_push(cavoid_env *e, const RolloutCfg &rc, const RolloutState &rs, const RolloutIO &rio, const ActorIO &io, int32_t step, hipStream_t s) {
     const KCfg &k = e->k;
-    int tile = (k.tile_rows * k.width + 3) & ~3;
-    if (tile < k.park_floats) tile = k.park_floats;
-    const size_t lds = (size_t)(lds_floats_block() + e->waves_per_block * (lds_floats_fixed(e->cfg.max_agents) + k.rvo_lds_floats + tile)) * sizeof(float);
+    const size_t lds = (size_t)(lds_floats_block() + e->waves_per_block * (lds_floats_fixed(e->cfg.max_agents) + k.rvo_lds_floats + loop_tile_floats(k))) * sizeof(float);
     hipLaunchKernelGGL((step_push_kernel<N, RVO>), dim3((unsigned)e->grid, 2u), dim3(64 * e->waves_per_block), lds, s, k, e->st, e->pool, rc, rs, rio, io, step);
     HIP_TRY(hipGetLastError());
     return CAVOID_OK;

@@ -8,26 +8,15 @@
 #include "cavoid_actor_ws.hpp"
 #include "cavoid_host.hpp"
 #include "cavoid_launch.hpp"
+#include "cavoid_loop_host.hpp"
 
 namespace cavoid {
 
 template <int N, bool RVO>
 static int launch_actor_ws(cavoid_env *e, const PolicyWsArgs &wa, const RolloutCfg &rc, const RolloutState &rs, const RolloutIO &rio, const ActorIO &io,
                            hipStream_t s) {
-    // > 64 KiB of dynamic LDS: opted into once per instantiation AND device (as launch_actor, cavoid_actor_host.hpp)
-    static bool opted_in[64] = {};
-    const int dev = e->device;
-    if (dev < 0 || dev >= 64 || !opted_in[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(actor_ws_kernel<N, RVO>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)policy_lds_bytes(4)));
-        if (dev >= 0 && dev < 64) opted_in[dev] = true;
-    }
-    const int64_t tiles = (e->W + e->k.wpw - 1) / e->k.wpw;
-    KCfg k = e->k;
-    k.stream_obs = 0;                                        // (the tile's own policy phase reads the rows next: they stay in the L2)
-    hipLaunchKernelGGL((actor_ws_kernel<N, RVO>), dim3((unsigned)tiles), dim3(256), policy_lds_bytes(4), s, k, e->st, e->pool, wa, rc, rs, rio, io);
-    HIP_TRY(hipGetLastError());
-    return CAVOID_OK;
+    return launch_big_lds<actor_ws_kernel<N, RVO>>(e->device, policy_lds_bytes(4), loop_tile_count(e), s, loop_kcfg(e, /*stream_obs=*/false), e->st, e->pool, wa,
+                                                   rc, rs, rio, io);
 }
 
 template <bool RVO>

@@ -11,52 +11,24 @@
 
 using namespace cavoid;
 
-template <int NB, bool RVO, bool FROZEN>
-static int launch_crowd_ws_eval(cavoid_env *e, unsigned tiles, const PolicyWsArgs &wa, const PolicyWsArgs &fz, const EvalIO &io, hipStream_t s) {
-    // > 64 KiB of dynamic LDS: opted into once per instantiation and device (see launch_actor)
-    static bool opted_in[64] = {};
-    const int dev = e->device;
-    if (dev < 0 || dev >= 64 || !opted_in[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(crowd_ws_evaluate_kernel<NB, RVO, FROZEN>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)eval_ws_lds_bytes()));
-        if (dev >= 0 && dev < 64) opted_in[dev] = true;
-    }
-    KCfg k = e->k;
-    k.stream_obs = 0;                                        // (the tile's own policy phase reads the rows next: they stay in the L2)
-    hipLaunchKernelGGL((crowd_ws_evaluate_kernel<NB, RVO, FROZEN>), dim3(tiles), dim3(256), eval_ws_lds_bytes(), s, k, e->st, (const PoolRec *)e->pool,
-                       wa, fz, io, e->cfg.max_agents);
-    HIP_TRY(hipGetLastError());
-    return CAVOID_OK;
-}
-
 template <bool FROZEN>
 static int launch_crowd_ws_eval_any(cavoid_env *e, const PolicyWsArgs &wa, const PolicyWsArgs &fz, const EvalIO &io, hipStream_t s) {
-    const KCfg &k = e->k;
-    const int n = e->cfg.max_agents;
-    if (!crowd_form(n) || n < 2 || n > CAVOID_MAX_AGENTS) return CAVOID_EUNSUPPORTED;
-    const int64_t tiles = (e->W + k.wpw - 1) / k.wpw;
-    if (tiles < 1 || tiles > 0x7fffffffLL) return CAVOID_EINVAL;
     // the env step borrows the (idle) activation rows: crowd_kernel's allocation, at most 64 KB of the rows' 65 KB -- the row list and
     // EvalShared behind them survive it
-    const size_t lds = crowd_actor_env_lds_bytes(n, k.tile_rows, k.width);
-    if (lds > 65536 || lds > actor_ws_lent_bytes()) return CAVOID_EUNSUPPORTED;
+    unsigned tiles = 0;
+    if (int rc_t = crowd_loop_tiles(e, /*lent=*/actor_ws_lent_bytes(), /*refuse_ahead=*/false, &tiles)) return rc_t;
     // every tile ADDS its running worlds on leaving: the word starts from zero, on the stream
     HIP_TRY(hipMemsetAsync(io.worlds_running, 0, sizeof(int32_t), s));
-    // an env whose worlds may hold ORCA agents (cfg.rvo_enabled = CAVOID_RVO_WAVE): the ORCA-carrying env step, as cavoid_launch_crowd routes
-    if (k.rvo_enabled)
-        return n <= 32 ? launch_crowd_ws_eval<32, true, FROZEN>(e, (unsigned)tiles, wa, fz, io, s)
-                       : launch_crowd_ws_eval<64, true, FROZEN>(e, (unsigned)tiles, wa, fz, io, s);
-    return n <= 32 ? launch_crowd_ws_eval<32, false, FROZEN>(e, (unsigned)tiles, wa, fz, io, s)
-                   : launch_crowd_ws_eval<64, false, FROZEN>(e, (unsigned)tiles, wa, fz, io, s);
+    return dispatch_crowd_bucket(e->cfg.max_agents, e->k.rvo_enabled != 0, [&](auto nb, auto rvo) {
+        return launch_big_lds<crowd_ws_evaluate_kernel<decltype(nb)::value, decltype(rvo)::value, FROZEN>>(
+            e->device, eval_ws_lds_bytes(), tiles, s, loop_kcfg(e, /*stream_obs=*/false), e->st, (const PoolRec *)e->pool, wa, fz, io, e->cfg.max_agents);
+    });
 }
 
 extern "C" int cavoid_crowd_eval_run_ws(cavoid_env *e, cavoid_policy *h, cavoid_policy *frozen, const cavoid_eval_buffers *b, float *obs, float *rewards,
                                         uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps, int32_t greedy,
                                         void *stream) {
-    if (!e || !h || !b || b->struct_size != (int32_t)sizeof(cavoid_eval_buffers) || !obs || !rewards || !done || !game_over || !actions || !values ||
-        n_steps < 0)
-        return CAVOID_EINVAL;
-    if (!b->ret || !b->goal_step || !b->world_steps || !b->worlds_running) return CAVOID_EINVAL;
+    if (!eval_args_ok(e, h, b, obs, rewards, done, game_over, actions, values, n_steps)) return CAVOID_EINVAL;
     // the kernel embeds the weight-sharing pass in its ring form, which serves a cavoid_policy_create_ws handle (1..19 neighbours) and a
     // cavoid_policy_create_ws_crowd handle (20..64) alike: an LSTM handle has cavoid_crowd_eval_run
     if (!h->ws || h->max_other > kWsMaxOthersCrowd) return CAVOID_EUNSUPPORTED;
@@ -81,15 +53,10 @@ extern "C" int cavoid_crowd_eval_run_ws(cavoid_env *e, cavoid_policy *h, cavoid_
     // (no cavoid_ahead_prepare: nothing restarts)
 
     PolicyWsArgs wa{};
-    wa.a = policy_common_args(h, nullptr, e->A, e->k.width);   // (x: the observation buffer, set by the kernel)
-    wa.a.seed_lo = (uint32_t)h->seed; wa.a.seed_hi = (uint32_t)(h->seed >> 32);
-    wa.a.step_counter = h->step_counter; wa.a.blocks_done = h->blocks_done;
+    wa.a = loop_policy_args(e, h);
     PolicyWsArgs fz = wa;                                    // the frozen network: same shapes, its own weights / normalisation; argmax only
-    if (frozen) fz.a = policy_common_args(frozen, nullptr, e->A, e->k.width);
-    EvalIO io{};
-    io.obs = obs; io.rewards = rewards; io.done = done; io.game_over = game_over; io.actions = actions; io.values = values;
-    io.ret = b->ret; io.goal_step = b->goal_step; io.world_steps = b->world_steps; io.worlds_running = b->worlds_running;
-    io.n_steps = n_steps; io.greedy = greedy ? 1 : 0;
+    if (frozen) fz.a = frozen_ws_args(e, frozen);
+    const EvalIO io = eval_io(b, obs, rewards, done, game_over, actions, values, n_steps, greedy);
     e->last_form = CAVOID_FORM_NONE;
     const int rc_raw = frozen ? launch_crowd_ws_eval_any<true>(e, wa, fz, io, s) : launch_crowd_ws_eval_any<false>(e, wa, wa, io, s);
     const int rc_launch = note_form(e, rc_raw, crowd_step_form(e));     // (reported as after cavoid_step)

@@ -1,7 +1,6 @@
 // cavoid_eval_ws.hip -- C ABI (include/cavoid.h, cavoid_eval_run_ws) over eval_ws_kernel<N> (cavoid_eval_ws.hpp): K evaluation steps of the
 // weight-sharing network -- policy forward, action selection, env.step without auto-reset, outcome record -- in ONE launch that finished
 // tiles leave early.  Own translation unit (the kernel carries the weight-sharing pass and the env step; instantiated per agent count).
-#include <cstdlib>
 #include "cavoid_eval_ws_host.hpp"
 #include "cavoid_policy_host.hpp"
 
@@ -13,10 +12,7 @@ static bool whole_row_ws(const cavoid_policy *h) { return h->ws && !h->crowd && 
 
 extern "C" int cavoid_eval_run_ws(cavoid_env *e, cavoid_policy *h, cavoid_policy *frozen, const cavoid_eval_buffers *b, float *obs, float *rewards,
                                   uint8_t *done, uint8_t *game_over, int32_t *actions, float *values, int32_t n_steps, int32_t greedy, void *stream) {
-    if (!e || !h || !b || b->struct_size != (int32_t)sizeof(cavoid_eval_buffers) || !obs || !rewards || !done || !game_over || !actions || !values ||
-        n_steps < 0)
-        return CAVOID_EINVAL;
-    if (!b->ret || !b->goal_step || !b->world_steps || !b->worlds_running) return CAVOID_EINVAL;
+    if (!eval_args_ok(e, h, b, obs, rewards, done, game_over, actions, values, n_steps)) return CAVOID_EINVAL;
     if (!whole_row_ws(h) || (frozen && !whole_row_ws(frozen))) return CAVOID_EUNSUPPORTED;
     if (n_steps == 0) return CAVOID_OK;
     if (!h->loaded) return CAVOID_EINVAL;
@@ -30,31 +26,20 @@ extern "C" int cavoid_eval_run_ws(cavoid_env *e, cavoid_policy *h, cavoid_policy
     if (frozen && (!frozen->loaded || frozen->device != e->device || frozen->in_size != h->in_size || frozen->max_other != h->max_other ||
                    frozen->num_actions != h->num_actions))
         return frozen->loaded ? CAVOID_EUNSUPPORTED : CAVOID_EINVAL;
-    const KCfg &k = e->k;
-    const bool rvo_form = e->cfg.rvo_enabled || (e->cfg.gen_mode == 1 && e->pool_size <= 0);      // actor_run_ws's routing
-    int tile = (k.tile_rows * k.width + 3) & ~3;
-    if (tile < k.park_floats) tile = k.park_floats;
+    const bool rvo_form = loop_rvo_form(e);                   // actor_run_ws's routing
     // the env step borrows the (idle) activation rows: staging arrays + obs tile (+ the ORCA lines)
-    if (eval_env_lds_bytes(e->cfg.max_agents, tile, k.rvo_lds_floats) > actor_ws_lent_bytes()) return CAVOID_EUNSUPPORTED;
+    const size_t lent = actor_ws_lent_bytes();
+    if (eval_env_lds_bytes(e->cfg.max_agents, loop_tile_floats(e->k), e->k.rvo_lds_floats) > lent) return CAVOID_EUNSUPPORTED;
     HIP_TRY(hipSetDevice(e->device));
     // (no cavoid_ahead_prepare: nothing restarts)
     hipStream_t s = static_cast<hipStream_t>(stream);
 
     PolicyWsArgs wa{};
-    wa.a = policy_common_args(h, nullptr, e->A, k.width);   // (x: the observation buffer, set by the kernel)
-    wa.a.seed_lo = (uint32_t)h->seed; wa.a.seed_hi = (uint32_t)(h->seed >> 32);
-    wa.a.step_counter = h->step_counter; wa.a.blocks_done = h->blocks_done;
+    wa.a = loop_policy_args(e, h);
     PolicyWsArgs fz = wa;                                    // the frozen network: same shapes, its own weights / normalisation; argmax only
-    if (frozen) fz.a = policy_common_args(frozen, nullptr, e->A, k.width);
-    EvalIO io{};
-    io.obs = obs; io.rewards = rewards; io.done = done; io.game_over = game_over; io.actions = actions; io.values = values;
-    io.ret = b->ret; io.goal_step = b->goal_step; io.world_steps = b->world_steps; io.worlds_running = b->worlds_running;
-    io.n_steps = n_steps; io.greedy = greedy ? 1 : 0;
-    // the tile's env step over the workgroup's four wavefronts where cavoid_actor_run_ws takes that form -- its LDS inside the lent rows
-    // (CAVOID_ACTOR_QUAD=0: wavefront 0 alone)
-    io.quad = (!rvo_form && e->cfg.max_agents <= kEvalQuadMaxAgents && k.tile_rows >= k.wpw * e->cfg.max_agents &&
-               quad_lds_bytes<kEvalQuadMaxAgents>((k.tile_rows * k.width + 3) & ~3) <= actor_ws_lent_bytes()) ? 1 : 0;
-    if (const char *ov = std::getenv("CAVOID_ACTOR_QUAD")) io.quad = (io.quad && std::atoi(ov) != 0) ? 1 : 0;
+    if (frozen) fz.a = frozen_ws_args(e, frozen);
+    EvalIO io = eval_io(b, obs, rewards, done, game_over, actions, values, n_steps, greedy);
+    io.quad = quad_form<kEvalQuadMaxAgents>(e, rvo_form, lent);      // (where cavoid_actor_run_ws takes that form, inside the lent rows)
     // every tile ADDS its running worlds on leaving: the word starts from zero, on the stream
     HIP_TRY(hipMemsetAsync(b->worlds_running, 0, sizeof(int32_t), s));
     const int rc_launch = frozen ? cavoid_launch_eval_ws_frozen(e, wa, fz, io, s)

@@ -9,25 +9,14 @@
 #include "cavoid_eval_ws.hpp"
 #include "cavoid_host.hpp"
 #include "cavoid_launch.hpp"
+#include "cavoid_loop_host.hpp"
 
 namespace cavoid {
 
 template <int N, bool RVO, bool FROZEN = false>
 static int launch_eval_ws(cavoid_env *e, const PolicyWsArgs &wa, const PolicyWsArgs &fz, const EvalIO &io, hipStream_t s) {
-    // > 64 KiB of dynamic LDS: opted into once per instantiation AND device (as launch_eval, cavoid_eval_host.hpp)
-    static bool opted_in[64] = {};
-    const int dev = e->device;
-    if (dev < 0 || dev >= 64 || !opted_in[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_ws_kernel<N, RVO, FROZEN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)eval_ws_lds_bytes()));
-        if (dev >= 0 && dev < 64) opted_in[dev] = true;
-    }
-    const int64_t tiles = (e->W + e->k.wpw - 1) / e->k.wpw;
-    KCfg k = e->k;
-    k.stream_obs = 0;                                        // (the tile's own policy phase reads the rows next: they stay in the L2)
-    hipLaunchKernelGGL((eval_ws_kernel<N, RVO, FROZEN>), dim3((unsigned)tiles), dim3(256), eval_ws_lds_bytes(), s, k, e->st, e->pool, wa, fz, io);
-    HIP_TRY(hipGetLastError());
-    return CAVOID_OK;
+    return launch_big_lds<eval_ws_kernel<N, RVO, FROZEN>>(e->device, eval_ws_lds_bytes(), loop_tile_count(e), s, loop_kcfg(e, /*stream_obs=*/false), e->st, e->pool,
+                                                          wa, fz, io);
 }
 
 template <bool RVO, bool FROZEN = false>

@@ -290,20 +290,24 @@ class _EvalRecords(object):
         self.ret.zero_(); self.goal_step.zero_(); self.world_steps.zero_()
 
 
+def _eval_launch(symbol: str, frozen: str, env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool) -> None:
+    """One launch of the library's evaluation entry point ``symbol`` on the env's own output buffers (``env.obs`` holds the current
+    observation).  ``frozen``: the entry point takes the frozen network's handle, which may be None ("optional"), takes it and needs one
+    ("required"), or carries one network and has no such argument ("none")."""
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    handles = (env._h, policy._h) + (() if frozen == "none" else (frozen_policy._h if frozen_policy is not None else None,))
+    _lib.check(getattr(_lib.lib(), symbol)(*handles, C.byref(rec.c), ptr(env.obs), ptr(env.rewards), ptr(env.done), ptr(env.game_over), ptr(rec.actions),
+                                           ptr(rec.values), int(n_steps), 1 if greedy else 0, env._stream()), symbol)
+
+
 def eval_run(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
     """One ``cavoid_eval_run`` launch on the env's own output buffers (``env.obs`` holds the current observation)."""
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    _lib.check(_lib.lib().cavoid_eval_run(env._h, policy._h, frozen_policy._h if frozen_policy is not None else None, C.byref(rec.c),
-                                          ptr(env.obs), ptr(env.rewards), ptr(env.done), ptr(env.game_over), ptr(rec.actions), ptr(rec.values),
-                                          int(n_steps), 1 if greedy else 0, env._stream()), "cavoid_eval_run")
+    _eval_launch("cavoid_eval_run", "optional", env, policy, frozen_policy, rec, n_steps, greedy)
 
 
 def eval_run_ws(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
     """One ``cavoid_eval_run_ws`` launch (the weight_sharing network's evaluation kernel): ``eval_run``'s arguments and buffers."""
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    _lib.check(_lib.lib().cavoid_eval_run_ws(env._h, policy._h, frozen_policy._h if frozen_policy is not None else None, C.byref(rec.c),
-                                             ptr(env.obs), ptr(env.rewards), ptr(env.done), ptr(env.game_over), ptr(rec.actions), ptr(rec.values),
-                                             int(n_steps), 1 if greedy else 0, env._stream()), "cavoid_eval_run_ws")
+    _eval_launch("cavoid_eval_run_ws", "optional", env, policy, frozen_policy, rec, n_steps, greedy)
 
 
 def eval_run_crowd(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
@@ -311,19 +315,13 @@ def eval_run_crowd(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec
     carries one network, so ``frozen_policy`` must be None."""
     if frozen_policy is not None:
         raise ValueError("cavoid_crowd_eval_run carries one network: no frozen_policy")
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    _lib.check(_lib.lib().cavoid_crowd_eval_run(env._h, policy._h, C.byref(rec.c), ptr(env.obs), ptr(env.rewards), ptr(env.done),
-                                                ptr(env.game_over), ptr(rec.actions), ptr(rec.values), int(n_steps), 1 if greedy else 0,
-                                                env._stream()), "cavoid_crowd_eval_run")
+    _eval_launch("cavoid_crowd_eval_run", "none", env, policy, None, rec, n_steps, greedy)
 
 
 def eval_run_crowd_ws(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
     """One ``cavoid_crowd_eval_run_ws`` launch (the evaluation kernel of crowd worlds with the weight_sharing network): ``eval_run_ws``'s
     arguments and buffers."""
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    _lib.check(_lib.lib().cavoid_crowd_eval_run_ws(env._h, policy._h, frozen_policy._h if frozen_policy is not None else None, C.byref(rec.c),
-                                                   ptr(env.obs), ptr(env.rewards), ptr(env.done), ptr(env.game_over), ptr(rec.actions),
-                                                   ptr(rec.values), int(n_steps), 1 if greedy else 0, env._stream()), "cavoid_crowd_eval_run_ws")
+    _eval_launch("cavoid_crowd_eval_run_ws", "optional", env, policy, frozen_policy, rec, n_steps, greedy)
 
 
 def eval_run_crowd_mix(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, n_steps: int, greedy: bool = True) -> None:
@@ -331,10 +329,17 @@ def eval_run_crowd_mix(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy,
     arguments and buffers; ``frozen_policy`` is required."""
     if frozen_policy is None:
         raise ValueError("cavoid_crowd_eval_run_mix carries two networks: it needs a frozen_policy")
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    _lib.check(_lib.lib().cavoid_crowd_eval_run_mix(env._h, policy._h, frozen_policy._h, C.byref(rec.c), ptr(env.obs), ptr(env.rewards),
-                                                    ptr(env.done), ptr(env.game_over), ptr(rec.actions), ptr(rec.values), int(n_steps),
-                                                    1 if greedy else 0, env._stream()), "cavoid_crowd_eval_run_mix")
+    _eval_launch("cavoid_crowd_eval_run_mix", "required", env, policy, frozen_policy, rec, n_steps, greedy)
+
+
+def _fused_switches():
+    """The fused forms of ``evaluate``: (switch name, reason function, launch).  Read at each call, so that the module's current
+    ``eval_run*`` and reason functions are the ones used."""
+    return (("fused", evaluate_fused_unavailable_reason, eval_run),
+            ("fused_ws", evaluate_fused_ws_unavailable_reason, eval_run_ws),
+            ("fused_crowd", evaluate_fused_crowd_unavailable_reason, eval_run_crowd),
+            ("fused_crowd_ws", evaluate_fused_crowd_ws_unavailable_reason, eval_run_crowd_ws),
+            ("fused_crowd_mix", evaluate_fused_crowd_mix_unavailable_reason, eval_run_crowd_mix))
 
 
 def _fused_round(env: BatchedCollisionAvoidanceEnv, policy, frozen_policy, rec: _EvalRecords, launch: Callable, steps_per_launch: int, limit: int,
@@ -402,30 +407,18 @@ def evaluate(env: BatchedCollisionAvoidanceEnv, policy: Callable, rounds: int = 
     ``steps_per_launch``, the loop by the steps the round took), as on the other fused paths; one round draws the same.
     ``details=True`` adds ``extra_time_p75`` / ``_p90`` and ``per_agent`` (``reduce_outcomes``)."""
     rec, launch = None, None
-    if fused and fused_ws:
-        raise ValueError("evaluate: fused=True (cavoid_eval_run, the rnn network) and fused_ws=True (cavoid_eval_run_ws, weight_sharing) exclude each other")
-    if fused_crowd and (fused or fused_ws):
-        raise ValueError("evaluate: fused_crowd=True (cavoid_crowd_eval_run, crowd worlds) excludes fused=True and fused_ws=True (tile worlds)")
-    if fused_crowd_ws and (fused or fused_ws or fused_crowd):
-        raise ValueError("evaluate: fused_crowd_ws=True (cavoid_crowd_eval_run_ws, crowd worlds, weight_sharing) excludes fused=True, fused_ws=True "
-                         "and fused_crowd=True")
-    if fused_crowd_mix and (fused or fused_ws or fused_crowd or fused_crowd_ws):
-        raise ValueError("evaluate: fused_crowd_mix=True (cavoid_crowd_eval_run_mix, crowd worlds, the rnn network and a frozen rnn network) excludes "
-                         "fused=True, fused_ws=True, fused_crowd=True and fused_crowd_ws=True")
-    if fused or fused_ws or fused_crowd or fused_crowd_ws or fused_crowd_mix:
-        which = ("fused_crowd_mix" if fused_crowd_mix else
-                 "fused_crowd_ws" if fused_crowd_ws else ("fused_crowd" if fused_crowd else ("fused_ws" if fused_ws else "fused")))
-        reason = {"fused": evaluate_fused_unavailable_reason, "fused_ws": evaluate_fused_ws_unavailable_reason,
-                  "fused_crowd": evaluate_fused_crowd_unavailable_reason, "fused_crowd_ws": evaluate_fused_crowd_ws_unavailable_reason,
-                  "fused_crowd_mix": evaluate_fused_crowd_mix_unavailable_reason}[which]
+    wanted = {"fused": fused, "fused_ws": fused_ws, "fused_crowd": fused_crowd, "fused_crowd_ws": fused_crowd_ws, "fused_crowd_mix": fused_crowd_mix}
+    on = [row for row in _fused_switches() if wanted[row[0]]]
+    if len(on) > 1:
+        raise ValueError("evaluate: " + " and ".join("%s=True" % row[0] for row in on) + " exclude each other (each is one launch form of the round)")
+    if on:
+        which, reason, launch = on[0]
         why = reason(env, policy, frozen_policy)
         if why is not None:
             raise ValueError("evaluate(%s=True) does not apply: " % which + why)
         if int(steps_per_launch) < 1:
             raise ValueError("steps_per_launch must be >= 1")
         rec = _EvalRecords(env)
-        launch = {"fused": eval_run, "fused_ws": eval_run_ws, "fused_crowd": eval_run_crowd, "fused_crowd_ws": eval_run_crowd_ws,
-                  "fused_crowd_mix": eval_run_crowd_mix}[which]
     W, N = env.num_worlds, env.max_agents
     dt = float(env.cfg.dt)
     limit = max_steps if max_steps is not None else 100000

@@ -445,43 +445,53 @@ class BatchedRollout(object):
             self._bufs = b
         return self._bufs
 
+    def _run_fused_on(self, symbol: str, n_steps: int, why: Optional[str], frozen: bool = False) -> None:
+        """``n_steps`` closed-loop steps of every world in one launch of the library's ``symbol`` (every fused actor entry point takes the
+        same arguments; ``frozen``: ``frozen_policy``'s handle follows the policy's).  ``why``: the RuntimeError text of a rollout the
+        launch does not apply to (None: it applies) -- raised before anything touches a device."""
+        if why is not None:
+            raise RuntimeError(why)
+        env = self.env
+        b = self._actor_buffers()
+        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
+        p = BatchedCollisionAvoidanceEnv._ptr
+        handles = (env._h, self.policy._h) + ((self.frozen_policy._h,) if frozen else ()) + (self._h,)
+        _lib.check(getattr(self._lib, symbol)(*handles, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done), p(env.game_over), p(self._act_out),
+                                              p(self._val_out), int(n_steps), 1 if self.greedy else 0, env._stream()), symbol)
+        self._cur = (self._cur + int(n_steps)) & 1
+        self.step_index += int(n_steps)
+
+    def _capture_steps(self, run, steps_per_graph: int, needs_policy: bool = False) -> None:
+        """``run(steps_per_graph)`` as one hipGraph that ``replay`` serves: an even step count (the two observation buffers alternate) and
+        two warm-up steps on a side stream outside the capture (allocator, lazy inits)."""
+        if steps_per_graph < 2 or steps_per_graph % 2:
+            raise ValueError("steps_per_graph must be a positive even number")
+        if needs_policy and self.policy is None:
+            raise ValueError("capture() needs a policy")
+        side = torch.cuda.Stream(device=self.env.device)
+        side.wait_stream(torch.cuda.current_stream(self.env.device))
+        with torch.cuda.stream(side):
+            run(2)
+        torch.cuda.current_stream(self.env.device).wait_stream(side)
+        torch.cuda.synchronize(self.env.device)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            run(steps_per_graph)
+        self.step_index -= steps_per_graph                # capture records, it does not execute
+        self._graph_steps = steps_per_graph
+
     def run_fused(self, n_steps: int) -> None:
         """``n_steps`` closed-loop steps of every world -- predict, select_action, env.step, Experience bookkeeping
         (ProcessAgent.py:116-211) -- in ONE launch (``cavoid_actor_run``): per tile of worlds a workgroup runs the policy
         on its own rows, steps its own worlds and records the step, with no kernel boundary and no host in between.
         Bit-identical to ``n_steps`` calls of ``step()``; capturable into a hipGraph."""
-        if not self.fused_available:
-            raise RuntimeError("run_fused needs a FusedPolicy and a configuration the fused kernel carries (see fused_available)")
-        env, pol = self.env, self.policy
-        b = self._actor_buffers()
-        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
-        p = BatchedCollisionAvoidanceEnv._ptr
-        if self.frozen_policy is not None:                  # learners + frozen-network agents (the GA3C-CADRL agent mechanism) in one launch
-            _lib.check(self._lib.cavoid_actor_run_mix(env._h, pol._h, self.frozen_policy._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards),
-                                                      p(env.done), p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps),
-                                                      1 if self.greedy else 0, env._stream()), "cavoid_actor_run_mix")
-        else:
-            _lib.check(self._lib.cavoid_actor_run(env._h, pol._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done),
-                                                  p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps), 1 if self.greedy else 0,
-                                                  env._stream()), "cavoid_actor_run")
-        self._cur = (self._cur + int(n_steps)) & 1
-        self.step_index += int(n_steps)
+        why = None if self.fused_available else "run_fused needs a FusedPolicy and a configuration the fused kernel carries (see fused_available)"
+        mix = self.frozen_policy is not None                # learners + frozen-network agents (the GA3C-CADRL agent mechanism) in one launch
+        self._run_fused_on("cavoid_actor_run_mix" if mix else "cavoid_actor_run", n_steps, why, frozen=mix)
 
     def capture_fused(self, steps_per_graph: int = 8) -> None:
         """``run_fused(steps_per_graph)`` as a one-node hipGraph (``replay`` then costs one graph launch per K steps)."""
-        if steps_per_graph < 2 or steps_per_graph % 2:
-            raise ValueError("steps_per_graph must be a positive even number")
-        side = torch.cuda.Stream(device=self.env.device)
-        side.wait_stream(torch.cuda.current_stream(self.env.device))
-        with torch.cuda.stream(side):
-            self.run_fused(2)
-        torch.cuda.current_stream(self.env.device).wait_stream(side)
-        torch.cuda.synchronize(self.env.device)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self.run_fused(steps_per_graph)
-        self.step_index -= steps_per_graph                # capture records, it does not execute
-        self._graph_steps = steps_per_graph
+        self._capture_steps(self.run_fused, steps_per_graph)
 
     # -- the fused actor of crowd worlds (17..64 agents): opt-in, beside the step-by-step path ---------------------------------
     @property
@@ -504,34 +514,12 @@ class BatchedRollout(object):
         tile of floor(64/N) worlds a workgroup runs the policy on its own rows (the ring form: up to 63 observed neighbours), steps its
         worlds and records the step.  Bit-identical to ``n_steps`` calls of ``step()``; capturable into a hipGraph."""
         why = self.crowd_fused_unavailable_reason
-        if why is not None:
-            raise RuntimeError("run_fused_crowd does not apply: " + why)
-        env, pol = self.env, self.policy
-        b = self._actor_buffers()
-        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
-        p = BatchedCollisionAvoidanceEnv._ptr
-        _lib.check(self._lib.cavoid_crowd_actor_run(env._h, pol._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done),
-                                                    p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps), 1 if self.greedy else 0,
-                                                    env._stream()), "cavoid_crowd_actor_run")
-        self._cur = (self._cur + int(n_steps)) & 1
-        self.step_index += int(n_steps)
+        self._run_fused_on("cavoid_crowd_actor_run", n_steps, None if why is None else "run_fused_crowd does not apply: " + why)
 
     def capture_fused_crowd(self, steps_per_graph: int = 4) -> None:
         """``run_fused_crowd(steps_per_graph)`` as a one-node hipGraph, as ``capture_fused``: an even step count (the two observation
         buffers alternate), two warm-up steps outside the capture; ``replay`` serves it."""
-        if steps_per_graph < 2 or steps_per_graph % 2:
-            raise ValueError("steps_per_graph must be a positive even number")
-        side = torch.cuda.Stream(device=self.env.device)
-        side.wait_stream(torch.cuda.current_stream(self.env.device))
-        with torch.cuda.stream(side):
-            self.run_fused_crowd(2)
-        torch.cuda.current_stream(self.env.device).wait_stream(side)
-        torch.cuda.synchronize(self.env.device)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self.run_fused_crowd(steps_per_graph)
-        self.step_index -= steps_per_graph                # capture records, it does not execute
-        self._graph_steps = steps_per_graph
+        self._capture_steps(self.run_fused_crowd, steps_per_graph)
 
     # -- the fused actor of crowd worlds with frozen-network agents (the training mix): opt-in, beside the step-by-step path ----------
     @property
@@ -557,34 +545,12 @@ class BatchedRollout(object):
         the same pass once more on ``frozen_policy``'s weights where the tile holds a running frozen-network agent and takes its argmax for
         those rows, steps its worlds and records the step.  Bit-identical to ``n_steps`` calls of ``step()``; capturable into a hipGraph."""
         why = self.crowd_mix_fused_unavailable_reason
-        if why is not None:
-            raise RuntimeError("run_fused_crowd_mix does not apply: " + why)
-        env, pol = self.env, self.policy
-        b = self._actor_buffers()
-        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
-        p = BatchedCollisionAvoidanceEnv._ptr
-        _lib.check(self._lib.cavoid_crowd_actor_run_mix(env._h, pol._h, self.frozen_policy._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards),
-                                                        p(env.done), p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps),
-                                                        1 if self.greedy else 0, env._stream()), "cavoid_crowd_actor_run_mix")
-        self._cur = (self._cur + int(n_steps)) & 1
-        self.step_index += int(n_steps)
+        self._run_fused_on("cavoid_crowd_actor_run_mix", n_steps, None if why is None else "run_fused_crowd_mix does not apply: " + why, frozen=True)
 
     def capture_fused_crowd_mix(self, steps_per_graph: int = 4) -> None:
         """``run_fused_crowd_mix(steps_per_graph)`` as a one-node hipGraph, as ``capture_fused_crowd``: an even step count (the two
         observation buffers alternate), two warm-up steps outside the capture; ``replay`` serves it."""
-        if steps_per_graph < 2 or steps_per_graph % 2:
-            raise ValueError("steps_per_graph must be a positive even number")
-        side = torch.cuda.Stream(device=self.env.device)
-        side.wait_stream(torch.cuda.current_stream(self.env.device))
-        with torch.cuda.stream(side):
-            self.run_fused_crowd_mix(2)
-        torch.cuda.current_stream(self.env.device).wait_stream(side)
-        torch.cuda.synchronize(self.env.device)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self.run_fused_crowd_mix(steps_per_graph)
-        self.step_index -= steps_per_graph                # capture records, it does not execute
-        self._graph_steps = steps_per_graph
+        self._capture_steps(self.run_fused_crowd_mix, steps_per_graph)
 
     # -- the fused actor of the weight_sharing network: opt-in, beside the step-by-step path ---------------------------------------
     @property
@@ -609,34 +575,12 @@ class BatchedRollout(object):
         (``cavoid_actor_run_ws``) -- per tile of floor(64/N) worlds a workgroup runs the weight_sharing pass (float32 MFMA) on its own
         rows, steps its worlds and records the step.  Bit-identical to ``n_steps`` calls of ``step()``; capturable into a hipGraph."""
         why = self.ws_fused_unavailable_reason
-        if why is not None:
-            raise RuntimeError("run_fused_ws does not apply: " + why)
-        env, pol = self.env, self.policy
-        b = self._actor_buffers()
-        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
-        p = BatchedCollisionAvoidanceEnv._ptr
-        _lib.check(self._lib.cavoid_actor_run_ws(env._h, pol._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done),
-                                                 p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps), 1 if self.greedy else 0,
-                                                 env._stream()), "cavoid_actor_run_ws")
-        self._cur = (self._cur + int(n_steps)) & 1
-        self.step_index += int(n_steps)
+        self._run_fused_on("cavoid_actor_run_ws", n_steps, None if why is None else "run_fused_ws does not apply: " + why)
 
     def capture_fused_ws(self, steps_per_graph: int = 4) -> None:
         """``run_fused_ws(steps_per_graph)`` as a one-node hipGraph, as ``capture_fused``: an even step count (the two observation
         buffers alternate), two warm-up steps outside the capture; ``replay`` serves it."""
-        if steps_per_graph < 2 or steps_per_graph % 2:
-            raise ValueError("steps_per_graph must be a positive even number")
-        side = torch.cuda.Stream(device=self.env.device)
-        side.wait_stream(torch.cuda.current_stream(self.env.device))
-        with torch.cuda.stream(side):
-            self.run_fused_ws(2)
-        torch.cuda.current_stream(self.env.device).wait_stream(side)
-        torch.cuda.synchronize(self.env.device)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self.run_fused_ws(steps_per_graph)
-        self.step_index -= steps_per_graph                # capture records, it does not execute
-        self._graph_steps = steps_per_graph
+        self._capture_steps(self.run_fused_ws, steps_per_graph)
 
     # -- the fused actor of crowd worlds with the weight_sharing network: opt-in, beside the step-by-step path ----------------------
     @property
@@ -662,34 +606,12 @@ class BatchedRollout(object):
         observed neighbours) on its own rows that need an action, steps its worlds and records the step.  Bit-identical to ``n_steps``
         calls of ``step()``; capturable into a hipGraph."""
         why = self.crowd_ws_fused_unavailable_reason
-        if why is not None:
-            raise RuntimeError("run_fused_crowd_ws does not apply: " + why)
-        env, pol = self.env, self.policy
-        b = self._actor_buffers()
-        cur, nxt = self._obs_buffers[self._cur], self._obs_buffers[1 - self._cur]
-        p = BatchedCollisionAvoidanceEnv._ptr
-        _lib.check(self._lib.cavoid_crowd_actor_run_ws(env._h, pol._h, self._h, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done),
-                                                       p(env.game_over), p(self._act_out), p(self._val_out), int(n_steps),
-                                                       1 if self.greedy else 0, env._stream()), "cavoid_crowd_actor_run_ws")
-        self._cur = (self._cur + int(n_steps)) & 1
-        self.step_index += int(n_steps)
+        self._run_fused_on("cavoid_crowd_actor_run_ws", n_steps, None if why is None else "run_fused_crowd_ws does not apply: " + why)
 
     def capture_fused_crowd_ws(self, steps_per_graph: int = 4) -> None:
         """``run_fused_crowd_ws(steps_per_graph)`` as a one-node hipGraph, as ``capture_fused_crowd``: an even step count (the two
         observation buffers alternate), two warm-up steps outside the capture; ``replay`` serves it."""
-        if steps_per_graph < 2 or steps_per_graph % 2:
-            raise ValueError("steps_per_graph must be a positive even number")
-        side = torch.cuda.Stream(device=self.env.device)
-        side.wait_stream(torch.cuda.current_stream(self.env.device))
-        with torch.cuda.stream(side):
-            self.run_fused_crowd_ws(2)
-        torch.cuda.current_stream(self.env.device).wait_stream(side)
-        torch.cuda.synchronize(self.env.device)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self.run_fused_crowd_ws(steps_per_graph)
-        self.step_index -= steps_per_graph                # capture records, it does not execute
-        self._graph_steps = steps_per_graph
+        self._capture_steps(self.run_fused_crowd_ws, steps_per_graph)
 
     # -- hipGraph path ---------------------------------------------------------------------------------
     def capture(self, steps_per_graph: int = 2) -> None:
@@ -698,23 +620,10 @@ class BatchedRollout(object):
         compiler).  The per-step launch train (tens of small kernels) then costs one graph replay.
         Must be even: the two observation buffers alternate.  The experience store is addressed by the
         handle's device-side step counter, so a replay lands in the right blocks."""
-        if steps_per_graph < 2 or steps_per_graph % 2:
-            raise ValueError("steps_per_graph must be a positive even number")
-        if self.policy is None:
-            raise ValueError("capture() needs a policy")
-        side = torch.cuda.Stream(device=self.env.device)
-        side.wait_stream(torch.cuda.current_stream(self.env.device))
-        with torch.cuda.stream(side):                      # warm-up outside capture (allocator, lazy inits)
-            for _ in range(2):
+        def steps(n):
+            for _ in range(n):
                 self.step()
-        torch.cuda.current_stream(self.env.device).wait_stream(side)
-        torch.cuda.synchronize(self.env.device)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            for _ in range(steps_per_graph):
-                self.step()
-        self.step_index -= steps_per_graph                # capture records, it does not execute
-        self._graph_steps = steps_per_graph
+        self._capture_steps(steps, steps_per_graph, needs_policy=True)
 
     def replay(self, n_replays: int = 1) -> None:
         """Run ``n_replays * steps_per_graph`` env steps of every world."""

@@ -66,6 +66,42 @@ def load_checkpoint(path: str, net: NetworkVP_rnn, trainer: A3CTrainer, device) 
     return int(ck.get("episode", 0))
 
 
+# The opt-in one-launch forms of the evaluation round and of the actor loop.  A row: the flag (the first one set wins, in this order), where
+# the reason comes from (a function of ga3c.evaluate / a property of BatchedRollout; None: the form applies), the message the run ends with
+# where it does not, the line rank 0 prints, and the call (evaluate()'s switch / the BatchedRollout method that captures the launch).
+EVALUATE_FORMS = (
+    ("fused_evaluate", "evaluate_fused_unavailable_reason",
+     lambda why: "--fused-evaluate: the fused evaluation kernel (cavoid_eval_run) does not apply: " + why,
+     "[Evaluate] fused evaluation kernel (cavoid_eval_run), %d env steps per launch", "fused"),
+    ("fused_ws_evaluate", "evaluate_fused_ws_unavailable_reason",
+     lambda why: "--fused-ws-evaluate: the fused weight_sharing evaluation kernel (cavoid_eval_run_ws) does not apply: " + why,
+     "[Evaluate] fused weight_sharing evaluation kernel (cavoid_eval_run_ws), %d env steps per launch", "fused_ws"),
+    ("fused_crowd_evaluate", "evaluate_fused_crowd_unavailable_reason",
+     lambda why: "--fused-crowd-evaluate: the fused crowd evaluation kernel (cavoid_crowd_eval_run) does not apply: " + why,
+     "[Evaluate] fused crowd evaluation kernel (cavoid_crowd_eval_run), %d env steps per launch", "fused_crowd"),
+    ("fused_crowd_ws_evaluate", "evaluate_fused_crowd_ws_unavailable_reason",
+     lambda why: "--fused-crowd-ws-evaluate: the fused crowd weight_sharing evaluation kernel (cavoid_crowd_eval_run_ws) does not apply: " + why,
+     "[Evaluate] fused crowd weight_sharing evaluation kernel (cavoid_crowd_eval_run_ws), %d env steps per launch", "fused_crowd_ws"),
+    ("fused_crowd_mix_evaluate", "evaluate_fused_crowd_mix_unavailable_reason",
+     lambda why: "--fused-crowd-mix-evaluate: the fused crowd evaluation kernel with a frozen network (cavoid_crowd_eval_run_mix) does not apply: " + why,
+     "[Evaluate] fused crowd evaluation kernel (cavoid_crowd_eval_run_mix), %d env steps per launch", "fused_crowd_mix"),
+)
+ACTOR_FORMS = (
+    ("fused_crowd_actor", "crowd_fused_unavailable_reason",
+     lambda why: "--fused-crowd-actor: the crowd actor kernel (cavoid_crowd_actor_run) does not apply: " + why,
+     "fused crowd actor kernel (cavoid_crowd_actor_run), %d env steps per launch", "capture_fused_crowd"),
+    ("fused_crowd_mix_actor", "crowd_mix_fused_unavailable_reason",
+     lambda why: "--fused-crowd-mix-actor: the crowd actor kernel with a frozen network (cavoid_crowd_actor_run_mix) does not apply: " + why,
+     "fused crowd actor kernel (cavoid_crowd_actor_run_mix: learner + frozen network), %d env steps per launch", "capture_fused_crowd_mix"),
+    ("fused_ws_actor", "ws_fused_unavailable_reason",
+     lambda why: "--fused-ws-actor: the weight_sharing actor kernel (cavoid_actor_run_ws) does not apply: " + why,
+     "fused weight_sharing actor kernel (cavoid_actor_run_ws), %d env steps per launch", "capture_fused_ws"),
+    ("fused_crowd_ws_actor", "crowd_ws_fused_unavailable_reason",
+     lambda why: "--fused-crowd-ws-actor: the crowd weight_sharing actor kernel (cavoid_crowd_actor_run_ws) does not apply: " + why,
+     "fused crowd weight_sharing actor kernel (cavoid_crowd_actor_run_ws), %d env steps per launch", "capture_fused_crowd_ws"),
+)
+
+
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--worlds", type=int, default=8192, help="total worlds over all GPUs")
@@ -344,68 +380,23 @@ def main(argv=None) -> None:
         return FusedPolicy(frozen_net, seed=0, ws_crowd=ws_crowd)
     if args.evaluate:
         frozen = make_frozen()
-        from .evaluate import evaluate, evaluate_fused_unavailable_reason
+        from . import evaluate as evaluation
         if fused is not None:
             fused.refresh(check_range=True)                   # (a checkpoint may have been loaded: a weight beyond the float16 split's range fails loudly)
         eval_policy = fused if fused is not None else net.predict_p_and_v
-        if args.fused_evaluate:
-            why = evaluate_fused_unavailable_reason(env, eval_policy, frozen)
+        form = next((row for row in EVALUATE_FORMS if getattr(args, row[0])), None)
+        switch = {}
+        if form is not None:
+            _, reason, refusal, line, which = form
+            why = getattr(evaluation, reason)(env, eval_policy, frozen)
             if why is not None:
-                raise SystemExit("--fused-evaluate: the fused evaluation kernel (cavoid_eval_run) does not apply: " + why)
+                raise SystemExit(refusal(why))
             if args.steps_per_graph < 1:
                 raise SystemExit("--steps-per-graph must be >= 1")
             if rank == 0:
-                print("[Evaluate] fused evaluation kernel (cavoid_eval_run), %d env steps per launch" % args.steps_per_graph, flush=True)
-            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused=True, steps_per_launch=args.steps_per_graph)
-        elif args.fused_ws_evaluate:
-            from .evaluate import evaluate_fused_ws_unavailable_reason
-            why = evaluate_fused_ws_unavailable_reason(env, eval_policy, frozen)
-            if why is not None:
-                raise SystemExit("--fused-ws-evaluate: the fused weight_sharing evaluation kernel (cavoid_eval_run_ws) does not apply: " + why)
-            if args.steps_per_graph < 1:
-                raise SystemExit("--steps-per-graph must be >= 1")
-            if rank == 0:
-                print("[Evaluate] fused weight_sharing evaluation kernel (cavoid_eval_run_ws), %d env steps per launch" % args.steps_per_graph,
-                      flush=True)
-            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused_ws=True, steps_per_launch=args.steps_per_graph)
-        elif args.fused_crowd_evaluate:
-            from .evaluate import evaluate_fused_crowd_unavailable_reason
-            why = evaluate_fused_crowd_unavailable_reason(env, eval_policy, frozen)
-            if why is not None:
-                raise SystemExit("--fused-crowd-evaluate: the fused crowd evaluation kernel (cavoid_crowd_eval_run) does not apply: " + why)
-            if args.steps_per_graph < 1:
-                raise SystemExit("--steps-per-graph must be >= 1")
-            if rank == 0:
-                print("[Evaluate] fused crowd evaluation kernel (cavoid_crowd_eval_run), %d env steps per launch" % args.steps_per_graph, flush=True)
-            res = evaluate(env, eval_policy, rounds=args.evaluate, fused_crowd=True, steps_per_launch=args.steps_per_graph)
-        elif args.fused_crowd_ws_evaluate:
-            from .evaluate import evaluate_fused_crowd_ws_unavailable_reason
-            why = evaluate_fused_crowd_ws_unavailable_reason(env, eval_policy, frozen)
-            if why is not None:
-                raise SystemExit("--fused-crowd-ws-evaluate: the fused crowd weight_sharing evaluation kernel (cavoid_crowd_eval_run_ws) does not "
-                                 "apply: " + why)
-            if args.steps_per_graph < 1:
-                raise SystemExit("--steps-per-graph must be >= 1")
-            if rank == 0:
-                print("[Evaluate] fused crowd weight_sharing evaluation kernel (cavoid_crowd_eval_run_ws), %d env steps per launch"
-                      % args.steps_per_graph, flush=True)
-            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused_crowd_ws=True,
-                           steps_per_launch=args.steps_per_graph)
-        elif args.fused_crowd_mix_evaluate:
-            from .evaluate import evaluate_fused_crowd_mix_unavailable_reason
-            why = evaluate_fused_crowd_mix_unavailable_reason(env, eval_policy, frozen)
-            if why is not None:
-                raise SystemExit("--fused-crowd-mix-evaluate: the fused crowd evaluation kernel with a frozen network (cavoid_crowd_eval_run_mix) "
-                                 "does not apply: " + why)
-            if args.steps_per_graph < 1:
-                raise SystemExit("--steps-per-graph must be >= 1")
-            if rank == 0:
-                print("[Evaluate] fused crowd evaluation kernel (cavoid_crowd_eval_run_mix), %d env steps per launch" % args.steps_per_graph,
-                      flush=True)
-            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, fused_crowd_mix=True,
-                           steps_per_launch=args.steps_per_graph)
-        else:
-            res = evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen)
+                print(line % args.steps_per_graph, flush=True)
+            switch = {which: True, "steps_per_launch": args.steps_per_graph}
+        res = evaluation.evaluate(env, eval_policy, rounds=args.evaluate, frozen_policy=frozen, **switch)
         if rank == 0:
             print("[Evaluate] " + "  ".join("%s %.4f" % (k, v) if isinstance(v, float) else "%s %d" % (k, v) for k, v in res.items()),
                   flush=True)
@@ -448,31 +439,14 @@ def main(argv=None) -> None:
     next_save = episodes_before + args.save_every
     finished = 0
     roll.reset()
-    if args.fused_crowd_actor:
-        why = roll.crowd_fused_unavailable_reason
+    form = next((row for row in ACTOR_FORMS if getattr(args, row[0])), None)
+    if form is not None:
+        _, reason, refusal, line, capture = form
+        why = getattr(roll, reason)
         if why is not None:
-            raise SystemExit("--fused-crowd-actor: the crowd actor kernel (cavoid_crowd_actor_run) does not apply: " + why)
-        roll.capture_fused_crowd(steps_per_graph=args.steps_per_graph)
-        actors = "fused crowd actor kernel (cavoid_crowd_actor_run), %d env steps per launch" % args.steps_per_graph
-    elif args.fused_crowd_mix_actor:
-        why = roll.crowd_mix_fused_unavailable_reason
-        if why is not None:
-            raise SystemExit("--fused-crowd-mix-actor: the crowd actor kernel with a frozen network (cavoid_crowd_actor_run_mix) does not apply: " + why)
-        roll.capture_fused_crowd_mix(steps_per_graph=args.steps_per_graph)
-        actors = ("fused crowd actor kernel (cavoid_crowd_actor_run_mix: learner + frozen network), %d env steps per launch"
-                  % args.steps_per_graph)
-    elif args.fused_ws_actor:
-        why = roll.ws_fused_unavailable_reason
-        if why is not None:
-            raise SystemExit("--fused-ws-actor: the weight_sharing actor kernel (cavoid_actor_run_ws) does not apply: " + why)
-        roll.capture_fused_ws(steps_per_graph=args.steps_per_graph)
-        actors = "fused weight_sharing actor kernel (cavoid_actor_run_ws), %d env steps per launch" % args.steps_per_graph
-    elif args.fused_crowd_ws_actor:
-        why = roll.crowd_ws_fused_unavailable_reason
-        if why is not None:
-            raise SystemExit("--fused-crowd-ws-actor: the crowd weight_sharing actor kernel (cavoid_crowd_actor_run_ws) does not apply: " + why)
-        roll.capture_fused_crowd_ws(steps_per_graph=args.steps_per_graph)
-        actors = "fused crowd weight_sharing actor kernel (cavoid_crowd_actor_run_ws), %d env steps per launch" % args.steps_per_graph
+            raise SystemExit(refusal(why))
+        getattr(roll, capture)(steps_per_graph=args.steps_per_graph)
+        actors = line % args.steps_per_graph
     elif roll.fused_available and not args.no_actor_kernel:
         roll.capture_fused(steps_per_graph=args.steps_per_graph)       # K closed-loop steps per launch (cavoid_actor_run)
         actors = "%s, %d env steps per launch" % (roll.actor_path, args.steps_per_graph)

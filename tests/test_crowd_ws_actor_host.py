@@ -70,8 +70,11 @@ def test_the_env_step_bound_is_the_crowd_kernels_allocation():
     assert rollout.crowd_env_step_lds_bytes(64, 447) == 4 * (128 + 6384 + 8064)
     # n = 17, M = 63 (a padded row): keys 2048; rows (2048 // 449) & ~3 = 4 -> 1788 floats < keys
     assert rollout.crowd_env_step_lds_bytes(17, 447) == 4 * (128 + 1344 + 16 * 80 + 2048)
+    # the bound stands once, in the crowd launches' shared prologue, and this unit hands it the weight_sharing loan
+    helper = open(os.path.join(CSRC, "cavoid_loop_host.hpp")).read()
+    assert re.search(r"lds\s*>\s*65536\s*\|\|\s*lds\s*>\s*lent\b", helper)
     src = open(os.path.join(CSRC, "cavoid_crowd_actor_ws.hip")).read()
-    assert re.search(r"lds\s*>\s*65536\s*\|\|\s*lds\s*>\s*actor_ws_lent_bytes\(\)", src)
+    assert re.search(r"crowd_loop_tiles\(\s*e\s*,\s*(?:/\*lent=\*/\s*)?actor_ws_lent_bytes\(\)\s*,", src)
 
 
 def test_the_entry_point_is_declared_exported_and_bound():
