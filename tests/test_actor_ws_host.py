@@ -104,7 +104,7 @@ def test_train_cli_knows_the_flag():
 def test_actor_ws_kernels_fit_two_workgroups_per_cu():
     """Every instantiation within 256 registers per lane (two workgroups per CU), 256 threads, and the ones the default shapes run -- N up to 15
     without ORCA, the WS-8 shape among them -- free of scratch (profiles/ws_actor_resources.txt lists all of them)."""
-    from tests.test_crowd_host import LLVM, _kernel_notes
+    from tests.host_support import LLVM, _kernel_notes
     if not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))):
         pytest.skip("llvm-objdump / llvm-readelf of the ROCm toolchain not present")
     text = _kernel_notes()

@@ -7,7 +7,7 @@ import re
 
 import pytest
 
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes
+from tests.host_support import LLVM, ROOT, _kernel_notes
 
 DEFAULT_FORM = ("split", 16)
 

@@ -1,36 +1,11 @@
 """CPU tests of the crowd step form's host side (worlds of 17..64 agents, CAVOID_FORM_CROWD): the agent range cavoid_create accepts,
 what it refuses above 16 agents, the header's declarations, and the built library's crowd kernels (zero scratch)."""
-import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rl_collision_avoidance_amd", "libcavoid_hip.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def _no_gpu():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("this test is about the GPU-less box")
-
-
-def _create(cfg):
-    from rl_collision_avoidance_amd import _lib
-    h = C.c_void_p()
-    return _lib.lib().cavoid_create(C.byref(cfg), 16, 0, 0, C.byref(h))
-
-
-def _cfg(n, m=None):
-    from rl_collision_avoidance_amd import _lib
-    cfg = _lib.CavoidCfg()
-    assert _lib.lib().cavoid_default_cfg(C.byref(cfg), n, n - 1 if m is None else m) == 0
-    return cfg
+from tests.host_support import LLVM, ROOT, _cfg, _create, _kernel_notes, _no_gpu
 
 
 @pytest.mark.parametrize("n", [17, 20, 33, 64])
@@ -67,23 +42,6 @@ def test_header_declares_the_crowd_range_and_form():
     assert m and _lib.STEP_FORMS[int(m.group(1))] == "CROWD"
     assert re.search(r"#define\s+CAVOID_ABI_VERSION\s+3\b", header)
     assert _lib.MAX_AGENTS == 64
-
-
-def _kernel_notes():
-    work = tempfile.mkdtemp(prefix="cavoid_notes_")
-    try:
-        local = os.path.join(work, "lib.so")
-        shutil.copy(LIB, local)
-        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], cwd=work, check=True, stdout=subprocess.DEVNULL,
-                       stderr=subprocess.DEVNULL)
-        text = ""
-        for name in sorted(os.listdir(work)):
-            if "amdgcn-amd-amdhsa--gfx950" in name:
-                text += subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(work, name)], check=True,
-                                       stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True).stdout
-        return text
-    finally:
-        shutil.rmtree(work, ignore_errors=True)
 
 
 @pytest.mark.skipif(not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))),

@@ -5,7 +5,7 @@ import re
 
 import pytest
 
-from tests.test_crowd_host import LLVM, _kernel_notes
+from tests.host_support import LLVM, _kernel_notes
 
 ONE, THREE = "step_push", "env, push, episode log"
 

@@ -7,7 +7,7 @@ import re
 
 import pytest
 
-from tests.test_crowd_host import LLVM, _cfg, _create, _kernel_notes, _no_gpu
+from tests.host_support import LLVM, _cfg, _create, _kernel_notes, _no_gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _HAVE_LLVM = os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))

@@ -8,7 +8,7 @@ import re
 
 import pytest
 
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes
+from tests.host_support import LLVM, ROOT, _kernel_notes
 
 CSRC = os.path.join(ROOT, "rl_collision_avoidance_amd", "csrc")
 

@@ -9,7 +9,7 @@ from types import SimpleNamespace
 
 import pytest
 
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes
+from tests.host_support import LLVM, ROOT, _kernel_notes
 
 RETURN_SENTENCE = "An agent's return sums the rewards up to and including the step at which its world is over."
 

@@ -9,7 +9,7 @@ from types import SimpleNamespace
 import pytest
 import torch
 
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes
+from tests.host_support import LLVM, ROOT, _kernel_notes
 
 DEFAULT_FORM = ("split", 16)
 

@@ -8,7 +8,7 @@ from types import SimpleNamespace
 
 import pytest
 
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes
+from tests.host_support import LLVM, ROOT, _kernel_notes
 
 
 def test_library_exports_the_entry_point_and_checks_its_arguments():

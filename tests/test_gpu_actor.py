@@ -12,48 +12,22 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import actor_twins as tw
 from tests import rollout_scripts as rs
+from tests.actor_twins import same as _same
+from tests.gpu_support import EINVAL, EUNSUPPORTED
 
 pytestmark = pytest.mark.gpu
 
 
 def _make(W, N, seed, reflush, greedy=False, skip_finished=None, M=None, time_max=5, **over):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
-    from rl_collision_avoidance_amd.config import EnvConfig
-    from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
-    from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
-    from rl_collision_avoidance_amd.ga3c.rollout import BatchedRollout
-
-    class Cfg(EnvConfig):
-        def __init__(self):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
-            if M is not None:
-                self.MAX_NUM_OTHER_AGENTS_OBSERVED = M
-            EnvConfig.__init__(self)
-    cfg = Cfg()
-    env = BatchedCollisionAvoidanceEnv(W, cfg, device="cuda:0", seed=seed, **over)
-    torch.manual_seed(1234)
-    net = NetworkVP_rnn(cfg).to("cuda:0")
-    pol = FusedPolicy(net, seed=77)
-    frozen = None
-    if over.get("gen_frozen_fraction", 0.0) > 0.0:          # the network behind the frozen-network agents: its own weights
-        torch.manual_seed(4321)
-        frozen = FusedPolicy(NetworkVP_rnn(cfg).to("cuda:0"), seed=0)
     # The fused kernel runs the network only for the rows that still need an action (a learning agent that has not finished; with the
     # re-flush quirk or frozen-network agents: every row), exactly the rows the step-by-step path lists with skip_finished -- what a
     # finished agent's ring entry holds as action is whatever it was last given, in both forms, so the forms are compared like for like.
     if skip_finished is None:
         skip_finished = (not reflush) and not (over.get("gen_frozen_fraction", 0.0) > 0.0)
-    # short chunks: many flushes; room for every duplicate row of the re-flush quirk (a full buffer drops rows in arrival order,
-    # which legitimately differs between the two forms)
-    roll = BatchedRollout(env, pol, reflush_done=reflush, greedy=greedy, time_max=time_max, dup_capacity=600000 if reflush else None,
-                          skip_finished=skip_finished, frozen_policy=frozen)
-    roll.reset()
-    return env, net, pol, roll
-
-
-def _same(a, b, what):
-    assert torch.equal(a, b), what
+    # short chunks: many flushes; the frozen-network agents' network where the generator makes them
+    return tw.make(W, N, M, seed, reflush, greedy, frozen="from_fraction", skip_finished=skip_finished, time_max=time_max, **over)
 
 
 @pytest.mark.parametrize("N,W,reflush,greedy,over", [
@@ -92,57 +66,16 @@ def _same(a, b, what):
     (4, 128, False, False, dict(time_max=31)),
 ])
 def test_fused_actor_equals_step_by_step(N, W, reflush, greedy, over):
-    seed = 21
-    env_a, net_a, pol_a, a = _make(W, N, seed, reflush, greedy, **over)
-    env_b, net_b, pol_b, b = _make(W, N, seed, reflush, greedy, **over)
+    twin_a, twin_b = _make(W, N, 21, reflush, greedy, **over), _make(W, N, 21, reflush, greedy, **over)
+    a = twin_a[3]
     assert a.fused_available and a.actor_path.startswith("fused actor kernel"), a.actor_path
-    for p, q in zip(net_a.parameters(), net_b.parameters()):
-        assert torch.equal(p, q)
-    _same(a.obs, b.obs, "first observation")
-    total = 0
-    for k in (2, 1, 7, 16, 4) + (16,) * 14 + (3,):                       # odd counts too: the observation buffers alternate
-        a.run_fused(k)
-        for _ in range(k):
-            b.step()
-        total += k
-        if total > 40 and total % 64:                                    # (full comparisons early on, then every fourth launch)
-            continue
-        _same(a.obs, b.obs, ("obs", total))
-        for x, y in zip(env_a.get_state(), env_b.get_state()):
-            _same(x, y, ("state", total))
-        _same(env_a.episode, env_b.episode, ("episode", total))
-        _same(env_a.rewards, env_b.rewards, ("rewards", total))
-        _same(env_a.done, env_b.done, ("done", total))
-        _same(env_a.game_over, env_b.game_over, ("game_over", total))
-        for name in ("x", "val", "ret", "act_ring", "emit_t"):
-            _same(getattr(a, name), getattr(b, name), (name, total))
-        assert a.step_index == b.step_index == total
-    assert env_a.episode.max().item() >= 1
-    # what reaches the trainer and the stats process
-    ba, bb = a.drain(flush_all=True), b.drain(flush_all=True)
-    assert len(ba) == len(bb) > 0 and ba.dropped == bb.dropped == 0
-    if over.get("time_max", 5) > 5:
-        rs.require_deep_flushes(bb.src.cpu().numpy(), over["time_max"], "fused actor N=%d W=%d reflush=%s" % (N, W, reflush))
-    ka = np.lexsort(ba.src.cpu().numpy().T[::-1])
-    kb = np.lexsort(bb.src.cpu().numpy().T[::-1])
-    assert np.array_equal(ba.src.cpu().numpy()[ka], bb.src.cpu().numpy()[kb])
-    assert np.array_equal(ba.x.cpu().numpy()[ka], bb.x.cpu().numpy()[kb])
-    assert np.array_equal(ba.r.cpu().numpy()[ka], bb.r.cpu().numpy()[kb])
-    assert np.array_equal(ba.a_index.cpu().numpy()[ka], bb.a_index.cpu().numpy()[kb])
-    ea, eb = a.drain_episodes().cpu().numpy(), b.drain_episodes().cpu().numpy()
-    assert len(ea) == len(eb) > 0
-    ea, eb = ea[np.lexsort(ea.T[::-1])], eb[np.lexsort(eb.T[::-1])]
-    assert np.array_equal(ea[:, 0], eb[:, 0]) and np.array_equal(ea[:, 2], eb[:, 2])
-    np.testing.assert_allclose(ea[:, 1], eb[:, 1], rtol=1e-6, atol=1e-6)
-    # and the two forms interleave: each continues where the other stopped
-    a.step(); a.run_fused(3)
-    b.run_fused(2); b.step(); b.step()
-    _same(a.obs, b.obs, "interleaved obs")
-    _same(a.emit_t, b.emit_t, "interleaved emit_t")
-    for r in (a, b):
-        r.close()
-    for e in (env_a, env_b):
-        e.close()
+    time_max = over.get("time_max", 5)
+    tw.fused_equals_step_by_step(
+        tw.TILE, twin_a, twin_b, ("fused actor", N, W, reflush), ks=tw.KS_TILE,
+        compare_at=lambda total: total <= 40 or total % 64 == 0,         # (full comparisons early on, then every fourth launch)
+        rings=tw.RINGS,                                                  # (this form's test never compared dup_count)
+        deep_flushes=(time_max, "fused actor N=%d W=%d reflush=%s" % (N, W, reflush)) if time_max > 5 else None,
+        interleave=tw.INTERLEAVE_TILE)                                   # (... and its interleave looks at obs and emit_t)
 
 
 def test_fused_actor_equals_step_by_step_with_a_row_list():
@@ -165,57 +98,37 @@ def test_fused_actor_equals_step_by_step_with_a_row_list():
             _same(getattr(a, name), getattr(b, name), name)
     ba, bb = a.drain(flush_all=True), b.drain(flush_all=True)
     assert len(ba) == len(bb) > 0
-    ka, kb = np.lexsort(ba.src.cpu().numpy().T[::-1]), np.lexsort(bb.src.cpu().numpy().T[::-1])
-    for name in ("src", "x", "r", "a_index"):
-        assert np.array_equal(getattr(ba, name).cpu().numpy()[ka], getattr(bb, name).cpu().numpy()[kb]), name
-    for r in (a, b):
-        r.close()
-    env_a.close(); env_b.close()
+    tw.compare_drained(ba, bb, "fused actor with a row list")
+    tw.close((env_a, a), (env_b, b))
 
 
 def test_fused_actor_graph_replay_equals_eager_calls():
     """`capture_fused`: the K-step launch as a one-node hipGraph; replays advance the device-side counters like eager calls."""
     W, N, seed = 256, 4, 3
-    env_a, _, _, a = _make(W, N, seed, False)
-    env_b, _, _, b = _make(W, N, seed, False)
-    a.capture_fused(steps_per_graph=4)          # (runs 2 warm-up steps outside the capture)
-    b.run_fused(2)
-    a.replay(3)
-    for _ in range(3):
-        b.run_fused(4)
-    _same(a.obs, b.obs, "obs")
-    for name in ("x", "ret", "emit_t"):
-        _same(getattr(a, name), getattr(b, name), name)
-    assert a.step_index == b.step_index == 14
-    for r in (a, b):
-        r.close()
-    env_a.close(); env_b.close()
+    twin_a, twin_b = _make(W, N, seed, False), _make(W, N, seed, False)
+
+    def compare(env_a, a, env_b, b, total):
+        _same(a.obs, b.obs, "obs")
+        for name in ("x", "ret", "emit_t"):
+            _same(getattr(a, name), getattr(b, name), name)
+        assert a.step_index == b.step_index == total == 14
+    tw.graph_replay(tw.TILE, twin_a, twin_b, 3, compare)
+    tw.close((twin_a[0], twin_a[3]), (twin_b[0], twin_b[3]))
 
 
 def test_fused_actor_refuses_what_it_does_not_carry():
-    from rl_collision_avoidance_amd import _lib
-    env, _, _, roll = _make(64, 4, 1, False, dynamics=2)               # velocity (holonomic) actions: the step-by-step entry points carry them
+    env, _, pol, roll = _make(64, 4, 1, False, dynamics=2)             # velocity (holonomic) actions: the step-by-step entry points carry them
     assert not roll.fused_available and "holonomic" in roll.actor_path
     with pytest.raises(RuntimeError):
         roll.run_fused(2)
     # straight at the C ABI: a code, not a crash
-    b = roll._actor_buffers()
-    import ctypes as C
-    p = lambda t: C.c_void_p(t.data_ptr())
-    rc = _lib.lib().cavoid_actor_run(env._h, roll.policy._h, roll._h, C.byref(b), p(roll._obs_buffers[0]), p(roll._obs_buffers[1]),
-                                     p(env.rewards), p(env.done), p(env.game_over), p(roll._act_out), p(roll._val_out), 2, 0, None)
-    assert rc == -4
-    rc = _lib.lib().cavoid_actor_run(env._h, roll.policy._h, roll._h, C.byref(b), p(roll._obs_buffers[0]), p(roll._obs_buffers[0]),
-                                     p(env.rewards), p(env.done), p(env.game_over), p(roll._act_out), p(roll._val_out), 2, 0, None)
-    assert rc == -1
+    assert tw.raw_run(tw.TILE, env, roll, pol, cur=0) == EUNSUPPORTED
+    assert tw.raw_run(tw.TILE, env, roll, pol, cur=0, same_buffer=True) == EINVAL
     roll.close(); env.close()
     # an env whose generator makes frozen-network agents: cavoid_actor_run (no second network) refuses it, cavoid_actor_run_mix carries it
-    env, _, _, roll = _make(64, 4, 1, False, gen_min_agents=2, gen_nonlearning_fraction=0.5, gen_frozen_fraction=0.5)
+    env, _, pol, roll = _make(64, 4, 1, False, gen_min_agents=2, gen_nonlearning_fraction=0.5, gen_frozen_fraction=0.5)
     assert roll.fused_available and "cavoid_actor_run_mix" in roll.actor_path
-    b = roll._actor_buffers()
-    rc = _lib.lib().cavoid_actor_run(env._h, roll.policy._h, roll._h, C.byref(b), p(roll._obs_buffers[0]), p(roll._obs_buffers[1]),
-                                     p(env.rewards), p(env.done), p(env.game_over), p(roll._act_out), p(roll._val_out), 2, 0, None)
-    assert rc == -4
+    assert tw.raw_run(tw.TILE, env, roll, pol, cur=0) == EUNSUPPORTED
     roll.run_fused(2)
     roll.close(); env.close()
 
@@ -303,14 +216,10 @@ def test_step_push_equals_step_then_push(N, W, reflush, over):
     assert len(ba) == len(bb) > 0 and ba.dropped == bb.dropped == 0
     if time_max > 5:
         rs.require_deep_flushes(bb.src.cpu().numpy(), time_max, "step_push N=%d W=%d reflush=%s" % (N, W, reflush))
-    ka, kb = np.lexsort(ba.src.cpu().numpy().T[::-1]), np.lexsort(bb.src.cpu().numpy().T[::-1])
-    for name in ("src", "x", "r", "a_index"):
-        assert np.array_equal(getattr(ba, name).cpu().numpy()[ka], getattr(bb, name).cpu().numpy()[kb]), name
+    tw.compare_drained(ba, bb, ("step_push", N, W, reflush))
     epa, epb = a.drain_episodes().cpu().numpy(), b.drain_episodes().cpu().numpy()
     assert len(epa) == len(epb) > 0
-    epa, epb = epa[np.lexsort(epa.T[::-1])], epb[np.lexsort(epb.T[::-1])]
-    assert np.array_equal(epa[:, 0], epb[:, 0]) and np.array_equal(epa[:, 2], epb[:, 2])
-    np.testing.assert_allclose(epa[:, 1], epb[:, 1], rtol=1e-6, atol=1e-6)
+    tw.compare_episode_records(epa, epb, ("step_push", N, W, reflush))
     for e, r in rolls:
         r.close(); e.close()
 

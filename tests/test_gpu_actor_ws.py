@@ -7,69 +7,30 @@ trainer; only the episode totals are compared to float32 rounding (they are accu
 
 The step-by-step form itself is pinned elsewhere: the weight_sharing kernels against PyTorch (test_gpu_policy_ws.py), env and rollout
 against the oracle and the reference's goldens (test_gpu_parity.py, test_gpu_rollout.py)."""
-import ctypes as C
-import os
-import subprocess
-import sys
-
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests import rollout_scripts as rs
+from tests import actor_twins as tw
+from tests.actor_twins import KS_TILE as KS, close as _close, same as _same
+from tests.gpu_support import EINVAL, EUNSUPPORTED, OK
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KS = (2, 1, 7, 16, 4) + (16,) * 14 + (3,)                    # odd counts too: the observation buffers alternate
-OK, EINVAL, EUNSUPPORTED = 0, -1, -4
+ARGS = ["--arch", "weight_sharing", "--agents", "4"]        # the train CLI's shape in this file
 
 
 def _make(W, N, M, seed, reflush=False, greedy=False, arch="weight_sharing", net_M=None, ws_crowd=False, time_max=5, **over):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
-    from rl_collision_avoidance_amd.config import EnvConfig
-    from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
-    from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
-    from rl_collision_avoidance_amd.ga3c.rollout import BatchedRollout
-
-    class Cfg(EnvConfig):
-        def __init__(self, m):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
-            self.MAX_NUM_OTHER_AGENTS_OBSERVED = m
-            EnvConfig.__init__(self)
-    cfg = Cfg(M)
-    env = BatchedCollisionAvoidanceEnv(W, cfg, device="cuda:0", seed=seed, **over)
-    torch.manual_seed(1234)
-    net = NetworkVP_rnn(cfg if net_M is None else Cfg(net_M), arch=arch).to("cuda:0")
-    pol = FusedPolicy(net, seed=77, ws_crowd=ws_crowd)
-    # skip_finished = not reflush: the fused kernel hands a result only to the rows that still need an action (with the re-flush quirk: to
-    # every row), exactly the rows the step-by-step path lists with skip_finished -- like is compared with like.  Short chunks: many
-    # flushes; room for every duplicate row of the re-flush quirk (a full buffer drops rows in arrival order, which legitimately differs).
-    roll = BatchedRollout(env, pol, reflush_done=reflush, greedy=greedy, time_max=time_max, dup_capacity=600000 if reflush else None,
-                          skip_finished=not reflush)
-    roll.reset()
-    return env, net, pol, roll
-
-
-def _same(a, b, what):
-    assert torch.equal(a, b), what
+    # short chunks: many flushes; the handle is the whole-row one unless a case asks for the ring handle
+    return tw.make(W, N, M, seed, reflush, greedy, arch=arch, net_M=net_M, ws_crowd=ws_crowd, time_max=time_max, **over)
 
 
 def _compare(env_a, a, env_b, b, total):
-    _same(a.obs, b.obs, ("obs", total))
-    for x, y in zip(env_a.get_state(), env_b.get_state()):
-        _same(x, y, ("state", total))
-    for name in ("episode", "rewards", "done", "game_over"):
-        _same(getattr(env_a, name), getattr(env_b, name), (name, total))
-    for name in ("x", "val", "ret", "act_ring", "emit_t"):
-        _same(getattr(a, name), getattr(b, name), (name, total))
-    assert a.step_index == b.step_index == total
+    tw.compare_twins(env_a, a, env_b, b, total, rings=tw.RINGS)         # (this form's tests never compared dup_count)
 
 
-def _close(*pairs):
-    for env, roll in pairs:
-        roll.close(); env.close()
+def _run(env, roll, pol, n_steps=2):
+    return tw.raw_run(tw.TILE_WS, env, roll, pol, n_steps)
 
 
 # (N, W, M, settings): the smallest shapes at which each part can go wrong
@@ -100,56 +61,17 @@ def _close(*pairs):
 def test_fused_ws_actor_equals_step_by_step(N, W, M, over):
     over = dict(over)
     reflush, greedy = over.pop("reflush", False), over.pop("greedy", False)
-    seed = 21
-    env_a, net_a, _, a = _make(W, N, M, seed, reflush, greedy, **over)
-    env_b, net_b, _, b = _make(W, N, M, seed, reflush, greedy, **over)
+    twin_a, twin_b = _make(W, N, M, 21, reflush, greedy, **over), _make(W, N, M, 21, reflush, greedy, **over)
+    a = twin_a[3]
     assert a.ws_fused_available, a.ws_fused_unavailable_reason
     assert not a.fused_available                             # (the default paths do not change)
-    for p, q in zip(net_a.parameters(), net_b.parameters()):
-        assert torch.equal(p, q)
-    _same(a.obs, b.obs, "first observation")
-    total = 0
-    for k in KS:
-        a.run_fused_ws(k)
-        for _ in range(k):
-            b.step()
-        total += k
-        if total > 40 and total % 64:                        # (full comparisons early on, then every fourth launch)
-            continue
-        _compare(env_a, a, env_b, b, total)
-    _compare(env_a, a, env_b, b, total)
-    assert env_a.episode.max().item() >= 1                   # restarts are inside what was compared
-    # what reaches the trainer and the stats process
-    ba, bb = a.drain(flush_all=True), b.drain(flush_all=True)
-    assert len(ba) == len(bb) > 0 and ba.dropped == bb.dropped == 0
-    if over.get("time_max", 5) > 5:
-        rs.require_deep_flushes(bb.src.cpu().numpy(), over["time_max"], "ws actor N=%d W=%d reflush=%s" % (N, W, reflush))
-    ka = np.lexsort(ba.src.cpu().numpy().T[::-1])
-    kb = np.lexsort(bb.src.cpu().numpy().T[::-1])
-    for name in ("src", "x", "r", "a_index"):
-        assert np.array_equal(getattr(ba, name).cpu().numpy()[ka], getattr(bb, name).cpu().numpy()[kb]), name
-    ea, eb = a.drain_episodes().cpu().numpy(), b.drain_episodes().cpu().numpy()
-    assert len(ea) == len(eb) > 0
-    ea, eb = ea[np.lexsort(ea.T[::-1])], eb[np.lexsort(eb.T[::-1])]
-    assert np.array_equal(ea[:, 0], eb[:, 0]) and np.array_equal(ea[:, 2], eb[:, 2])
-    np.testing.assert_allclose(ea[:, 1], eb[:, 1], rtol=1e-6, atol=1e-6)
-    # and the two forms interleave: each continues where the other stopped
-    a.step(); a.run_fused_ws(3)
-    b.run_fused_ws(2); b.step(); b.step()
-    _same(a.obs, b.obs, "interleaved obs")
-    _same(a.emit_t, b.emit_t, "interleaved emit_t")
-    _close((env_a, a), (env_b, b))
-
-
-def _run(env, roll, pol, n_steps=2):
-    from rl_collision_avoidance_amd import _lib
-    p = lambda t: C.c_void_p(t.data_ptr())
-    b = roll._actor_buffers()
-    cur, nxt = roll._obs_buffers[roll._cur], roll._obs_buffers[1 - roll._cur]
-    rc = _lib.lib().cavoid_actor_run_ws(env._h, pol._h, roll._h, C.byref(b), p(cur), p(nxt), p(env.rewards), p(env.done), p(env.game_over),
-                                        p(roll._act_out), p(roll._val_out), n_steps, 0, None)
-    torch.cuda.synchronize()
-    return rc
+    time_max = over.get("time_max", 5)
+    tw.fused_equals_step_by_step(
+        tw.TILE_WS, twin_a, twin_b, ("ws actor", N, W, M, reflush), ks=KS,
+        compare_at=lambda total: total <= 40 or total % 64 == 0,         # (full comparisons early on, then every fourth launch)
+        compare_at_end=True, rings=tw.RINGS,                             # (restarts are inside what was compared; no dup_count in this form's test)
+        deep_flushes=(time_max, "ws actor N=%d W=%d reflush=%s" % (N, W, reflush)) if time_max > 5 else None,
+        interleave=tw.INTERLEAVE_TILE)
 
 
 @pytest.mark.parametrize("N", range(1, 17))
@@ -171,15 +93,9 @@ def test_availability_agrees_with_the_entry_point_for_every_agent_count(N):
 
 def test_fused_ws_actor_graph_replay_equals_eager_calls():
     """`capture_fused_ws`: the K-step launch as a one-node hipGraph; replays advance the device-side counters like eager calls."""
-    env_a, _, _, a = _make(130, 4, 7, 3)
-    env_b, _, _, b = _make(130, 4, 7, 3)
-    a.capture_fused_ws(steps_per_graph=4)        # (runs 2 warm-up steps outside the capture)
-    b.run_fused_ws(2)
-    a.replay(6)
-    for _ in range(6):
-        b.run_fused_ws(4)
-    _compare(env_a, a, env_b, b, 26)
-    _close((env_a, a), (env_b, b))
+    twin_a, twin_b = _make(130, 4, 7, 3), _make(130, 4, 7, 3)
+    tw.graph_replay(tw.TILE_WS, twin_a, twin_b, 6, _compare)            # (compared at step 2 + 6 * 4 = 26)
+    _close((twin_a[0], twin_a[3]), (twin_b[0], twin_b[3]))
 
 
 def test_a_masked_reset_between_two_fused_ws_launches_needs_no_flag_fixup():
@@ -237,12 +153,7 @@ def test_fused_ws_actor_refuses_what_it_does_not_carry():
     def refused(word, *args, **kw):
         env, _, pol, roll = _make(*args, **kw)
         made.append((env, roll))
-        why = roll.ws_fused_unavailable_reason
-        assert why is not None and word in why, why
-        with pytest.raises(RuntimeError) as err:
-            roll.run_fused_ws(2)
-        assert why in str(err.value)
-        assert _run(env, roll, pol) == EUNSUPPORTED          # straight at the C ABI: a code, not a crash
+        tw.refused(tw.TILE_WS, env, pol, roll, EUNSUPPORTED, word, reason_in_error=True)
     refused("rnn network", 32, 4, 3, 1, arch="rnn")
     refused("ring", 32, 4, 24, 1, ws_crowd=True)             # a 4-agent env padded to M = 24: the ring handle
     refused("20 agents per world", 8, 20, 7, 1)
@@ -265,41 +176,25 @@ def test_fused_ws_actor_refuses_what_it_does_not_carry():
     made.append((env_m, roll_m))
     assert "the env's rows carry 7" in roll_m.ws_fused_unavailable_reason and _run(env_m, roll_m, pol_m) == EINVAL
     roll.run_fused_ws(3)
-    before = [t.clone() for t in (roll._obs_buffers[0], roll._obs_buffers[1], roll.x, roll.emit_t, env.episode, env.rewards, *env.get_state())]
-    assert _run(env, roll, pol, n_steps=0) == OK
-    after = [roll._obs_buffers[0], roll._obs_buffers[1], roll.x, roll.emit_t, env.episode, env.rewards, *env.get_state()]
-    assert all(torch.equal(u, v) for u, v in zip(before, after))
+    tensors = lambda: (roll._obs_buffers[0], roll._obs_buffers[1], roll.x, roll.emit_t, env.episode, env.rewards, *env.get_state())
+    assert tw.unchanged_by(lambda: _run(env, roll, pol, n_steps=0), tensors, "cavoid_actor_run_ws with n_steps = 0") == OK
     _close(*made)
 
 
-def _train(tmp_path, extra):
-    cmd = [sys.executable, "-m", "rl_collision_avoidance_amd.ga3c.train", "--arch", "weight_sharing", "--agents", "4", "--worlds", "64",
-           "--episodes", "300", "--pretrain-steps", "0", "--print-every", "100", "--train-rows", "2048",
-           "--checkpoint-dir", str(tmp_path / "ck")] + extra
-    env = dict(os.environ)
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    run = subprocess.run(cmd, cwd=ROOT, env=env, timeout=300, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(run.stdout[-3000:])
-    return run
-
-
 def test_train_cli_with_the_flag_runs_the_ws_actor_kernel(tmp_path):
-    run = _train(tmp_path, ["--fused-ws-actor"])
-    assert run.returncode == 0
-    assert "actors: fused weight_sharing actor kernel (cavoid_actor_run_ws), 4 env steps per launch" in run.stdout
-    assert "finished" in run.stdout and " 0 training steps" not in run.stdout
+    tw.train_cli_runs_the_kernel(tmp_path, ARGS + ["--fused-ws-actor"],
+                                 "actors: fused weight_sharing actor kernel (cavoid_actor_run_ws), 4 env steps per launch")
 
 
 def test_train_cli_without_the_flag_prints_todays_line(tmp_path):
-    run = _train(tmp_path, [])
-    assert run.returncode == 0
-    assert ("actors: one launch per phase (policy, env + bookkeeping) -- fused kernel not applicable: the policy is the weight_sharing network "
-            "(the fused actor kernel embeds the LSTM pass; its kernel acts step by step); in a hipGraph, 4 env steps per graph") in run.stdout
-    assert "cavoid_actor_run_ws" not in run.stdout and "finished" in run.stdout
+    tw.train_cli_prints_todays_line(
+        tmp_path, ARGS,
+        "actors: one launch per phase (policy, env + bookkeeping) -- fused kernel not applicable: the policy is the weight_sharing network "
+        "(the fused actor kernel embeds the LSTM pass; its kernel acts step by step); in a hipGraph, 4 env steps per graph", "cavoid_actor_run_ws")
 
 
 def test_train_cli_with_the_flag_ends_where_the_kernel_does_not_apply(tmp_path):
-    run = _train(tmp_path, ["--fused-ws-actor", "--scripted-fraction", "0.5", "--frozen-fraction", "0.5"])
+    run = tw.train_cli(tmp_path, ARGS + ["--fused-ws-actor", "--scripted-fraction", "0.5", "--frozen-fraction", "0.5"])
     assert run.returncode != 0
     assert "--fused-ws-actor: the weight_sharing actor kernel (cavoid_actor_run_ws) does not apply: frozen-network agents" in run.stdout
     assert "actors:" not in run.stdout

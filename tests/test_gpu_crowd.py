@@ -14,7 +14,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from oracle import c_oracle as co
-from tests.test_gpu_parity import OBS_TOL, _compare_step, _env, _goal_seeking_actions, _pull, _push
+from tests.gpu_support import OBS_TOL, _compare_step, _env, _goal_seeking_actions, _pull, _push
 
 pytestmark = pytest.mark.gpu
 
@@ -321,7 +321,7 @@ def test_crowd_rollout_with_the_fused_policy_and_the_torch_network():
 _DRIFT_CHILD = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, sys.argv[2])
-from tests.test_gpu_parity import _env
+from tests.gpu_support import _env
 # (tag, M offset from N - 1, overrides): the default configuration; closest_first with GEN v2 generated inside the step, the max-turn-rate
 # dynamics and U2 / U4 / U7b flipped; time-to-impact with exact gaps, a finite horizon, clipping, evaluate mode and the U1 / U5 / U11
 # switches; holonomic dynamics (continuous actions only)

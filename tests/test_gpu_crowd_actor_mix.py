@@ -8,16 +8,21 @@ rounding (unordered double atomics), as in tests/test_gpu_crowd_actor.py, whose 
 
 Every case sets max_time_ratio = 0.1, so that worlds end and restart inside the run, and asserts on the step-by-step side that a running
 frozen-network row was listed at some step, that episodes ended, rows were drained and episode records written: nothing passes on nothing."""
-import ctypes as C
-
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.test_gpu_crowd_actor import FAST, KS, _compare, _make, _same
+from tests import actor_twins as tw
+from tests.actor_twins import FAST, KS, compare_twins as _compare, same as _same
+from tests.gpu_support import EINVAL, EUNSUPPORTED, OK
 
 pytestmark = pytest.mark.gpu
+
+
+def _make(W, N, M, seed, reflush, greedy=False, net_M=None, arch="rnn", frozen=False, time_max=5, **over):
+    # tests/test_gpu_crowd_actor.py's twin: room for every duplicate row of the re-flush quirk, at most one per slot and step
+    return tw.make(W, N, M, seed, reflush, greedy, arch=arch, net_M=net_M, ws_crowd=False, frozen="rnn" if frozen else False,
+                   dup_capacity=W * N * 160, time_max=time_max, **over)
 
 MIX = dict(gen_nonlearning_fraction=0.5, gen_frozen_fraction=0.5)            # (with the default static share: about a quarter frozen-network agents)
 # ORCA agents AND frozen-network agents: the settings of tests/test_gpu_crowd_ws_eval.py (the default static share leaves no room for them)
@@ -52,60 +57,23 @@ def _frozen_rows_spy(env):
     (33, 520, 32, False, False, dict(**MIX)),                                  # 520 workgroups: two per CU on every CU
 ])
 def test_fused_crowd_mix_actor_equals_step_by_step(N, W, M, reflush, greedy, over):
-    seed = 21
-    env_a, net_a, pol_a, a = _make(W, N, M, seed, reflush, greedy, frozen=True, **FAST, **over)
-    env_b, net_b, pol_b, b = _make(W, N, M, seed, reflush, greedy, frozen=True, **FAST, **over)
+    twin_a = _make(W, N, M, 21, reflush, greedy, frozen=True, **FAST, **over)
+    twin_b = _make(W, N, M, 21, reflush, greedy, frozen=True, **FAST, **over)
+    env_a, _, pol_a, a = twin_a
     assert a.crowd_mix_fused_available, a.crowd_mix_fused_unavailable_reason
     assert not a.fused_available and not a.crowd_fused_available                 # (the existing switches say what they said)
     assert "frozen-network agents" in a.crowd_fused_unavailable_reason
     assert pol_a.max_others == M == env_a.cfg.max_other == a.frozen_policy.max_others
-    for p, q in zip(net_a.parameters(), net_b.parameters()):
-        assert torch.equal(p, q)
-    _same(a.obs, b.obs, "first observation")
-    listed = _frozen_rows_spy(env_b)
-    form = ("CROWD_RVO", 0) if over.get("rvo_enabled") else ("CROWD", 0)
-    total = 0
-    for k in KS:
-        a.run_fused_crowd_mix(k)
-        for _ in range(k):
-            b.step()
-        total += k
-        _compare(env_a, a, env_b, b, total)
-        assert env_a.last_step_form == form and env_b.last_step_form == form
-    # the step-by-step side (the code of before) did what the case is about: nothing below passes on nothing
-    frozen_seen = torch.stack(listed).view(-1).cpu().numpy()
-    dup_b = b.dup_count.tolist()
-    ba, bb = a.drain(flush_all=True), b.drain(flush_all=True)
-    ea, eb = a.drain_episodes().cpu().numpy(), b.drain_episodes().cpu().numpy()
-    print("crowd mix actor N=%d W=%d M=%d: step-by-step side: frozen rows listed at %d of %d steps (max %d), episode max %d, drained %d rows, "
-          "%d duplicates (%d dropped), %d episode records" % (N, W, M, int((frozen_seen > 0).sum()), len(frozen_seen), int(frozen_seen.max()),
-                                                              env_b.episode.max().item(), len(bb), dup_b[0], dup_b[1], len(eb)))
-    assert len(frozen_seen) == total and int(frozen_seen.max()) >= 1
-    assert env_b.episode.max().item() >= 1
-    assert len(bb) > 0 and len(eb) > 0
-    assert dup_b[1] == 0 and (dup_b[0] > 0 if reflush else dup_b[0] == 0)
-    # what reaches the trainer and the stats process
-    assert len(ba) == len(bb) and ba.dropped == bb.dropped == 0
-    ka = np.lexsort(ba.src.cpu().numpy().T[::-1])
-    kb = np.lexsort(bb.src.cpu().numpy().T[::-1])
-    for name in ("src", "x", "r", "a_index"):
-        assert np.array_equal(getattr(ba, name).cpu().numpy()[ka], getattr(bb, name).cpu().numpy()[kb]), name
-    assert len(ea) == len(eb)
-    ea, eb = ea[np.lexsort(ea.T[::-1])], eb[np.lexsort(eb.T[::-1])]
-    assert np.array_equal(ea[:, 0], eb[:, 0]) and np.array_equal(ea[:, 2], eb[:, 2])
-    np.testing.assert_allclose(ea[:, 1], eb[:, 1], rtol=1e-6, atol=1e-6)         # (double atomics whose order varies)
-    # and the two forms interleave: each continues where the other stopped
-    a.step(); a.run_fused_crowd_mix(3)
-    b.run_fused_crowd_mix(2); b.step(); b.step()
-    _same(a.obs, b.obs, "interleaved obs")
-    for x, y in zip(env_a.get_state(), env_b.get_state()):
-        _same(x, y, "interleaved state")
-    for name in ("x", "val", "ret", "act_ring", "emit_t"):
-        _same(getattr(a, name), getattr(b, name), ("interleaved", name))
-    for r in (a, b):
-        r.close()
-    for e in (env_a, env_b):
-        e.close()
+    listed = _frozen_rows_spy(twin_b[0])
+
+    def frozen_rows_listed(total):                           # the step-by-step side listed a running frozen-network row at some step
+        frozen_seen = torch.stack(listed).view(-1).cpu().numpy()
+        assert len(frozen_seen) == total and int(frozen_seen.max()) >= 1
+        return "frozen rows listed at %d of %d steps (max %d), " % (int((frozen_seen > 0).sum()), len(frozen_seen), int(frozen_seen.max()))
+    tw.fused_equals_step_by_step(
+        tw.CROWD_MIX, twin_a, twin_b, ("crowd mix actor", N, W, M, reflush), ks=KS,
+        step_form=("CROWD_RVO", 0) if over.get("rvo_enabled") else ("CROWD", 0),
+        check_step_side=tw.step_side("crowd mix actor", N, W, M, reflush, extra=frozen_rows_listed))
 
 
 def test_without_frozen_agents_the_mix_launch_equals_the_one_network_launch():
@@ -135,50 +103,25 @@ def test_without_frozen_agents_the_mix_launch_equals_the_one_network_launch():
 def test_fused_crowd_mix_graph_replay_equals_step_by_step(N, W, M):
     """`capture_fused_crowd_mix(4)`: the K-step launch as a one-node hipGraph against step(); replays advance the device-side counters like
     eager calls -- one more step() on each side lands in the same ring block and draws the same actions only if both counters agree."""
-    env_a, _, _, a = _make(W, N, M, 3, False, frozen=True, **FAST, **MIX)
-    env_b, _, _, b = _make(W, N, M, 3, False, frozen=True, **FAST, **MIX)
-    listed = _frozen_rows_spy(env_b)
-    a.capture_fused_crowd_mix(steps_per_graph=4)      # (runs 2 warm-up steps outside the capture)
-    a.replay(3)
-    for _ in range(14):
-        b.step()
-    _compare(env_a, a, env_b, b, 14)
-    a.step(); b.step()
-    _compare(env_a, a, env_b, b, 15)
-    assert (a.emit_t >= 0).any() and int(torch.stack(listed).max()) >= 1
-    with pytest.raises(ValueError):
-        a.capture_fused_crowd_mix(steps_per_graph=3)
-    for r in (a, b):
-        r.close()
-    env_a.close(); env_b.close()
+    twin_a, twin_b = _make(W, N, M, 3, False, frozen=True, **FAST, **MIX), _make(W, N, M, 3, False, frozen=True, **FAST, **MIX)
+    listed = _frozen_rows_spy(twin_b[0])
+    tw.graph_replay(tw.CROWD_MIX, twin_a, twin_b, 3, _compare, eager=False, one_more_step=True, refused_steps_per_graph=3)
+    assert int(torch.stack(listed).max()) >= 1
+    tw.close((twin_a[0], twin_a[3]), (twin_b[0], twin_b[3]))
 
 
 def _run(env, roll, pol, fz, n_steps=2):
-    from rl_collision_avoidance_amd import _lib
-    p = lambda t: C.c_void_p(t.data_ptr())
-    b = roll._actor_buffers()
-    rc = _lib.lib().cavoid_crowd_actor_run_mix(env._h, pol._h, fz._h if fz is not None else None, roll._h, C.byref(b), p(roll._obs_buffers[0]),
-                                               p(roll._obs_buffers[1]), p(env.rewards), p(env.done), p(env.game_over), p(roll._act_out),
-                                               p(roll._val_out), n_steps, 0, None)
-    torch.cuda.synchronize()
-    return rc
+    return tw.raw_run(tw.CROWD_MIX, env, roll, pol, n_steps, fz=fz, cur=0)
 
 
 def test_fused_crowd_mix_actor_refuses_what_it_does_not_carry():
     from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
     from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
-    OK, EINVAL, EUNSUPPORTED = 0, -1, -4
     made = []
 
     def refused(code, word, env, pol, roll, fz):
         made.append((env, roll))
-        assert word in roll.crowd_mix_fused_unavailable_reason, roll.crowd_mix_fused_unavailable_reason
-        assert not roll.crowd_mix_fused_available
-        with pytest.raises(RuntimeError, match="run_fused_crowd_mix does not apply"):
-            roll.run_fused_crowd_mix(2)
-        state = [t.clone() for t in env.get_state()]
-        assert _run(env, roll, pol, fz) == code                  # straight at the C ABI: a code, not a crash
-        assert all(torch.equal(u, v) for u, v in zip(state, env.get_state()))
+        tw.refused(tw.CROWD_MIX, env, pol, roll, code, word, fz=fz, cur=0, error_match="run_fused_crowd_mix does not apply", state_untouched=True)
 
     env, _, pol, roll = _make(32, 4, 3, 1, False, frozen=True, **MIX)                # a tile env: cavoid_actor_run_mix carries it
     refused(EUNSUPPORTED, "cavoid_actor_run_mix", env, pol, roll, roll.frozen_policy)
@@ -216,10 +159,8 @@ def test_fused_crowd_mix_actor_refuses_what_it_does_not_carry():
     env, _, pol, roll = _make(24, 20, 19, 1, False, frozen=True, **MIX)
     made.append((env, roll))
     roll.run_fused_crowd_mix(3)
-    before = [t.clone() for t in (roll._obs_buffers[0], roll._obs_buffers[1], roll.x, roll.emit_t, env.episode, env.rewards, *env.get_state())]
-    assert _run(env, roll, pol, roll.frozen_policy, n_steps=0) == OK
-    assert _run(env, roll, pol, None, n_steps=0) == EINVAL
-    after = [roll._obs_buffers[0], roll._obs_buffers[1], roll.x, roll.emit_t, env.episode, env.rewards, *env.get_state()]
-    assert all(torch.equal(u, v) for u, v in zip(before, after))
-    for e, r in made:
-        r.close(); e.close()
+    tensors = lambda: (roll._obs_buffers[0], roll._obs_buffers[1], roll.x, roll.emit_t, env.episode, env.rewards, *env.get_state())
+    codes = tw.unchanged_by(lambda: (_run(env, roll, pol, roll.frozen_policy, n_steps=0), _run(env, roll, pol, None, n_steps=0)), tensors,
+                            "cavoid_crowd_actor_run_mix with n_steps = 0")
+    assert codes == (OK, EINVAL)
+    tw.close(*made)

@@ -16,7 +16,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests import cfg_regimes as R
-from tests.test_gpu_parity import _env
+from tests.gpu_support import _env
 
 pytestmark = pytest.mark.gpu
 

@@ -17,13 +17,12 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.test_gpu_eval_fused import BIAS, MAX_STEPS, NETS, _StepLog, _assert_same, _outcomes
-from tests.test_gpu_parity import _env as _crowd_env
+from tests import eval_twins as tw
+from tests.eval_twins import MAX_STEPS, _not_over, _outcomes
+from tests.gpu_support import EINVAL, EUNSUPPORTED, OK, ROOT, _env as _crowd_env
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED = 0, -1, -4
 ORCA = dict(rvo_enabled=2, gen_rvo_fraction=0.5, gen_nonlearning_fraction=0.5)
 
 # name: (N, W, M, env settings, network, max_time_ratio, steps per launch).  The shapes are the smallest at which the lane mapping, the
@@ -56,14 +55,7 @@ CASES = {
 SAMPLED = ("n22_box", 7)             # the sampled case: greedy=False on this shape
 
 
-def _policy(cfg, net, seed=1234, policy_seed=77):
-    from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
-    from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
-    model = NetworkVP_rnn(cfg, seed=seed).to("cuda:0")
-    if NETS[net] is not None:
-        with torch.no_grad():
-            model.p_bias[NETS[net]] += BIAS
-    return FusedPolicy(model, seed=policy_seed)
+_policy = tw.policy
 
 
 def _make(name, **more):
@@ -72,57 +64,10 @@ def _make(name, **more):
     return env, _policy(env.config, net)
 
 
-_REFS = {}
-
-
-def _reference(name, greedy=True, max_steps=MAX_STEPS):
-    """evaluate(details=True) of one case, step by step: result, final world buffer, the step log, env.obs at the end -- computed once"""
-    from rl_collision_avoidance_amd.ga3c.evaluate import evaluate
-    key = (name, greedy, max_steps)
-    if key not in _REFS:
-        env, pol = _make(name)
-        log = _StepLog(env)
-        res = evaluate(env, pol, rounds=1, greedy=greedy, max_steps=max_steps, details=True)
-        _REFS[key] = (res, [t.clone() for t in env.get_state()], log, env.obs.clone())
-        pol.close(); env.close()
-    return _REFS[key]
-
-
-def _fused(name, spl, greedy=True, max_steps=MAX_STEPS, monkeypatch=None):
-    """the same round on the kernel; with it the observation buffer as the LAST LAUNCH left it (before evaluate() settles the env)"""
-    from rl_collision_avoidance_amd.ga3c import evaluate as ev
-    env, pol = _make(name)
-    assert ev.evaluate_fused_crowd_unavailable_reason(env, pol) is None
-    seen = {}
-    settle = ev._settle_finished
-
-    def spy(env_, world_steps, env_steps):
-        seen["obs"], seen["world_steps"], seen["env_steps"] = env_.obs.clone(), world_steps.clone(), env_steps
-        return settle(env_, world_steps, env_steps)
-    ev._settle_finished = spy
-    try:
-        res = ev.evaluate(env, pol, rounds=1, greedy=greedy, max_steps=max_steps, fused_crowd=True, steps_per_launch=spl, details=True)
-    finally:
-        ev._settle_finished = settle
-    state = [t.clone() for t in env.get_state()]
-    form = env.last_step_form
-    pol.close(); env.close()
-    return res, state, seen, form
-
-
-def _same_round(name, spl, greedy=True, max_steps=MAX_STEPS):
-    N, W = CASES[name][0], CASES[name][1]
-    ref, ref_state, log, ref_obs = _reference(name, greedy, max_steps)
-    got, got_state, seen, _ = _fused(name, spl, greedy, max_steps)
-    _assert_same(ref, ref_state, got, got_state, (name, spl, greedy), log)
-    # the records: the step at which each world was over
-    ws = log.world_steps().to(seen["world_steps"].device)
-    assert torch.equal(seen["world_steps"], ws), (name, spl, "world_steps")
-    assert seen["env_steps"] == ref["env_steps"]
-    # the observation of the worlds that ended at the round's last step (or were cut there): the loop stepped them last at that step too
-    last = (ws == ref["env_steps"]).nonzero().flatten()
-    assert last.numel() >= 1
-    assert torch.equal(seen["obs"].view(W, N, -1)[last], ref_obs.view(W, N, -1)[last]), (name, spl, "obs of the worlds that ended last")
+# the step-by-step round of every case is computed once (family "crowd_eval" of the one cache); no frozen policy in this form
+ROUNDS = tw.CrowdRounds("crowd_eval", CASES, lambda name: _make(name) + (None,), switch="fused_crowd",
+                        reason="evaluate_fused_crowd_unavailable_reason", run="eval_run_crowd")
+_reference, _same_round = ROUNDS.reference, ROUNDS.same_round
 
 
 def test_the_step_by_step_rounds_are_not_empty():
@@ -132,7 +77,7 @@ def test_the_step_by_step_rounds_are_not_empty():
     from rl_collision_avoidance_amd.ga3c.evaluate import OUTCOME_COLLISION, OUTCOME_GOAL, OUTCOME_TIMEOUT
     seen, paid = set(), 0
     for name, (N, W, M, over, net, ratio, _) in CASES.items():
-        res, state, log, _ = _reference(name)
+        res, state, log, _, _ = _reference(name)
         ws = log.world_steps()
         masked, paid_after = log.masked_return(N)
         out = _outcomes(res)
@@ -165,36 +110,11 @@ def test_sampled_evaluation():
 
 def test_round_cut_at_max_steps():
     """max_steps = 10 with launches of 7: the last launch is cut to 3, and the round equals the step-by-step round cut at 10"""
-    from rl_collision_avoidance_amd.ga3c import evaluate as ev
-    name = "n17_three_worlds"
-    launches = []
-    run = ev.eval_run_crowd
-
-    def spy(env, policy, frozen_policy, rec, n_steps, greedy=True):
-        launches.append(n_steps)
-        run(env, policy, frozen_policy, rec, n_steps, greedy)
-    ev.eval_run_crowd = spy
-    try:
-        _same_round(name, 7, max_steps=10)
-    finally:
-        ev.eval_run_crowd = run
-    assert launches == [7, 3]
-    assert _reference(name, max_steps=10)[0]["env_steps"] == 10
+    ROUNDS.cut_at_max_steps("n17_three_worlds")
 
 
 def _raw(env, pol, rec, n, greedy=1, buffers=None):
-    from rl_collision_avoidance_amd import _lib
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    return _lib.lib().cavoid_crowd_eval_run(env._h, pol._h if pol is not None else None, C.byref(buffers if buffers is not None else rec.c),
-                                            p(env.obs), p(env.rewards), p(env.done), p(env.game_over), p(rec.actions), p(rec.values), n, greedy,
-                                            env._stream())
-
-
-def _not_over(env):
-    """worlds not over, from the world buffer: cavoid_step's game_over predicate in EVALUATE_MODE"""
-    from rl_collision_avoidance_amd import _lib
-    fl = env.get_state()[2].view(env.num_worlds, env.max_agents)
-    return (((fl & _lib.F_PRESENT) != 0) & ((fl & _lib.F_DONE_MASK) == 0)).any(1)
+    return tw.raw("cavoid_crowd_eval_run", env, pol, rec, n, greedy=greedy, buffers=buffers)
 
 
 def test_launch_edges_at_the_raw_entry_point():
@@ -251,7 +171,7 @@ def test_launch_edges_at_the_raw_entry_point():
     assert all(torch.equal(a, b) for a, b in zip(before, after))
     assert int(rec.worlds_running.item()) == 0
     # the records are the step-by-step round's
-    ref, _, log, _ = _reference(name)
+    ref, _, log, _, _ = _reference(name)
     assert torch.equal(rec.world_steps, log.world_steps().to(rec.world_steps.device))
     assert torch.equal(rec.ret, log.masked_return(N)[0])
     pol.close(); env.close()
@@ -363,24 +283,12 @@ def test_the_entry_point_refuses_a_non_default_product_form(tmp_path):
     assert run.returncode == 0 and run.stdout.strip().endswith("REFUSED")
 
 
-def _cli(extra):
-    cmd = [sys.executable, "-m", "rl_collision_avoidance_amd.ga3c.train", "--agents", "20", "--worlds", "64", "--evaluate", "1"] + extra
-    env = dict(os.environ)
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    run = subprocess.run(cmd, cwd=ROOT, env=env, timeout=300, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(run.stdout[-3000:])
-    assert run.returncode == 0
-    return run.stdout
-
-
 def test_train_cli_runs_the_kernel_and_prints_the_same_result():
-    fused, plain = _cli(["--fused-crowd-evaluate"]), _cli([])
+    fused, plain = tw.cli(["--agents", "20", "--worlds", "64", "--fused-crowd-evaluate"]), tw.cli(["--agents", "20", "--worlds", "64"])
     assert "[Evaluate] fused crowd evaluation kernel (cavoid_crowd_eval_run), 4 env steps per launch" in fused
     assert "cavoid_crowd_eval_run" not in plain
-    last = lambda out: [l for l in out.splitlines() if l.startswith("[Evaluate] agents ")]
+    last, strip = tw.last_evaluate_line, tw.without_mean_reward
     assert len(last(fused)) == 1 and len(last(plain)) == 1
-    # mean_reward is the one figure the two definitions of the return may tell apart (include/cavoid.h): left out of the comparison
-    strip = lambda line: " ".join(w for w in line.replace("mean_reward ", "mean_reward=").split("  ") if not w.startswith("mean_reward="))
     assert strip(last(fused)[0]) == strip(last(plain)[0])
     assert "success_rate" in strip(last(fused)[0]) and "mean_reward" not in strip(last(fused)[0])
 
@@ -392,3 +300,4 @@ def test_train_cli_with_the_flag_ends_where_the_kernel_does_not_apply():
         train.main(["--agents", "4", "--worlds", "64", "--evaluate", "1", "--fused-crowd-evaluate"])
     with pytest.raises(SystemExit, match="--fused-crowd-evaluate.*not a FusedPolicy"):
         train.main(["--agents", "20", "--worlds", "64", "--evaluate", "1", "--fused-crowd-evaluate", "--torch-policy"])
+    tw.report_cache("crowd_eval")  # (a whole run of this file: 10 cases, the sampled round, the round cut at 10 steps: 12)

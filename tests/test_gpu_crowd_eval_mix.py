@@ -11,18 +11,16 @@ definitions the README states (tests/test_gpu_eval_fused.py's `_assert_same`).  
 The step-by-step result of every case is computed once and shared; with it, per step, the host notes from the world buffer's flags which
 tiles had no learner row left that needs an action but a running frozen-network row: the steps at which the kernel runs the frozen pass
 alone."""
-import ctypes as C
-
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.test_gpu_crowd_eval import MAX_STEPS, _StepLog, _assert_same, _policy
-from tests.test_gpu_parity import _env as _crowd_env
+from tests import eval_twins as tw
+from tests.eval_twins import MAX_STEPS, policy as _policy
+from tests.gpu_support import EINVAL, EUNSUPPORTED, OK, _env as _crowd_env
 
 pytestmark = pytest.mark.gpu
 
-OK, EINVAL, EUNSUPPORTED = 0, -1, -4
 MIX = dict(gen_nonlearning_fraction=0.5, gen_frozen_fraction=0.5)            # (with the default static share: about a quarter frozen-network agents)
 # ORCA agents AND frozen-network agents: the settings of tests/test_gpu_crowd_ws_eval.py (the default static share leaves no room for them)
 ORCA_MIX = dict(rvo_enabled=2, gen_rvo_fraction=0.5, gen_static_fraction=0.1, gen_frozen_fraction=0.3, gen_nonlearning_fraction=0.5)
@@ -46,82 +44,43 @@ def _make(name):
     return env, _policy(env.config, net), _policy(env.config, "free", seed=4321, policy_seed=0)
 
 
-def _close(env, pol, fz):
-    pol.close(); fz.close(); env.close()
+_close = tw.close
 
 
-_REFS = {}
-
-
-def _reference(name, greedy=True, max_steps=MAX_STEPS):
-    """evaluate(frozen_policy=fz, details=True) of one case, step by step: result, final world buffer, the step log, env.obs at the end, and
-    per step (frozen rows listed, tiles with a running frozen-network row and no learner row that needs an action) -- computed once"""
+def _frozen_pass_alone(env, name):
+    """per step of the step-by-step round: (frozen rows listed, tiles with a running frozen-network row and no learner row that needs an
+    action), noted from the world buffer's flags BEFORE the step"""
     from rl_collision_avoidance_amd import _lib
-    from rl_collision_avoidance_amd.ga3c.evaluate import evaluate
-    key = (name, greedy, max_steps)
-    if key not in _REFS:
-        N, W = CASES[name][0], CASES[name][1]
-        env, pol, fz = _make(name)
-        log = _StepLog(env)
-        per_step = []
-        rows_of = env.policy_rows
-        wpw = 64 // N
-        tiles = (W + wpw - 1) // wpw
-
-        def spy(policy_id, only_running=True):
-            out = rows_of(policy_id, only_running)
-            if policy_id == _lib.POLICY_FROZEN_NET:
-                fl = env.get_state()[2].view(-1).long()                                  # the state BEFORE this step
-                live = ((fl & _lib.F_PRESENT) != 0) & ((fl & _lib.F_LEARNING) != 0) & ((fl & _lib.F_DONE_MASK) == 0)
-                frozen = torch.zeros_like(live)
-                frozen[out[0][:int(out[1].item())].long()] = True
-                pol4 = ((fl >> _lib.F_POLICY_SHIFT) & _lib.F_POLICY_MASK) == _lib.POLICY_FROZEN_NET
-                assert bool((frozen == (pol4 & ((fl & _lib.F_PRESENT) != 0) & ((fl & _lib.F_DONE_MASK) == 0))).all())   # (the kernel's predicate)
-                pad = tiles * wpw * N - W * N
-                tile = lambda m: torch.cat([m, m.new_zeros(pad)]).view(tiles, wpw * N).any(1)
-                per_step.append((int(frozen.sum()), int((tile(frozen) & ~tile(live)).sum())))
-            return out
-        env.policy_rows = spy
-        res = evaluate(env, pol, rounds=1, greedy=greedy, max_steps=max_steps, frozen_policy=fz, details=True)
-        _REFS[key] = (res, [t.clone() for t in env.get_state()], log, env.obs.clone(), per_step)
-        _close(env, pol, fz)
-    return _REFS[key]
-
-
-def _fused(name, spl, greedy=True, max_steps=MAX_STEPS):
-    """the same round on the kernel; with it the observation buffer as the LAST LAUNCH left it (before evaluate() settles the env)"""
-    from rl_collision_avoidance_amd.ga3c import evaluate as ev
-    env, pol, fz = _make(name)
-    assert ev.evaluate_fused_crowd_mix_unavailable_reason(env, pol, fz) is None     # (no case passes by falling back: the call would raise, too)
-    assert "frozen_policy" in ev.evaluate_fused_crowd_unavailable_reason(env, pol, fz)   # (the one-network switch goes on refusing)
-    seen = {}
-    settle = ev._settle_finished
-
-    def spy(env_, world_steps, env_steps):
-        seen["obs"], seen["world_steps"], seen["env_steps"] = env_.obs.clone(), world_steps.clone(), env_steps
-        return settle(env_, world_steps, env_steps)
-    ev._settle_finished = spy
-    try:
-        res = ev.evaluate(env, pol, rounds=1, greedy=greedy, max_steps=max_steps, frozen_policy=fz, fused_crowd_mix=True, steps_per_launch=spl,
-                          details=True)
-    finally:
-        ev._settle_finished = settle
-    state = [t.clone() for t in env.get_state()]
-    _close(env, pol, fz)
-    return res, state, seen
-
-
-def _same_round(name, spl, greedy=True, max_steps=MAX_STEPS):
     N, W = CASES[name][0], CASES[name][1]
-    ref, ref_state, log, ref_obs, _ = _reference(name, greedy, max_steps)
-    got, got_state, seen = _fused(name, spl, greedy, max_steps)
-    _assert_same(ref, ref_state, got, got_state, (name, spl, greedy), log)
-    ws = log.world_steps().to(seen["world_steps"].device)
-    assert torch.equal(seen["world_steps"], ws), (name, spl, "world_steps")
-    assert seen["env_steps"] == ref["env_steps"]
-    last = (ws == ref["env_steps"]).nonzero().flatten()
-    assert last.numel() >= 1
-    assert torch.equal(seen["obs"].view(W, N, -1)[last], ref_obs.view(W, N, -1)[last]), (name, spl, "obs of the worlds that ended last")
+    per_step, rows_of = [], env.policy_rows
+    wpw = 64 // N
+    tiles = (W + wpw - 1) // wpw
+
+    def spy(policy_id, only_running=True):
+        out = rows_of(policy_id, only_running)
+        if policy_id == _lib.POLICY_FROZEN_NET:
+            fl = env.get_state()[2].view(-1).long()                                  # the state BEFORE this step
+            live = ((fl & _lib.F_PRESENT) != 0) & ((fl & _lib.F_LEARNING) != 0) & ((fl & _lib.F_DONE_MASK) == 0)
+            frozen = torch.zeros_like(live)
+            frozen[out[0][:int(out[1].item())].long()] = True
+            pol4 = ((fl >> _lib.F_POLICY_SHIFT) & _lib.F_POLICY_MASK) == _lib.POLICY_FROZEN_NET
+            assert bool((frozen == (pol4 & ((fl & _lib.F_PRESENT) != 0) & ((fl & _lib.F_DONE_MASK) == 0))).all())   # (the kernel's predicate)
+            pad = tiles * wpw * N - W * N
+            tile = lambda m: torch.cat([m, m.new_zeros(pad)]).view(tiles, wpw * N).any(1)
+            per_step.append((int(frozen.sum()), int((tile(frozen) & ~tile(live)).sum())))
+        return out
+    return spy, per_step
+
+
+def _one_network_switch_refuses(ev, env, pol, fz):
+    assert "frozen_policy" in ev.evaluate_fused_crowd_unavailable_reason(env, pol, fz)   # (the one-network switch goes on refusing)
+
+
+# the step-by-step round of every case is computed once (family "crowd_eval_mix" of the one cache)
+ROUNDS = tw.CrowdRounds("crowd_eval_mix", CASES, lambda name: _make(name), switch="fused_crowd_mix",
+                        reason="evaluate_fused_crowd_mix_unavailable_reason", run="eval_run_crowd_mix", rows_spy=_frozen_pass_alone,
+                        also=_one_network_switch_refuses)
+_reference, _same_round = ROUNDS.reference, ROUNDS.same_round
 
 
 def test_the_step_by_step_rounds_show_the_frozen_pass_and_the_frozen_pass_alone():
@@ -159,28 +118,11 @@ def test_sampled_evaluation():
 
 def test_round_cut_at_max_steps():
     """max_steps = 10 with launches of 7: the last launch is cut to 3, and the round equals the step-by-step round cut at 10"""
-    from rl_collision_avoidance_amd.ga3c import evaluate as ev
-    launches = []
-    run = ev.eval_run_crowd_mix
-
-    def spy(env, policy, frozen_policy, rec, n_steps, greedy=True):
-        launches.append(n_steps)
-        run(env, policy, frozen_policy, rec, n_steps, greedy)
-    ev.eval_run_crowd_mix = spy
-    try:
-        _same_round("n20", 7, max_steps=10)
-    finally:
-        ev.eval_run_crowd_mix = run
-    assert launches == [7, 3]
-    assert _reference("n20", max_steps=10)[0]["env_steps"] == 10
+    ROUNDS.cut_at_max_steps("n20")
 
 
 def _raw(env, pol, fz, rec, n, greedy=1):
-    from rl_collision_avoidance_amd import _lib
-    p = lambda t: C.c_void_p(t.data_ptr())
-    return _lib.lib().cavoid_crowd_eval_run_mix(env._h, pol._h if pol is not None else None, fz._h if fz is not None else None, C.byref(rec.c),
-                                                p(env.obs), p(env.rewards), p(env.done), p(env.game_over), p(rec.actions), p(rec.values), n, greedy,
-                                                env._stream())
+    return tw.raw("cavoid_crowd_eval_run_mix", env, pol, rec, n, fz, greedy)
 
 
 def test_launch_edges_at_the_raw_entry_point():
@@ -255,3 +197,4 @@ def test_the_entry_point_refuses_what_it_does_not_carry():
     refused(EUNSUPPORTED, "holonomic", env, _policy(env.config, "free"), _policy(env.config, "free", seed=4321))
     env = _crowd_env(8, 20, 19, seed=1, evaluate_mode=1, **MIX)                   # no frozen_policy
     refused(EINVAL, "no frozen_policy", env, _policy(env.config, "free"), None)
+    tw.report_cache("crowd_eval_mix")  # (a whole run of this file: 5 cases, the sampled round, the round cut at 10 steps: 7)

@@ -13,7 +13,7 @@ torch = pytest.importorskip("torch")
 
 from oracle import rollout_oracle as ro
 from tests import rollout_scripts as rs
-from tests.test_gpu_parity import _env
+from tests.gpu_support import _env
 
 pytestmark = pytest.mark.gpu
 

@@ -18,8 +18,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from oracle import c_oracle as co
-from oracle import cavoid_oracle as po
-from tests.test_gpu_parity import OBS_TOL, _compare_step, _env, _goal_seeking_actions, _pull, _push
+from tests.gpu_support import OBS_TOL, _compare_step, _env, _goal_seeking_actions, _infeasible_first_programmes, _pull, _push
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +31,7 @@ MIX = dict(rvo_enabled=2, gen_rvo_fraction=0.6, gen_nonlearning_fraction=0.6, ge
 _BITWISE_CHILD = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, sys.argv[2])
-from tests.test_gpu_parity import _env, _push
+from tests.gpu_support import _env, _push
 from oracle import c_oracle as co
 from tests import orca_regimes as R
 # box scenarios generated inside the step, the training mix; ring scenarios (head-on traffic through a crowded centre): the programmes
@@ -125,26 +124,6 @@ def test_wave_cooperative_orca_equals_the_tile_forms_bitwise_at_small_n(tmp_path
 
 
 # ---- against the float64 oracle at crowd sizes ---------------------------------------------------------------------------------------
-def _infeasible_first_programmes(st, N, worlds=6):
-    """how many running ORCA agents of worlds 0..worlds-1 have a first programme without a solution (oracle/cavoid_oracle.py's own
-    orca_lines / _lp_plane on the pre-move state): those agents take the least-penetration programme"""
-    cfg = po.OracleConfig(max_agents=N, max_other_agents_observed=N - 1)
-    count = 0
-    for w in range(worlds):
-        k = slice(w * N, (w + 1) * N)
-        world = po.world_from_arrays(st.f64[:, k], st.f32[:, k], st.flags[k], cfg)
-        for hi, host in enumerate(world.agents):
-            if host.policy != po.POLICY_RVO or host.is_done:
-                continue
-            gx, gy = host.goal[0] - host.pos[0], host.goal[1] - host.pos[1]
-            gn = math.sqrt(gx * gx + gy * gy)
-            scale = host.pref_speed / gn if gn > 0.0 else 0.0
-            lines = po.orca_lines(hi, world.agents, cfg)
-            fail, _, _ = po._lp_plane(lines, host.pref_speed, scale * gx, scale * gy, False)
-            count += fail < len(lines)
-    return count
-
-
 # The seed of a case is the first from 23 up with which every world stays within the bar for all 120 steps.  Each seed passed over was
 # tried on an MI355X: one world left the oracle at a running ORCA agent, and tests/replay.py::classify_divergence (run by
 # tools/crowd_rvo_seeds.py, with env.step / the oracle's step in place of the auto-reset step) calls it a TIE of that agent's linear

@@ -12,23 +12,17 @@ The networks are `NetworkVP_rnn(arch="weight_sharing")` with their random initia
 one policy logit ("straight": full speed ahead, "turn": turning on the spot, "free": none); up to 19 observed neighbours they run on the
 whole-row handle, above on the ring handle (`ws_crowd=True`).  The step-by-step result of every case is computed once and shared."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.test_gpu_crowd_eval import MAX_STEPS, _StepLog, _assert_same, _outcomes
-from tests.test_gpu_parity import _env as _crowd_env
+from tests import eval_twins as tw
+from tests.eval_twins import BIAS, MAX_STEPS, NETS, _not_over, _outcomes
+from tests.gpu_support import EINVAL, EUNSUPPORTED, OK, _env as _crowd_env
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED = 0, -1, -4
-BIAS = 1.0                       # on the favoured logit, as tests/test_gpu_eval_ws_fused.py
-NETS = {"straight": 2, "turn": 8, "free": None}
 ORCA = dict(rvo_enabled=2, gen_rvo_fraction=0.5, gen_nonlearning_fraction=0.5)
 
 # name: (N, W, M, env settings, network, max_time_ratio, steps per launch, frozen policy).  The shapes are the smallest at which the lane
@@ -70,16 +64,8 @@ SAMPLED = ("n22_box", 7)             # the sampled case: greedy=False on this sh
 
 
 def _policy(cfg, net, seed=1234, policy_seed=77, arch="weight_sharing"):
-    from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
-    from rl_collision_avoidance_amd.ga3c.policy_kernel import MAX_OTHERS_WS, FusedPolicy
-    model = NetworkVP_rnn(cfg, seed=seed, arch=arch).to("cuda:0")
-    if NETS[net] is not None:
-        with torch.no_grad():
-            model.p_bias[NETS[net]] += BIAS
-    if arch != "weight_sharing":
-        return FusedPolicy(model, seed=policy_seed)
     # the whole-row handle up to 19 observed neighbours, the ring handle above
-    return FusedPolicy(model, seed=policy_seed, ws_crowd=model.max_others > MAX_OTHERS_WS)
+    return tw.policy(cfg, net, seed, policy_seed, arch, ws_crowd=None)
 
 
 def _make(name, **more):
@@ -91,75 +77,26 @@ def _make(name, **more):
     return env, pol, fz
 
 
-def _close(env, pol, fz):
-    pol.close()
-    if fz is not None:
-        fz.close()
-    env.close()
+_close = tw.close
 
 
-_REFS = {}
-
-
-def _reference(name, greedy=True, max_steps=MAX_STEPS):
-    """evaluate(details=True) of one case, step by step: result, final world buffer, the step log, env.obs at the end, and per step the
-    number of running frozen-network rows the loop listed -- computed once"""
+def _frozen_rows(env, name):
+    """per step of the step-by-step round, the number of running frozen-network rows the loop listed"""
     from rl_collision_avoidance_amd import _lib
-    from rl_collision_avoidance_amd.ga3c.evaluate import evaluate
-    key = (name, greedy, max_steps)
-    if key not in _REFS:
-        env, pol, fz = _make(name)
-        log = _StepLog(env)
-        frozen_rows = []
-        rows_of = env.policy_rows
+    frozen_rows, rows_of = [], env.policy_rows
 
-        def spy(policy_id, only_running=True):
-            out = rows_of(policy_id, only_running)
-            if policy_id == _lib.POLICY_FROZEN_NET:
-                frozen_rows.append(int(out[1].item()))
-            return out
-        env.policy_rows = spy
-        res = evaluate(env, pol, rounds=1, greedy=greedy, max_steps=max_steps, frozen_policy=fz, details=True)
-        _REFS[key] = (res, [t.clone() for t in env.get_state()], log, env.obs.clone(), frozen_rows)
-        _close(env, pol, fz)
-    return _REFS[key]
+    def spy(policy_id, only_running=True):
+        out = rows_of(policy_id, only_running)
+        if policy_id == _lib.POLICY_FROZEN_NET:
+            frozen_rows.append(int(out[1].item()))
+        return out
+    return spy, frozen_rows
 
 
-def _fused(name, spl, greedy=True, max_steps=MAX_STEPS):
-    """the same round on the kernel; with it the observation buffer as the LAST LAUNCH left it (before evaluate() settles the env)"""
-    from rl_collision_avoidance_amd.ga3c import evaluate as ev
-    env, pol, fz = _make(name)
-    assert ev.evaluate_fused_crowd_ws_unavailable_reason(env, pol, fz) is None     # (no case passes by falling back: the call would raise, too)
-    seen = {}
-    settle = ev._settle_finished
-
-    def spy(env_, world_steps, env_steps):
-        seen["obs"], seen["world_steps"], seen["env_steps"] = env_.obs.clone(), world_steps.clone(), env_steps
-        return settle(env_, world_steps, env_steps)
-    ev._settle_finished = spy
-    try:
-        res = ev.evaluate(env, pol, rounds=1, greedy=greedy, max_steps=max_steps, frozen_policy=fz, fused_crowd_ws=True, steps_per_launch=spl,
-                          details=True)
-    finally:
-        ev._settle_finished = settle
-    state = [t.clone() for t in env.get_state()]
-    _close(env, pol, fz)
-    return res, state, seen
-
-
-def _same_round(name, spl, greedy=True, max_steps=MAX_STEPS):
-    N, W = CASES[name][0], CASES[name][1]
-    ref, ref_state, log, ref_obs, _ = _reference(name, greedy, max_steps)
-    got, got_state, seen = _fused(name, spl, greedy, max_steps)
-    _assert_same(ref, ref_state, got, got_state, (name, spl, greedy), log)
-    # the records: the step at which each world was over
-    ws = log.world_steps().to(seen["world_steps"].device)
-    assert torch.equal(seen["world_steps"], ws), (name, spl, "world_steps")
-    assert seen["env_steps"] == ref["env_steps"]
-    # the observation of the worlds that ended at the round's last step (or were cut there): the loop stepped them last at that step too
-    last = (ws == ref["env_steps"]).nonzero().flatten()
-    assert last.numel() >= 1
-    assert torch.equal(seen["obs"].view(W, N, -1)[last], ref_obs.view(W, N, -1)[last]), (name, spl, "obs of the worlds that ended last")
+# the step-by-step round of every case is computed once (family "crowd_ws_eval" of the one cache)
+ROUNDS = tw.CrowdRounds("crowd_ws_eval", CASES, lambda name: _make(name), switch="fused_crowd_ws",
+                        reason="evaluate_fused_crowd_ws_unavailable_reason", run="eval_run_crowd_ws", rows_spy=_frozen_rows)
+_reference, _same_round = ROUNDS.reference, ROUNDS.same_round
 
 
 def test_the_step_by_step_rounds_are_not_empty():
@@ -209,36 +146,11 @@ def test_sampled_evaluation():
 def test_round_cut_at_max_steps():
     """max_steps = 10 with launches of 7: the last launch is cut to 3 (the cut lies inside a launch of the uncut round), and the round
     equals the step-by-step round cut at 10"""
-    from rl_collision_avoidance_amd.ga3c import evaluate as ev
-    name = "n17_ws8"
-    launches = []
-    run = ev.eval_run_crowd_ws
-
-    def spy(env, policy, frozen_policy, rec, n_steps, greedy=True):
-        launches.append(n_steps)
-        run(env, policy, frozen_policy, rec, n_steps, greedy)
-    ev.eval_run_crowd_ws = spy
-    try:
-        _same_round(name, 7, max_steps=10)
-    finally:
-        ev.eval_run_crowd_ws = run
-    assert launches == [7, 3]
-    assert _reference(name, max_steps=10)[0]["env_steps"] == 10
+    ROUNDS.cut_at_max_steps("n17_ws8")
 
 
 def _raw(env, pol, rec, n, frozen=None, greedy=1, buffers=None):
-    from rl_collision_avoidance_amd import _lib
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    return _lib.lib().cavoid_crowd_eval_run_ws(env._h, pol._h if pol is not None else None, frozen._h if frozen is not None else None,
-                                               C.byref(buffers if buffers is not None else rec.c), p(env.obs), p(env.rewards), p(env.done),
-                                               p(env.game_over), p(rec.actions), p(rec.values), n, greedy, env._stream())
-
-
-def _not_over(env):
-    """worlds not over, from the world buffer: cavoid_step's game_over predicate in EVALUATE_MODE"""
-    from rl_collision_avoidance_amd import _lib
-    fl = env.get_state()[2].view(env.num_worlds, env.max_agents)
-    return (((fl & _lib.F_PRESENT) != 0) & ((fl & _lib.F_DONE_MASK) == 0)).any(1)
+    return tw.raw("cavoid_crowd_eval_run_ws", env, pol, rec, n, frozen, greedy, buffers)
 
 
 def test_launch_edges_at_the_raw_entry_point():
@@ -404,17 +316,6 @@ def test_the_other_switches_keep_their_reasons_on_these_envs_and_policies():
         _close(env, pol, None)
 
 
-def _cli(ckpt, extra):
-    cmd = [sys.executable, "-m", "rl_collision_avoidance_amd.ga3c.train", "--arch", "weight_sharing", "--agents", "20", "--observed", "19",
-           "--worlds", "24", "--load", ckpt, "--evaluate", "1"] + extra
-    env = dict(os.environ)
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    run = subprocess.run(cmd, cwd=ROOT, env=env, timeout=300, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(run.stdout[-3000:])
-    assert run.returncode == 0
-    return run.stdout
-
-
 def test_train_cli_runs_the_kernel_and_prints_the_same_result(tmp_path):
     """a fresh child process each, on a checkpoint this test writes (a weight_sharing network of 19 observed neighbours, "straight")"""
     from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
@@ -425,13 +326,12 @@ def test_train_cli_runs_the_kernel_and_prints_the_same_result(tmp_path):
         net.p_bias[NETS["straight"]] += BIAS
     ckpt = str(tmp_path / "network_00000000.pt")
     torch.save({"episode": 0, "model": net.state_dict(), "training_step": 0, "arch": net.arch, "max_others": net.max_others}, ckpt)
-    fused, plain = _cli(ckpt, ["--fused-crowd-ws-evaluate"]), _cli(ckpt, [])
+    args = ["--arch", "weight_sharing", "--agents", "20", "--observed", "19", "--worlds", "24", "--load", ckpt]
+    fused, plain = tw.cli(args + ["--fused-crowd-ws-evaluate"]), tw.cli(args)
     assert "[Evaluate] fused crowd weight_sharing evaluation kernel (cavoid_crowd_eval_run_ws), 4 env steps per launch" in fused
     assert "cavoid_crowd_eval_run_ws" not in plain
-    last = lambda out: [l for l in out.splitlines() if l.startswith("[Evaluate] agents ")]
+    last, strip = tw.last_evaluate_line, tw.without_mean_reward
     assert len(last(fused)) == 1 and len(last(plain)) == 1
-    # mean_reward is the one figure the two definitions of the return may tell apart (include/cavoid.h): left out of the comparison
-    strip = lambda line: " ".join(w for w in line.replace("mean_reward ", "mean_reward=").split("  ") if not w.startswith("mean_reward="))
     assert strip(last(fused)[0]) == strip(last(plain)[0])
     assert "success_rate" in strip(last(fused)[0]) and "mean_reward" not in strip(last(fused)[0])
 
@@ -443,3 +343,4 @@ def test_train_cli_with_the_flag_ends_where_the_kernel_does_not_apply():
         train.main(["--agents", "4", "--worlds", "64", "--arch", "weight_sharing", "--evaluate", "1", "--fused-crowd-ws-evaluate"])
     with pytest.raises(SystemExit, match="--fused-crowd-ws-evaluate.*cavoid_crowd_eval_run embeds"):
         train.main(["--agents", "20", "--worlds", "64", "--evaluate", "1", "--fused-crowd-ws-evaluate"])
+    tw.report_cache("crowd_ws_eval")  # (a whole run of this file: 12 cases, the sampled round, the round cut at 10 steps: 14)

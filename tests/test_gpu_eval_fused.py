@@ -7,7 +7,6 @@ BIT for bit: the result dict, every per-agent tensor, the world buffer the round
 The networks are `NetworkVP_rnn` with their random initial weights and a bias on one policy logit, so that the argmax depends on the
 observation but favours one behaviour: action 2 (full speed, straight ahead: goals and collisions), action 8 (turning on the spot:
 timeouts), or none.  The step-by-step result of every (shape, network) is computed once and shared by the cases that need it."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -16,145 +15,51 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import eval_twins as tw
+from tests.eval_twins import MAX_STEPS, MIX, NETS, SPLS, _assert_same, _not_over, _outcomes, _StepLog
+from tests.gpu_support import EINVAL, EUNSUPPORTED, OK, ROOT, _env as _crowd_env
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED = 0, -1, -4
-MAX_STEPS = 400
-BIAS = 1.0                       # on the favoured logit (the initial weights' logits spread over a few tenths)
-NETS = {"straight": 2, "turn": 8, "free": None}
-SPLS = (1, 7, 16)                # 7 divides no episode length in particular: launches begin on part-finished tiles
+FAMILY = "eval_fused"            # this file's rounds in the one cache of step-by-step references
 
 
-def _cfg_class(N):
-    from rl_collision_avoidance_amd.config import EnvConfig
-
-    class Cfg(EnvConfig):
-        def __init__(self):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
-            EnvConfig.__init__(self)
-    return Cfg()
-
-
-def _policy(cfg, bias_action, seed=1234, policy_seed=77):
-    from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
-    from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
-    net = NetworkVP_rnn(cfg, seed=seed).to("cuda:0")
-    if bias_action is not None:
-        with torch.no_grad():
-            net.p_bias[bias_action] += BIAS
-    return FusedPolicy(net, seed=policy_seed)
+def _policy(cfg, net, seed=1234, policy_seed=77):
+    return tw.policy(cfg, net, seed, policy_seed)
 
 
 def _env(W, N, seed, **over):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
     over.setdefault("evaluate_mode", 1)
     over.setdefault("max_time_ratio", 1.75)
-    return BatchedCollisionAvoidanceEnv(W, _cfg_class(N), device="cuda:0", seed=seed, **over)
+    return _crowd_env(W, N, seed=seed, **over)
 
 
-class _StepLog(object):
-    """wraps env.step of the step-by-step twin: every step's rewards and game_over flags, as the loop saw them"""
-
-    def __init__(self, env):
-        self.rew, self.over, self._step = [], [], env.step
-        env.step = self
-
-    def __call__(self, actions):
-        out = self._step(actions)
-        self.rew.append(out[1].clone().view(-1)); self.over.append(out[3].clone())
-        return out
-
-    def masked_return(self, N):
-        """(the return as include/cavoid.h defines it, restated on the host: the float64 sum, in step order, of the rewards of the steps
-        before which the agent's world was not over; which agents the loop paid something AFTER their world was over)"""
-        want = torch.zeros_like(self.rew[0], dtype=torch.float64)
-        paid_after = torch.zeros_like(self.rew[0], dtype=torch.bool)
-        running = torch.ones_like(self.over[0], dtype=torch.bool)
-        for rew, over_t in zip(self.rew, self.over):
-            live = running.repeat_interleave(N)
-            want += torch.where(live, rew.double(), torch.zeros_like(want))
-            paid_after |= ~live & (rew != 0)
-            running &= over_t == 0
-        return want, paid_after
-
-    def world_steps(self):
-        """the step at which each world was over (the step count of the round where it never was)"""
-        over = torch.stack(self.over).bool()                                   # [T, W]
-        first = torch.where(over.any(0), over.int().argmax(0) + 1, torch.full_like(over[0], len(self.over), dtype=torch.int64))
-        return first.to(torch.int32)
-
-
-_REFS = {}
+def _make(W, N, net, frozen, over):
+    env = _env(W, N, 21, **over)
+    return env, _policy(env.config, net), _policy(env.config, "free", seed=4321, policy_seed=0) if frozen else None
 
 
 def _reference(W, N, net, greedy=True, frozen=False, **over):
     """evaluate(fused=False, details=True) of one (shape, network): result, final world buffer, the step log -- computed once"""
     from rl_collision_avoidance_amd.ga3c.evaluate import evaluate
-    key = (W, N, net, greedy, frozen, tuple(sorted(over.items())))
-    if key not in _REFS:
-        env = _env(W, N, 21, **over)
-        pol = _policy(env.config, NETS[net])
-        fz = _policy(env.config, None, seed=4321, policy_seed=0) if frozen else None
+
+    def compute():
+        env, pol, fz = _make(W, N, net, frozen, over)
         log = _StepLog(env)
         res = evaluate(env, pol, rounds=1, greedy=greedy, max_steps=MAX_STEPS, frozen_policy=fz, details=True)
-        _REFS[key] = (res, [t.clone() for t in env.get_state()], log)
-        pol.close()
-        if fz is not None:
-            fz.close()
-        env.close()
-    return _REFS[key]
+        out = (res, [t.clone() for t in env.get_state()], log)
+        tw.close(env, pol, fz)
+        return out
+    return tw.cached(FAMILY, (W, N, net, greedy, frozen, tuple(sorted(over.items()))), compute)
 
 
 def _fused(W, N, net, spl, greedy=True, frozen=False, **over):
     from rl_collision_avoidance_amd.ga3c.evaluate import evaluate
-    env = _env(W, N, 21, **over)
-    pol = _policy(env.config, NETS[net])
-    fz = _policy(env.config, None, seed=4321, policy_seed=0) if frozen else None
+    env, pol, fz = _make(W, N, net, frozen, over)
     res = evaluate(env, pol, rounds=1, greedy=greedy, max_steps=MAX_STEPS, frozen_policy=fz, fused=True, steps_per_launch=spl, details=True)
     state = [t.clone() for t in env.get_state()]
-    pol.close()
-    if fz is not None:
-        fz.close()
-    env.close()
+    tw.close(env, pol, fz)
     return res, state
-
-
-def _assert_same(ref, ref_state, got, got_state, what, log=None, skip=()):
-    """Everything bit for bit.  The return (``per_agent["ret"]``, ``mean_reward``) is held to the step-by-step run twice: bitwise to the
-    loop's own sum for every agent the loop paid nothing after its world was over -- and, with ``log``, bitwise to the definition of
-    include/cavoid.h (the rewards up to and including the step at which the world is over) for EVERY agent.  The two differ where
-    cavoid_step goes on paying a finished world: at the default rewards that is the getting-close penalty of an agent that ran out of
-    time within 0.2 m of another (measured: 10 x 48 box scenarios, unbiased network: loop mean_reward -0.19782, kernel -0.13149; the
-    4 x 64 scripted mixes likewise), with reward_time_step every agent (test_return_stops_where_the_world_is_over)."""
-    masked, paid_after = (None, None)
-    if log is not None:
-        masked, paid_after = log.masked_return(ref_state[2].numel() // log.over[0].numel())
-        if bool(paid_after.any()):
-            print("%s: the loop paid %d agent(s) after their world was over; mean_reward loop %.17g kernel %.17g"
-                  % (what, int(paid_after.sum()), ref["mean_reward"], got["mean_reward"]))
-            skip = tuple(skip) + ("mean_reward", "ret")
-    for k in ref:
-        if k == "per_agent" or k in skip:
-            continue
-        assert type(ref[k]) is type(got[k]) and ref[k] == got[k], (what, k, ref[k], got[k])
-    assert list(ref) == list(got)
-    for k, t in ref["per_agent"].items():
-        if k in skip:
-            continue
-        assert t.dtype == got["per_agent"][k].dtype and torch.equal(t, got["per_agent"][k]), (what, "per_agent", k)
-    if masked is not None:
-        learning = ref["per_agent"]["learning"]
-        assert torch.equal(got["per_agent"]["ret"], masked), (what, "ret against its definition")
-        assert got["mean_reward"] == float(masked[learning].sum()) / max(int(learning.sum()), 1), (what, "mean_reward")
-        assert torch.equal(got["per_agent"]["ret"][~paid_after], ref["per_agent"]["ret"][~paid_after]), (what, "ret against the loop's")
-    for name, a, b in zip(("f64", "f32", "flags"), ref_state, got_state):
-        assert torch.equal(a, b), (what, "final state", name)
-
-
-def _outcomes(res):
-    per = res["per_agent"]
-    return set(per["outcome"][per["learning"]].tolist())
 
 
 def _check_not_empty(W, N, over, frozen=False):
@@ -242,9 +147,6 @@ def test_fused_round_equals_step_by_step_on_one_wavefront(tmp_path):
     assert run.returncode == 0 and run.stdout.strip().endswith("SAME")
 
 
-MIX = dict(gen_min_agents=2, gen_nonlearning_fraction=0.5, rvo_enabled=1, gen_rvo_fraction=0.34, gen_static_fraction=0.33)
-
-
 @pytest.mark.parametrize("frozen", [False, True])
 def test_scripted_and_frozen_agents(frozen):
     """4 x 64 among static / non-cooperative / ORCA agents (the ORCA instantiation); with frozen-network agents and their network
@@ -267,16 +169,14 @@ def test_frozen_agents_without_their_network_are_refused():
     from rl_collision_avoidance_amd.ga3c.evaluate import _EvalRecords, evaluate, evaluate_fused_unavailable_reason
     from rl_collision_avoidance_amd import _lib
     env = _env(64, 4, 21, **dict(MIX, gen_frozen_fraction=0.3))
-    pol = _policy(env.config, None)
+    pol = _policy(env.config, "free")
     why = evaluate_fused_unavailable_reason(env, pol, None)
     assert why is not None and "frozen" in why
     with pytest.raises(ValueError, match="frozen"):
         evaluate(env, pol, fused=True)
     env.reset()
     rec = _EvalRecords(env)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    rc = _lib.lib().cavoid_eval_run(env._h, pol._h, None, C.byref(rec.c), p(env.obs), p(env.rewards), p(env.done), p(env.game_over),
-                                    p(rec.actions), p(rec.values), 4, 1, env._stream())
+    rc = _raw(env, pol, rec, 4)
     assert rc == EUNSUPPORTED
     pol.close(); env.close()
 
@@ -309,19 +209,7 @@ def test_return_stops_where_the_world_is_over():
 
 
 def _raw(env, pol, rec, n, frozen=None, buffers=None, obs=None):
-    from rl_collision_avoidance_amd import _lib
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    return _lib.lib().cavoid_eval_run(env._h, pol._h if pol is not None else None, frozen._h if frozen is not None else None,
-                                      C.byref(buffers if buffers is not None else rec.c), p(env.obs if obs is None else obs), p(env.rewards),
-                                      p(env.done), p(env.game_over), p(rec.actions), p(rec.values), n, 1, env._stream())
-
-
-def _not_over(env):
-    """worlds not over, from the world buffer: cavoid_step's game_over predicate in EVALUATE_MODE"""
-    from rl_collision_avoidance_amd import _lib
-    fl = env.get_state()[2].view(env.num_worlds, env.max_agents)
-    running = ((fl & _lib.F_PRESENT) != 0) & ((fl & _lib.F_DONE_MASK) == 0)
-    return running.any(1)
+    return tw.raw("cavoid_eval_run", env, pol, rec, n, frozen, buffers=buffers, obs=obs)
 
 
 def test_launch_edges_at_the_raw_entry_point():
@@ -329,7 +217,7 @@ def test_launch_edges_at_the_raw_entry_point():
     from rl_collision_avoidance_amd.ga3c.evaluate import _EvalRecords
     W, N = 64, 4
     env = _env(W, N, 21)
-    pol = _policy(env.config, NETS["straight"])
+    pol = _policy(env.config, "straight")
     env.reset()
     rec = _EvalRecords(env)
     snap = lambda: [t.clone() for t in (*env.get_state(), env.obs, rec.ret, rec.goal_step, rec.world_steps, rec.worlds_running, rec.actions)]
@@ -348,7 +236,7 @@ def test_launch_edges_at_the_raw_entry_point():
         assert _raw(env, pol, rec, 4, buffers=bad) == EINVAL, field
     assert _raw(env, None, rec, 4) == EINVAL
     other = _env(16, 5, 3)                                   # handles that do not describe the same batch: a policy of another width
-    wide = _policy(other.config, None)
+    wide = _policy(other.config, "free")
     assert _raw(env, wide, rec, 4) == EINVAL
     assert _raw(env, pol, rec, -1) == EINVAL
     assert all(torch.equal(a, b) for a, b in zip(before, snap()))
@@ -383,19 +271,10 @@ def test_launch_edges_at_the_raw_entry_point():
     pol.close(); env.close()
 
 
-def _cli(extra):
-    cmd = [sys.executable, "-m", "rl_collision_avoidance_amd.ga3c.train", "--worlds", "64", "--evaluate", "1"] + extra
-    env = dict(os.environ)
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    run = subprocess.run(cmd, cwd=ROOT, env=env, timeout=300, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(run.stdout[-3000:])
-    assert run.returncode == 0
-    return run.stdout
-
-
 def test_train_cli_runs_the_kernel_and_prints_the_same_result():
-    fused, plain = _cli(["--fused-evaluate"]), _cli([])
+    fused, plain = tw.cli(["--worlds", "64", "--fused-evaluate"]), tw.cli(["--worlds", "64"])
     assert "[Evaluate] fused evaluation kernel (cavoid_eval_run), 4 env steps per launch" in fused
     assert "cavoid_eval_run" not in plain
-    last = lambda out: [l for l in out.splitlines() if l.startswith("[Evaluate] agents ")]
+    last = tw.last_evaluate_line
     assert len(last(fused)) == 1 and last(fused) == last(plain)
+    tw.report_cache(FAMILY)      # (a whole run of this file: 6 shapes x 3 networks, the two mixes x 3, two sampled rounds, the time-step reward: 27)

@@ -7,7 +7,6 @@ world buffer the round leaves behind, and the return against its definition (inc
 
 The networks are `NetworkVP_rnn(arch="weight_sharing")` with their random initial weights and a bias on one policy logit (the helpers and
 the three behaviours of tests/test_gpu_eval_fused.py).  The step-by-step result of every (shape, network) is computed once and shared."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -17,11 +16,13 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.test_gpu_eval_fused import EINVAL, EUNSUPPORTED, MAX_STEPS, MIX, NETS, OK, ROOT, SPLS, _assert_same, _not_over, _outcomes, _StepLog
+from tests import eval_twins as tw
+from tests.eval_twins import MAX_STEPS, MIX, NETS, SPLS, _assert_same, _not_over, _outcomes, _StepLog
+from tests.gpu_support import EINVAL, EUNSUPPORTED, OK, ROOT, _env as _crowd_env
 
 pytestmark = pytest.mark.gpu
 
-BIAS = 1.0                       # on the favoured logit, as the rnn tests (raise it here if the early-exit assertions below ask for it)
+FAMILY = "eval_ws_fused"         # this file's rounds in the one cache of step-by-step references
 
 
 def _cfg(N, M):
@@ -35,51 +36,38 @@ def _cfg(N, M):
     return Cfg()
 
 
-def _policy(cfg, bias_action, seed=1234, policy_seed=77, arch="weight_sharing", ws_crowd=False):
-    from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
-    from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
-    net = NetworkVP_rnn(cfg, seed=seed, arch=arch).to("cuda:0")
-    if bias_action is not None:
-        with torch.no_grad():
-            net.p_bias[bias_action] += BIAS
-    return FusedPolicy(net, seed=policy_seed, ws_crowd=ws_crowd)
+def _policy(cfg, net, seed=1234, policy_seed=77, arch="weight_sharing", ws_crowd=False):
+    return tw.policy(cfg, net, seed, policy_seed, arch, ws_crowd)
 
 
 def _env(W, N, M, seed, **over):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
     over.setdefault("evaluate_mode", 1)
     over.setdefault("max_time_ratio", 1.75)
-    return BatchedCollisionAvoidanceEnv(W, _cfg(N, M), device="cuda:0", seed=seed, **over)
-
-
-_REFS = {}
+    return _crowd_env(W, N, M, seed=seed, **over)
 
 
 def _make(W, N, M, net, frozen, over):
     env = _env(W, N, M, 21, **over)
-    pol = _policy(env.config, NETS[net])
-    fz = _policy(env.config, None, seed=4321, policy_seed=0) if frozen else None
+    pol = _policy(env.config, net)
+    fz = _policy(env.config, "free", seed=4321, policy_seed=0) if frozen else None
     return env, pol, fz
 
 
-def _close(env, pol, fz):
-    pol.close()
-    if fz is not None:
-        fz.close()
-    env.close()
+_close = tw.close
 
 
 def _reference(W, N, M, net, greedy=True, frozen=False, **over):
     """evaluate(fused=False, details=True) of one (shape, network): result, final world buffer, the step log -- computed once"""
     from rl_collision_avoidance_amd.ga3c.evaluate import evaluate
-    key = (W, N, M, net, greedy, frozen, tuple(sorted(over.items())))
-    if key not in _REFS:
+
+    def compute():
         env, pol, fz = _make(W, N, M, net, frozen, over)
         log = _StepLog(env)
         res = evaluate(env, pol, rounds=1, greedy=greedy, max_steps=MAX_STEPS, frozen_policy=fz, details=True)
-        _REFS[key] = (res, [t.clone() for t in env.get_state()], log)
+        out = (res, [t.clone() for t in env.get_state()], log)
         _close(env, pol, fz)
-    return _REFS[key]
+        return out
+    return tw.cached(FAMILY, (W, N, M, net, greedy, frozen, tuple(sorted(over.items()))), compute)
 
 
 def _fused(W, N, M, net, spl, greedy=True, frozen=False, **over):
@@ -219,11 +207,7 @@ def test_many_tiles_two_workgroups_per_cu():
 
 
 def _raw(env, pol, rec, n, frozen=None, buffers=None, fn="cavoid_eval_run_ws"):
-    from rl_collision_avoidance_amd import _lib
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    return getattr(_lib.lib(), fn)(env._h, pol._h if pol is not None else None, frozen._h if frozen is not None else None,
-                                   C.byref(buffers if buffers is not None else rec.c), p(env.obs), p(env.rewards), p(env.done), p(env.game_over),
-                                   p(rec.actions), p(rec.values), n, 1, env._stream())
+    return tw.raw(fn, env, pol, rec, n, frozen, buffers=buffers)
 
 
 def test_launch_edges_at_the_raw_entry_point():
@@ -231,7 +215,7 @@ def test_launch_edges_at_the_raw_entry_point():
     from rl_collision_avoidance_amd.ga3c.evaluate import _EvalRecords
     W, N, M = 64, 4, 7
     env = _env(W, N, M, 21)
-    pol = _policy(env.config, NETS["straight"])
+    pol = _policy(env.config, "straight")
     env.reset()
     rec = _EvalRecords(env)
     snap = lambda: [t.clone() for t in (*env.get_state(), env.obs, rec.ret, rec.goal_step, rec.world_steps, rec.worlds_running, rec.actions)]
@@ -249,12 +233,12 @@ def test_launch_edges_at_the_raw_entry_point():
         setattr(bad, field, None)
         assert _raw(env, pol, rec, 4, buffers=bad) == EINVAL, field
     assert _raw(env, None, rec, 4) == EINVAL
-    narrow = _policy(_cfg(N, 3), None)                       # handles that do not describe the same batch: a policy of another width
+    narrow = _policy(_cfg(N, 3), "free")                       # handles that do not describe the same batch: a policy of another width
     assert _raw(env, narrow, rec, 4) == EINVAL
     assert _raw(env, pol, rec, -1) == EINVAL
     # what the kernel does not carry
-    rnn = _policy(env.config, None, arch="rnn")
-    ring = _policy(_cfg(N, 24), None, ws_crowd=True)
+    rnn = _policy(env.config, "free", arch="rnn")
+    ring = _policy(_cfg(N, 24), "free", ws_crowd=True)
     assert _raw(env, rnn, rec, 4) == EUNSUPPORTED            # an rnn handle (cavoid_eval_run's)
     assert _raw(env, ring, rec, 4) == EUNSUPPORTED           # a ws_crowd handle: the ring form
     assert _raw(env, pol, rec, 4, frozen=rnn) == EUNSUPPORTED          # an rnn frozen handle beside a weight-sharing learner
@@ -302,8 +286,8 @@ def test_launch_edges_at_the_raw_entry_point():
 def test_fused_ws_is_refused_with_its_reason_where_it_does_not_apply():
     from rl_collision_avoidance_amd.ga3c.evaluate import evaluate, evaluate_fused_unavailable_reason, evaluate_fused_ws_unavailable_reason
     env = _env(64, 4, 7, 21, **dict(MIX, gen_frozen_fraction=0.3))
-    pol = _policy(env.config, None)
-    rnn = _policy(env.config, None, arch="rnn")
+    pol = _policy(env.config, "free")
+    rnn = _policy(env.config, "free", arch="rnn")
     assert "frozen" in evaluate_fused_ws_unavailable_reason(env, pol, None)
     assert "frozen policy" in evaluate_fused_ws_unavailable_reason(env, pol, rnn)
     assert "rnn" in evaluate_fused_ws_unavailable_reason(env, rnn, None)
@@ -317,20 +301,13 @@ def test_fused_ws_is_refused_with_its_reason_where_it_does_not_apply():
     pol.close(); rnn.close(); env.close()
 
 
-def _cli(extra):
-    cmd = [sys.executable, "-m", "rl_collision_avoidance_amd.ga3c.train", "--worlds", "64", "--evaluate", "1", "--arch", "weight_sharing",
-           "--observed", "7", "--steps-per-graph", "4"] + extra
-    env = dict(os.environ)
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    run = subprocess.run(cmd, cwd=ROOT, env=env, timeout=300, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(run.stdout[-3000:])
-    assert run.returncode == 0
-    return run.stdout
+CLI = ["--worlds", "64", "--arch", "weight_sharing", "--observed", "7", "--steps-per-graph", "4"]
 
 
 def test_train_cli_runs_the_kernel_and_prints_the_same_result():
-    fused, plain = _cli(["--fused-ws-evaluate"]), _cli([])
+    fused, plain = tw.cli(CLI + ["--fused-ws-evaluate"]), tw.cli(CLI)
     assert "[Evaluate] fused weight_sharing evaluation kernel (cavoid_eval_run_ws), 4 env steps per launch" in fused
     assert "cavoid_eval_run" not in plain
-    last = lambda out: [l for l in out.splitlines() if l.startswith("[Evaluate] agents ")]
+    last = tw.last_evaluate_line
     assert len(last(fused)) == 1 and last(fused) == last(plain)
+    tw.report_cache(FAMILY)      # (a whole run of this file: 6 shapes x 3 networks, 16 x 32 x 2, the two mixes x 3, two sampled rounds, 4 x 8192: 29)

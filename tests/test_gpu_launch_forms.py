@@ -25,123 +25,19 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests.cfg_regimes import TABLE5, TABLE32, WIDE          # (the tables live beside the other off-default cases)
+from tests.gpu_support import F_PRESENT, INT32_MAX, INT32_MIN, _actions, _make_env, _Reference, _Subject
 
 pytestmark = pytest.mark.gpu
 
-INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
-F_IN_COLL, F_PRESENT = 0x04, 0x20
-ENV_VARS = ("CAVOID_QUAD", "CAVOID_PIPELINE", "CAVOID_RELAY_CONSUMERS", "CAVOID_PREFETCH_POOL", "CAVOID_WPW")
 # the form's switches; CAVOID_QUAD=0 everywhere: a one-step launch (K = 1) is env_kernel's plain step
 FORMS = {"relay": dict(CAVOID_PIPELINE="2"), "pipe": dict(CAVOID_PIPELINE="1"), "loop_pf": dict(CAVOID_PIPELINE="0"),
          "loop": dict(CAVOID_PREFETCH_POOL="0")}
-def _make_env(monkeypatch, W, N, M, seed, env_vars, over):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
-    from rl_collision_avoidance_amd.config import EnvConfig
-
-    class Cfg(EnvConfig):
-        def __init__(self):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
-            self.MAX_NUM_OTHER_AGENTS_OBSERVED = N - 1 if M is None else M
-            EnvConfig.__init__(self)
-    for k in ENV_VARS:                                      # cavoid_create reads them: set for this env only
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("CAVOID_QUAD", "0")
-    for k, v in env_vars.items():
-        monkeypatch.setenv(k, v)
-    try:
-        return BatchedCollisionAvoidanceEnv(W, Cfg(), device="cuda:0", seed=seed, **over)
-    finally:
-        for k in ENV_VARS:
-            monkeypatch.delenv(k, raising=False)
-
-
 def _launch_lengths(N, lookahead=0):
     ring = 8 if N <= 5 else 4                               # relay_ring<N>() (cavoid_relay.hpp)
     lens = [1, 2, 3, 4, 5, 6, ring - 1, ring, ring + 1, 47, 48, 49, 63, 64, 65, 100, 129]
     if lookahead:                                           # a launch holds at most R - 1 steps with the look-ahead rings
         lens = [k for k in lens if k <= lookahead - 1]
     return lens
-
-
-def _actions(rng, T, W, N, num_actions, straight, p_edge=0.03):
-    """(raw, clamped) int32 [T, W, N]: mostly straight ahead (goals are reached, worlds restart), some random, and a few
-    out-of-range values of every kind in the raw set."""
-    a = rng.integers(0, num_actions, size=(T, W, N)).astype(np.int64)
-    a[rng.random((T, W, N)) < 0.6] = straight
-    edge = rng.random((T, W, N)) < p_edge
-    a[edge] = rng.choice(np.array([-1, num_actions, INT32_MIN, INT32_MAX], np.int64), size=int(edge.sum()))
-    return a.astype(np.int32), np.clip(a, 0, num_actions - 1).astype(np.int32)
-
-
-def _bits(t):
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _same(x, y, tag):
-    if torch.equal(_bits(x), _bits(y)):
-        return
-    if x.dim() >= 3 and x.shape[0] > 1:                     # which step, for the message
-        bad = [t for t in range(x.shape[0]) if not torch.equal(_bits(x[t]), _bits(y[t]))]
-        raise AssertionError("%s: first differing step %d of %d (%d differ)" % (tag, bad[0], x.shape[0], len(bad)))
-    raise AssertionError(str(tag))
-
-
-class _Reference(object):
-    """env_kernel, one step per launch, the host-clamped actions; every step's outputs kept for the launch being checked."""
-
-    def __init__(self, env, kmax):
-        W, N, D = env.num_worlds, env.max_agents, env.obs_width
-        self.env = env
-        self.obs = torch.empty((kmax, W, N, D), dtype=torch.float32, device=env.device)
-        self.rew = torch.empty((kmax, W, N), dtype=torch.float32, device=env.device)
-        self.done = torch.empty((kmax, W, N), dtype=torch.uint8, device=env.device)
-        self.go = torch.empty((kmax, W), dtype=torch.uint8, device=env.device)
-        self.coll = torch.zeros((), dtype=torch.bool, device=env.device)
-        self.r_coll = float(env.cfg.reward_collision)
-
-    def run(self, acts):
-        for t in range(acts.shape[0]):
-            o, r, d, g = self.env.step_autoreset(acts[t])
-            assert self.env.last_step_form == ("STEP", 0)
-            self.obs[t].copy_(o); self.rew[t].copy_(r); self.done[t].copy_(d); self.go[t].copy_(g)
-            # a collision: the flag of an agent whose world runs on, or the collision reward (the clip's floor) when it ended the world
-            self.coll |= ((self.env.get_state()[2] & F_IN_COLL) != 0).any() | (r <= self.r_coll).any()
-
-
-class _Subject(object):
-    """One form, one output kind: 'slots' (every step in its slot), 'packed' (every step's packed records), 'last'
-    (out_step_stride = 0)."""
-
-    def __init__(self, env, form, kind, expect, kmax):
-        self.env, self.form, self.kind, self.expect = env, form, kind, expect
-        self.slots = env.new_step_slots(kmax, packed=(kind == "packed")) if kind != "last" else None
-
-    def launch(self, acts):
-        if self.kind == "packed":
-            self.env.step_autoreset_packed(acts, self.slots)
-        else:
-            self.env.step_autoreset_n(acts, slots=self.slots)
-
-    def check(self, ref, K, tag):
-        e = self.env
-        got = e.last_step_form
-        want = ("STEP", 0) if K == 1 else self.expect
-        assert got == want, (tag, "ran %r, expected %r" % (got, want))
-        if self.kind == "slots":
-            s = self.slots
-            _same(s.obs[:K], ref.obs[:K], (tag, "obs")); _same(s.rewards[:K], ref.rew[:K], (tag, "rewards"))
-            _same(s.done[:K], ref.done[:K], (tag, "done")); _same(s.game_over[:K], ref.go[:K], (tag, "game_over"))
-        elif self.kind == "packed":
-            p, D = self.slots.packed, e.obs_width
-            _same(p[:K, ..., :D], ref.obs[:K], (tag, "packed obs")); _same(p[:K, ..., D], ref.rew[:K], (tag, "packed reward"))
-            _same(p[:K, ..., D + 1], ref.done[:K].float(), (tag, "packed done"))
-            _same(self.slots.game_over[:K], ref.go[:K], (tag, "packed game_over"))
-        else:
-            _same(e.obs, ref.obs[K - 1], (tag, "obs")); _same(e.rewards, ref.rew[K - 1], (tag, "rewards"))
-            _same(e.done, ref.done[K - 1], (tag, "done")); _same(e.game_over, ref.go[K - 1], (tag, "game_over"))
-        for name, x, y in zip(("f64", "f32", "flags"), e.get_state(), ref.env.get_state()):
-            _same(x, y, (tag, name))
-        _same(e.episode, ref.env.episode, (tag, "episode"))
 
 
 # id: (N, M, W, cavoid_cfg overrides, case options)

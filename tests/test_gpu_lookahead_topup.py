@@ -15,40 +15,12 @@ torch = pytest.importorskip("torch")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tests.gpu_support import ONE_STEP, _lookahead_env as _env, _same_slots, _same_state
+
 pytestmark = pytest.mark.gpu
 
-# one-step episodes: the time budget of a fresh agent is max(MAX_TIME_RATIO * straight-line time, dt), so a vanishing ratio leaves
-# exactly one step -- every agent runs out at its first step and EVERY world restarts at EVERY step: the boundary of the host's
-# `budget >= n_steps` rule and of "the launch reads no record beyond episode-at-entry + n_steps"
-ONE_STEP = dict(max_time_ratio=1e-9)
 # the short episodes of test_gpu_lookahead.py::test_random_launch_sequences_keep_the_rings_covered (restarts every few steps, not all at once)
 SHORT = dict(max_time_ratio=0.3)
-
-
-def _cfg(N):
-    from rl_collision_avoidance_amd.config import EnvConfig
-
-    class Cfg(EnvConfig):
-        def __init__(self):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
-            EnvConfig.__init__(self)
-    return Cfg()
-
-
-def _env(W, N, seed, lookahead, **over):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
-    kw = dict(gen_pool_size=0, **over)
-    if lookahead:
-        kw["gen_lookahead"] = lookahead
-    return BatchedCollisionAvoidanceEnv(W, _cfg(N), device="cuda:0", seed=seed, **kw)
-
-
-def _same_state(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a.get_state(), b.get_state())) and torch.equal(a.episode, b.episode)
-
-
-def _same_slots(sa, sb, K):
-    return all(torch.equal(getattr(sa, n)[:K], getattr(sb, n)[:K]) for n in ("obs", "rewards", "done", "game_over"))
 
 
 def _relay_launches(W, N, K, R, launches, over, seed=11):

@@ -21,6 +21,7 @@ torch = pytest.importorskip("torch")
 
 import replay as rp
 from tests import orca_regimes as R
+from tests.gpu_support import _orca_env as make_env, _orca_push as _push
 
 pytestmark = pytest.mark.gpu
 
@@ -28,25 +29,6 @@ OBS_TOL, STATE_TOL = 1e-5, 1e-9
 K = R.STEPS
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = ("step", "single", "slots", "packed")
-
-
-def make_env(group, N, rvo_enabled):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
-    from rl_collision_avoidance_amd.config import EnvConfig
-
-    class Cfg(EnvConfig):
-        def __init__(self):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
-            self.MAX_NUM_OTHER_AGENTS_OBSERVED = N - 1
-            EnvConfig.__init__(self)
-    return BatchedCollisionAvoidanceEnv(R.num_worlds(group, N), Cfg(), device="cuda:0", seed=R.SEED, **R.over_of(group, rvo_enabled))
-
-
-def _push(env, run):
-    """the batch as the oracle run started from it, the episode counters back at 0"""
-    env.seed(R.SEED, torch.zeros(env.num_worlds, dtype=torch.int32, device=env.device))
-    st = run.start
-    env.set_state(torch.from_numpy(st.f64).cuda(), torch.from_numpy(st.f32).cuda(), torch.from_numpy(st.flags.view(np.int32)).cuda())
 
 
 class Seen(object):
@@ -212,7 +194,7 @@ import json, sys
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
 import numpy as np, torch
 from tests import orca_regimes as R
-from tests.test_gpu_orca_regimes import make_env, _push
+from tests.gpu_support import _orca_env as make_env, _orca_push as _push
 run = R.Run.of("default", 4)
 env = make_env(R.GROUPS["default"], 4, 1)
 env.reset()

@@ -11,24 +11,9 @@ torch = pytest.importorskip("torch")
 
 from oracle import c_oracle as co
 from tests.cfg_regimes import _cont_actions, _goal_seeking_actions          # (shared with the off-default cases)
+from tests.gpu_support import OBS_TOL, STATE_TOL, _compare_step, _env, _pull, _push
 
 pytestmark = pytest.mark.gpu
-
-OBS_TOL = 1e-5      # tolerance stated by north_star for float observations / rewards
-STATE_TOL = 1e-9    # float64 world state (positions, heading, time) after free-running both sides
-
-
-def _env(W, N, M=None, seed=0, **over):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
-    from rl_collision_avoidance_amd.config import EnvConfig
-
-    class Cfg(EnvConfig):
-        def __init__(self):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
-            self.MAX_NUM_OTHER_AGENTS_OBSERVED = N - 1 if M is None else M
-            EnvConfig.__init__(self)
-    return BatchedCollisionAvoidanceEnv(W, Cfg(), device="cuda:0", seed=seed, **over)
-
 
 DEFAULT_POOL = 65536     # cavoid_default_cfg's gen_pool_size
 
@@ -37,38 +22,6 @@ def _oracle(N, M=None, gen_min=None, nonl=0.0, pool=DEFAULT_POOL, **over):
     cfg = co.default_cfg(N, N - 1 if M is None else M, **over)
     gen = co.default_gen(N if gen_min is None else gen_min, N, nonl, pool_size=pool)
     return cfg, gen
-
-
-def _push(env, st):
-    env.set_state(torch.from_numpy(st.f64).cuda(), torch.from_numpy(st.f32).cuda(),
-                  torch.from_numpy(st.flags.view(np.int32)).cuda())
-
-
-def _pull(env):
-    f64, f32, fl = env.get_state()
-    return f64.cpu().numpy(), f32.cpu().numpy(), fl.cpu().numpy().view(np.uint32)
-
-
-def _compare_step(tag, env_out, ora_out, env, st):
-    obs, rew, done, go = [t.cpu().numpy() for t in env_out]
-    oobs, orew, odone, ogo = ora_out
-    assert np.array_equal(done, odone), tag
-    assert np.array_equal(go, ogo), tag
-    f64, f32, fl = _pull(env)
-    assert np.array_equal(fl, st.flags), tag                       # every flag bit, incl. collision / goal
-    assert np.array_equal(f32, st.f32), tag
-    np.testing.assert_allclose(f64, st.f64, rtol=0, atol=STATE_TOL, err_msg=str(tag))
-    np.testing.assert_allclose(rew, orew, rtol=0, atol=OBS_TOL, err_msg=str(tag))
-    # heading_ego_frame (col 3) is an ANGLE: the reference's wrap() has its branch cut at +-pi, and an
-    # agent that has just run over its goal centre sits exactly on it (goal dead astern), where a
-    # 1-ulp atan2 difference turns -pi into +pi.  Compare that column on the circle; all else plain.
-    dh = np.abs(obs[..., 3].astype(np.float64) - oobs[..., 3])
-    dh = np.minimum(dh, np.abs(dh - 2.0 * np.pi))
-    assert dh.max() <= OBS_TOL, (tag, dh.max())
-    keep = np.ones(obs.shape[-1], bool)
-    keep[3] = False
-    np.testing.assert_allclose(obs[..., keep], oobs[..., keep], rtol=0, atol=OBS_TOL, err_msg=str(tag))
-    assert np.array_equal(obs[..., :2], oobs[..., :2].astype(np.float32)), tag   # is_learning, num_other exact
 
 
 @pytest.mark.parametrize("N,M,sort,nonl,gen_min", [

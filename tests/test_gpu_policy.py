@@ -1,6 +1,6 @@
 """GPU parity of the fused policy kernel (HIP, through the C ABI: cavoid_policy_*) against the plain PyTorch
 float32 ``NetworkVP_rnn.forward`` of the same weights -- a floating-point kernel, so the torch fp32 graph
-is its reference (tolerances below); the action selection is integer work and is checked exactly."""
+is its reference (tolerances: tests/policy_support.py); the action selection is integer work and is checked exactly."""
 import numpy as np
 import pytest
 
@@ -8,40 +8,9 @@ torch = pytest.importorskip("torch")
 
 from oracle.cavoid_oracle import philox4x32
 from tests.policy_regimes import assert_gradients_match
+from tests.policy_support import P_TOL, V_TOL, _check_forms_bit_identical, _inputs, _net
 
 pytestmark = pytest.mark.gpu
-
-P_TOL = 2e-5       # softmax probabilities (absolute; p <= 1): f32 MFMA vs rocBLAS f32, different summation order
-V_TOL = 2e-4       # value head (|v| = O(1)); absolute + relative
-
-
-def _net(M, seed=0, min_policy=0.0, normalize=True, A=11):
-    from rl_collision_avoidance_amd.config import EnvConfig
-    from rl_collision_avoidance_amd.ga3c.network import NetworkVP_rnn
-
-    class Cfg(EnvConfig):
-        def __init__(self):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = M + 1
-            EnvConfig.__init__(self)
-    cfg = Cfg()
-    cfg.MIN_POLICY = min_policy
-    cfg.NORMALIZE_INPUT = normalize
-    net = NetworkVP_rnn(cfg, num_actions=A, seed=seed).cuda()
-    g = torch.Generator().manual_seed(seed + 100)
-    with torch.no_grad():                      # non-zero biases so that every bias path is exercised
-        for name, prm in net.named_parameters():
-            if name.endswith("_bias"):
-                prm.copy_((torch.rand(prm.shape, generator=g) - 0.5).to(prm.device))
-    return net
-
-
-def _inputs(net, B, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    M = net.max_others
-    x = torch.randn((B, net.input_size), generator=g) * scale * net.std.cpu() + net.avg.cpu()
-    x[:, 0] = torch.randint(0, M + 1, (B,), generator=g).to(torch.float32)
-    return x.cuda()
-
 
 @pytest.mark.parametrize("M,B", [(3, 1), (3, 63), (3, 64), (3, 130), (3, 32768), (9, 1000), (19, 517), (1, 200)])
 def test_forward_matches_torch_fp32(M, B):
@@ -508,32 +477,3 @@ def test_other_tile_to_wavefront_forms_are_bit_identical(M, B, scale, form, monk
     net = _net(M, seed=60 + M)
     x = _inputs(net, B, seed=11, scale=scale)
     _check_forms_bit_identical(net, x, M, B, form, monkeypatch)
-
-
-def _check_forms_bit_identical(net, x, M, B, form, monkeypatch):
-    """the body of test_other_tile_to_wavefront_forms_are_bit_identical (tests/test_gpu_policy_loss_heads.py runs it on a confident
-    network too); returns the default form's probabilities"""
-    from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
-    g = torch.Generator().manual_seed(3)
-    x[:, 0] = torch.randint(0, M + 1, (B,), generator=g).float().cuda()
-    x[: B // 3, 0] = float(M)                               # tiles in which every row is live at every LSTM step
-    x[B // 3: B // 3 + 70, 0] = 1.0                         # ... and a tile with fewer steps than its neighbour (duo: the idle barrier pairs)
-    monkeypatch.setenv("CAVOID_POLICY_FORM", "quad")
-    pol4 = FusedPolicy(net, seed=77)
-    monkeypatch.setenv("CAVOID_POLICY_FORM", form)
-    pol8 = FusedPolicy(net, seed=77)
-    a4, p4, v4 = pol4.act(x)
-    a8, p8, v8 = pol8.act(x)
-    assert torch.equal(p4, p8) and torch.equal(v4, v8) and torch.equal(a4, a8)
-    assert float((p4.sum(dim=1) - 1.0).abs().max()) < 1e-5 and (B < 100 or a4.float().std().item() > 0)
-    idx = torch.zeros(B, dtype=torch.int32, device="cuda")
-    listed = torch.randperm(B, generator=torch.Generator().manual_seed(1))[: B // 2 + 3].to(torch.int32).cuda()
-    idx[: listed.numel()] = listed
-    count = torch.tensor([listed.numel()], dtype=torch.int32, device="cuda")
-    a4r, p4r, v4r = pol4.act(x, rows=(idx, count))
-    a8r, p8r, v8r = pol8.act(x, rows=(idx, count))
-    assert torch.equal(p4r, p8r) and torch.equal(v4r, v8r) and torch.equal(a4r, a8r)
-    count.zero_()                                            # an empty list: every workgroup leaves at once
-    a0, p0, v0 = pol8.act(x, rows=(idx, count))
-    assert float(p0.abs().sum()) == 0.0
-    return p4

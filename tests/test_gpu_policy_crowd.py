@@ -7,8 +7,8 @@ import ctypes as C
 import pytest
 import torch
 
-from tests.test_gpu_parity import _env
-from tests.test_gpu_policy import P_TOL, V_TOL, _inputs, _net
+from tests.gpu_support import _env
+from tests.policy_support import P_TOL, V_TOL, _inputs, _net
 
 pytestmark = pytest.mark.gpu
 

@@ -17,7 +17,7 @@ torch = pytest.importorskip("torch")
 
 from oracle.cavoid_oracle import philox4x32
 from tests import policy_regimes as R
-from tests.test_gpu_policy import P_TOL, _check_forms_bit_identical
+from tests.policy_support import P_TOL, _check_forms_bit_identical
 
 pytestmark = pytest.mark.gpu
 
@@ -207,10 +207,10 @@ def test_fused_actor_equals_step_by_step_on_a_confident_network():
     """The actor kernel inlines the same split_select_action next to its env step; test_fused_actor_equals_step_by_step only ever
     feeds it near-uniform rows.  Its networks have zero biases, hence the larger gain (p_kernel x 1000)."""
     from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedPolicy
-    from tests.test_gpu_actor import _make, _same
+    from tests.actor_twins import make, same as _same
     W, N = 512, 4
-    env_a, net_a, pol_a, a = _make(W, N, 21, False)
-    env_b, net_b, pol_b, b = _make(W, N, 21, False)
+    env_a, net_a, pol_a, a = make(W, N, None, 21)              # (tests/test_gpu_actor.py's twins)
+    env_b, net_b, pol_b, b = make(W, N, None, 21)
     for net, pol in ((net_a, pol_a), (net_b, pol_b)):
         with torch.no_grad():
             net.p_kernel.mul_(R.GAIN_ACTOR)

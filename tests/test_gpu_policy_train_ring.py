@@ -162,7 +162,7 @@ def test_ring_trainer_learns_like_the_autograd_trainer():
     FusedPolicy then acts on the updated weights (tests/test_gpu_policy_crowd.py's forward bounds)"""
     from rl_collision_avoidance_amd.ga3c.network import A3CTrainer
     from rl_collision_avoidance_amd.ga3c.policy_kernel import FusedA3CTrainer
-    from tests.test_gpu_policy import P_TOL, V_TOL
+    from tests.policy_support import P_TOL, V_TOL
     M, B = 31, 256
     net_a = _crowd_net(M, seed=31)
     net_b = copy.deepcopy(net_a)

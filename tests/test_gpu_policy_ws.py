@@ -11,8 +11,8 @@ import torch
 
 from oracle.cavoid_oracle import philox4x32
 from tests.policy_regimes import assert_gradients_match
-from tests.test_gpu_parity import _env
-from tests.test_gpu_policy import P_TOL, V_TOL, _inputs
+from tests.gpu_support import _env
+from tests.policy_support import P_TOL, V_TOL, _inputs
 
 pytestmark = pytest.mark.gpu
 

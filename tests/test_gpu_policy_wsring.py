@@ -67,7 +67,7 @@ def _case(M, B):
 
 
 def _check32(p, v, p_ref, v_ref):
-    from tests.test_gpu_policy import P_TOL, V_TOL
+    from tests.policy_support import P_TOL, V_TOL
     assert torch.isfinite(p).all() and torch.isfinite(v).all()
     assert (p - p_ref).abs().max().item() <= P_TOL
     assert ((v - v_ref).abs() <= V_TOL + V_TOL * v_ref.abs()).all()

@@ -16,7 +16,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.test_gpu_launch_forms import _Reference, _Subject, _actions, _make_env, _same
+from tests.gpu_support import ONE_STEP, _actions, _lookahead_env as _env, _make_env, _Reference, _same_bits as _same, _same_slots, _same_state, _Subject
 
 pytestmark = pytest.mark.gpu
 
@@ -162,7 +162,6 @@ def test_lookahead_rings_with_the_top_up_in_both_tiles(W, monkeypatch):
     six consecutive launches of K = R / 2 steps with every world restarting at every step, held bitwise to generation inside the step as
     tests/test_gpu_lookahead_topup.py does -- the rings wrap three times; a slot one T left stale or wrote for the wrong tile shows as a
     wrong scenario.  Not one refill launch follows the first fill.  W = 40: an odd tile count, the last workgroup has one tile."""
-    from tests.test_gpu_lookahead_topup import ONE_STEP, _env, _same_slots, _same_state
     N, K, R, launches, seed = 4, 8, 16, 6, 11
     monkeypatch.setenv("CAVOID_RELAY_TILES", "2")
     monkeypatch.setenv("CAVOID_RELAY_CONSUMERS", "4")

@@ -9,21 +9,11 @@ torch = pytest.importorskip("torch")
 
 from oracle import rollout_oracle as ro
 from tests import rollout_scripts as rs
+from tests.gpu_support import _default_device_env as _make
 
 pytestmark = pytest.mark.gpu
 
 R_TOL = 1e-6      # n-step returns: float64 on both sides, emitted as float32
-
-
-def _make(W, N, seed, **over):
-    from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
-    from rl_collision_avoidance_amd.config import EnvConfig
-
-    class Cfg(EnvConfig):
-        def __init__(self):
-            self.MAX_NUM_AGENTS_IN_ENVIRONMENT = N
-            EnvConfig.__init__(self)
-    return BatchedCollisionAvoidanceEnv(W, Cfg(), seed=seed, **over)
 
 
 @pytest.mark.parametrize("fuse_env_push", ["1", "0"])      # env.step + bookkeeping as ONE launch (cavoid_step_push, the default) / as three

@@ -285,7 +285,7 @@ def test_compaction_without_room(which):
 # ---- the same paths through BatchedRollout ----------------------------------------------------------------------------------------
 def _python_rollout(monkeypatch, fuse="0", steps=120, **kw):
     from rl_collision_avoidance_amd.ga3c.rollout import BatchedRollout
-    from tests.test_gpu_rollout import _make
+    from tests.gpu_support import _default_device_env as _make
     monkeypatch.setenv("CAVOID_FUSE_ENV_PUSH", fuse)
     W, N, seed = 96, 4, 3
     env = _make(W, N, seed, gen_min_agents=2, gen_nonlearning_fraction=0.3)

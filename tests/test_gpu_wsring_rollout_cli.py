@@ -7,7 +7,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from tests.test_gpu_parity import _env
+from tests.gpu_support import _env
 
 pytestmark = pytest.mark.gpu
 

@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes, _no_gpu
+from tests.host_support import LLVM, ROOT, _kernel_notes, _no_gpu
 
 
 def _policy_create(m):

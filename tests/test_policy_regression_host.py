@@ -15,7 +15,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests import regression_regimes as G
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes
+from tests.host_support import LLVM, ROOT, _kernel_notes
 
 NEW_SYMBOLS = ("cavoid_policy_train_regression", "cavoid_policy_train_regression_ws")
 HEADER = os.path.join(ROOT, "include", "cavoid.h")

@@ -10,7 +10,7 @@ import tempfile
 
 import pytest
 
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes, _no_gpu
+from tests.host_support import LLVM, ROOT, _kernel_notes, _no_gpu
 
 NEW_SYMBOLS = ("cavoid_policy_create_ws", "cavoid_policy_load_ws", "cavoid_policy_train_ws")
 HEADER = os.path.join(ROOT, "include", "cavoid.h")

@@ -11,7 +11,7 @@ import tempfile
 
 import pytest
 
-from tests.test_crowd_host import LLVM, ROOT, _kernel_notes, _no_gpu
+from tests.host_support import LLVM, ROOT, _kernel_notes, _no_gpu
 
 HEADER = os.path.join(ROOT, "include", "cavoid.h")
 CSRC = os.path.join(ROOT, "rl_collision_avoidance_amd", "csrc")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Which generator seeds the oracle cases of tests/test_gpu_crowd_rvo.py::test_crowd_orca_parity_with_the_oracle can take, decided by
-code: for every case and seed the test's own trajectory is run (env.step against the float64 oracle, tests/test_gpu_parity.py's
+code: for every case and seed the test's own trajectory is run (env.step against the float64 oracle, tests/gpu_support.py's
 _compare_step); at the first step that misses the bar every world that left the oracle goes through
 tests/replay.py::classify_divergence -- with env.step and the oracle's step in place of the auto-reset step, since the test steps
 without restarts, the oracle's states and actions of the last 32 steps as history (the drift test), and --trials sign patterns of the
@@ -23,8 +23,7 @@ import replay
 from oracle import c_oracle as co
 from rl_collision_avoidance_amd.batched_env import BatchedCollisionAvoidanceEnv
 from rl_collision_avoidance_amd.config import EnvConfig
-from tests.test_gpu_crowd_rvo import _infeasible_first_programmes
-from tests.test_gpu_parity import _compare_step, _goal_seeking_actions, _pull, _push
+from tests.gpu_support import _compare_step, _goal_seeking_actions, _infeasible_first_programmes, _pull, _push
 
 # (N, gen_min, nonlearning, static, rvo, scenario mode, W, time-outs expected): the test's table
 CASES = [(17, 17, .6, .2, .6, 1, 96, True), (20, 10, .6, .2, .6, 1, 96, True), (24, 24, .7, 0., 1., 0, 64, False), (33, 30, .5, .2, .6, 1, 48, True),
